@@ -6,7 +6,7 @@ that is already resident in HBM.  Default workload: GibbsRtIrt, nSubj=100000, nI
 the configuration the north-star target is quoted on); data per setDataRtIrt's distributions, fixed seed.
 
 Headline = the fp64 engine (`dtype: f64`): the reference's arithmetic is Float64 throughout (src/Base.pl.jl:67-78, the Post arrays).
-The fp32 fast mode (fp32 cell arithmetic, fp64 accumulation) is measured in the same invocation on the same resident inputs and
+The fp32 fast mode (fp32 cell arithmetic, fp64 accumulation) is measured (--full) in the same invocation on the same resident inputs and
 carried in the same JSON line as the nested object `fp32`.
 
 N GPUs = N independent chains, one per GPU, no data-path collective: "scaling": "weak".  What is measured at N > 1 is the path a Julia
@@ -16,7 +16,7 @@ devices, one ncclAllReduce; `rccl_ranks` is that communicator's ncclCommCount, `
 runs it directly; under `torch.distributed.run --nproc-per-node N` (the driver's launch) rank 0 drives the farm over the N devices and the other ranks
 only take part in the barriers and the MAX-reduction of the time (torch.distributed over gloo: they never touch a GPU).  `--multiprocess` keeps the
 older layout (one process per GPU, torch.distributed "nccl", chain_id = rank; `python bench.py --gpus N --multiprocess` spawns its ranks itself).
-At N > 1 the line also carries BASELINE.json configs[4] (500000 x 100, nChain = N, one chain per GPU) as `configs4_value` / `configs4_ms_per_step`
+At N > 1 a --full line also carries BASELINE.json configs[4] (500000 x 100, nChain = N, one chain per GPU) as `configs4_value` / `configs4_ms_per_step`
 and the nested object `configs4`.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
@@ -24,6 +24,17 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
                   HIP events on the engine's stream, against the 8 TB/s HBM peak;
   cpu_baseline -- the CPU oracle (kind "port": fp64 C restatement of the reference's un-fused schedule, 1 thread) timed on this
                   host for a bounded number of sweeps of the SAME workload.  The reference itself is Julia and cannot run here.
+
+A plain run measures the headline only: set-up, the untimed clock warm-up, W warm-up steps, K timed steps, the line.  Everything else -- the
+cold measurement (ms_per_step_cold), the nested fp32 leg, two chains on one GPU, the CPU baselines, configs[4] and the multi-GPU self-check -- runs
+with --full only (the --no-* flags still take single items out of a --full run).
+
+Determinism: after the time-based clock warm-up every chain is rewound to a fresh engine's start (erm_set_seed with the same seed restarts the
+sweep counter that addresses the random streams; erm_set_state puts the initial state back) and runs min(K, 64) sweeps, then one untimed call of
+exactly K sweeps (which captures every graph the timed call replays), so the W + K steps compute the same chain in every run with the same
+arguments.  --dump-outputs DIR writes what the timed steps computed: the state after the last step (<field>.npy) and the posterior means over the
+timed steps (mean_<field>.npy), float64.  At N > 1 through the chain farm the states are stacked over chains (first axis) and the means are the
+farm's reduced Post.mean; with --multiprocess (and --shard) rank 0 writes its own chain (its own rows) only, nothing is gathered for the dump.
 """
 from __future__ import annotations
 
@@ -79,7 +90,7 @@ def parse_args(argv=None):
     ap.add_argument("--lanes-per-row", type=int, default=0)
     ap.add_argument("--block-threads", type=int, default=0)
     ap.add_argument("--grid-blocks", type=int, default=0)
-    ap.add_argument("--cpu-sweeps", type=int, default=-1, help="oracle sweeps for cpu_baseline (-1 = auto ~15 s, 0 = skip)")
+    ap.add_argument("--cpu-sweeps", type=int, default=-1, help="--full: oracle sweeps for cpu_baseline (-1 = auto ~15 s, 0 = skip)")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket sweep-kernel launches with HIP events")
     ap.add_argument("--clock-warmup-ms", type=float, default=300.0, help="after the W warm-up steps, keep the GPU busy with further UNTIMED sweeps of the same engine for "
                                                                          "this long before the timed region (a few ms of work do not bring an idle MI355X to its sustained clock; 0 = off)")
@@ -91,7 +102,48 @@ def parse_args(argv=None):
     ap.add_argument("--no-self-check", action="store_true", help="N > 1: skip the farm's self-validation (communicator size, farm mean = separately run engines, per-chain time)")
     ap.add_argument("--no-two-chains", action="store_true", help="N = 1: skip the nested measurement of TWO independent chains sharing the one GPU (the chain farm on devices [0, 0])")
     ap.add_argument("--no-cold", action="store_true", help="skip the extra cold measurement (the same W + K steps from an idle device, before the clock warm-up)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the cold measurement, the fp32 leg, two chains on one GPU, "
+                                                        "the CPU baselines, configs[4] and the multi-GPU self-check (a plain run skips all of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed steps computed as DIR/<name>.npy (float64): the state after the last step and the posterior means")
+    args = ap.parse_args(argv)
+    if not args.full and args.cpu_sweeps not in (-1, 0):
+        ap.error("--cpu-sweeps N times the CPU baseline, which runs with --full only")
+    if not args.full:
+        args.no_cold = args.no_fp32 = args.no_two_chains = args.no_configs4 = args.no_self_check = True
+        args.cpu_sweeps = 0
+    return args
+
+
+# what a caller of erm_run / erm_farm_run gets back, by model (erm_get_state / erm_get_mean fields)
+def output_fields(model):
+    if model == "mlirt":
+        return ("theta", "a", "b", "beta")
+    f = ["theta", "zeta", "a", "b", "lambda_", "sig2t", "sigp", "rho" if model in ("crossqr", "cross") else "beta"]
+    return f + (["nu"] if model in ("latentqr", "crossqr") else [])
+
+
+DUMP_MAX_ELEMS = 1 << 20      # a larger output (the Qr models' nu, N x J) is written as a fixed seeded sample of this many entries: 64 MB in all at most
+
+
+def dump_outputs(path, model, state, mean):
+    """state / mean: {field: float64 array}; writes <field>.npy and mean_<field>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for prefix, arrs in (("", state), ("mean_", mean)):
+        for k in output_fields(model):
+            v = arrs.get(k)
+            if v is None:
+                continue
+            v = np.asarray(v, dtype=np.float64)
+            if v.size > DUMP_MAX_ELEMS:
+                idx = np.sort(np.random.default_rng(2024).choice(v.size, DUMP_MAX_ELEMS, replace=False))
+                v = v.reshape(-1)[idx]
+            np.save(os.path.join(path, prefix + k.rstrip("_") + ".npy"), v)
+
+
+def rewind_fields(model):
+    """The state erm_set_state takes back for a rewind (nu is redrawn from the state by the first sweep after erm_set_seed)."""
+    return [k for k in output_fields(model) if k != "nu"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -271,6 +323,7 @@ def measure(pkg, ge_mod, torch, dist, args, model, N, J, F, precision, data, st,
     else:
         eng.set_data(Y, logT, X)   # inputs resident in HBM from here on
     eng.set_state(**{("lambda_" if k == "lam" else k): v for k, v in st.items()})
+    start = eng.get_state(which=rewind_fields(model))       # the chain's start, put back after the clock warm-up
 
     def barrier():
         if dist is not None:
@@ -297,6 +350,14 @@ def measure(pkg, ge_mod, torch, dist, args, model, N, J, F, precision, data, st,
             eng.reset_trace()
             eng.run(chunk)
             spun += chunk
+        # rewind (the number of sweeps spun depends on the clock): the same seed restarts the streams (and drops the captured graphs), the start
+        # state goes back; one chunk draws the statistics of the restored state, then one call of exactly K sweeps captures every graph the timed
+        # call replays (at K > 32 the 32-sweep graph and the tail graph of K % 32 sweeps)
+        eng.set_seed(eng.cfg.seed)
+        eng.set_state(**start)
+        for n in (chunk, args.steps):
+            eng.reset_trace()
+            eng.run(n)
         eng.reset_trace()
     # 3. the W warm-up steps (= the burn-in rows), then EXACTLY K timed steps, all of them post-burn-in
     if args.warmup > 0:
@@ -345,6 +406,8 @@ def measure_farm(pkg, torch, dist, args, model, N, J, F, precision, data, n_dev,
             farm.set_data(*data)   # inputs resident in HBM from here on (every chain its own copy, uploaded by the chain's host thread)
         for l in range(n_dev):     # every chain its own setInitialValues
             farm.set_state(l, **{("lambda_" if k == "lam" else k): v for k, v in init_state(model, N, J, F, l).items()})
+        keep = rewind_fields(model)
+        starts = [{k: v for k, v in farm.get_state(l).items() if k in keep} for l in range(n_dev)]
     dt_cold = None
     if not args.no_cold and args.clock_warmup_ms > 0:
         if driver and args.warmup > 0:
@@ -365,6 +428,12 @@ def measure_farm(pkg, torch, dist, args, model, N, J, F, precision, data, n_dev,
             farm.reset_trace()
             farm.run(chunk)
             spun += chunk
+        farm.set_seed(farm.cfg.seed)      # rewind, as in measure()
+        for l in range(n_dev):
+            farm.set_state(l, **starts[l])
+        for n in (chunk, args.steps):
+            farm.reset_trace()
+            farm.run(n)
         farm.reset_trace()
     if driver and args.warmup > 0:
         farm.run(args.warmup)
@@ -534,10 +603,13 @@ def main_farm(args, world_env):
     dt, dt_cold, ftm, etm, farm = measure_farm(model=model, N=N, J=J, F=F, precision=prec, data=data, trace=args.trace, **common)
     gather = None
     if driver:      # Post.mean over iterations and chains: the ONE collective of the path (the library's RCCL all-reduce)
-        farm.get_mean()
+        mean = farm.get_mean()
         g = farm.timing()
         gather = {"gather_ms": g["gather_ms"], "allreduce_ms": g["allreduce_ms"], "comm_init_ms": g["comm_init_ms"], "rccl_ranks": g["rccl_ranks"], "n_devices": g["n_devices"], "used_rccl": farm.used_rccl,
                   "post_count": farm.post_count}
+        if args.dump_outputs:
+            states = [farm.get_state(l) for l in range(n_dev)]
+            dump_outputs(args.dump_outputs, model, {k: np.stack([s[k] for s in states]) for k, v in states[0].items() if v is not None}, mean)
         del farm
     fp32 = None
     if prec == "f64" and not args.no_fp32:
@@ -687,6 +759,8 @@ def main():
         pkg.parallel.gather_posterior_summaries(P, eng.post_count, device=None if rehearse else f"cuda:{local_rank}")
         torch.cuda.synchronize()
         gather_ms = (time.perf_counter() - g0) * 1e3
+    if args.dump_outputs and rank == 0:      # (--shard: rank 0's rows)
+        dump_outputs(args.dump_outputs, model, eng.get_state(), eng.get_mean())
     del eng
 
     # the fp32 fast mode on the same resident-input protocol (every rank takes part: the barriers are collective)

@@ -83,7 +83,7 @@ def test_two_ranks_with_the_hip_engine_and_a_collective_on_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "ERM_BENCH_LAUNCH_ONLY"):
         e.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--multiprocess", "--steps", "12", "--warmup", "4", "--nsubj", "4000", "--nitem", "12",
-                        "--clock-warmup-ms", "0"], env=e, capture_output=True, text=True, timeout=900)
+                        "--clock-warmup-ms", "0", "--full"], env=e, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][0])
     assert out["n_gpus"] == 2 and out["config"]["chains"] == 2 and out["config"]["collective_backend"] == "gloo" and out["scaling"] == "weak"
@@ -103,7 +103,7 @@ def test_gpus_n_measures_the_c_abi_chain_farm():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "ERM_BENCH_LAUNCH_ONLY"):
         e.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--nsubj", "4000", "--nitem", "12",
-                        "--clock-warmup-ms", "20"], env=e, capture_output=True, text=True, timeout=900)
+                        "--clock-warmup-ms", "20", "--full"], env=e, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][0])
     c = out["config"]
@@ -120,3 +120,82 @@ def test_gpus_n_measures_the_c_abi_chain_farm():
     sc = out["self_check"]
     assert sc["ok"] and sc["rccl_ranks"] == sc["rccl_ranks_expected"] == 1 and sc["farm_mean_vs_separate_engines_max_rel_err"] <= 1e-12 and sc["post_rows"] == sc["post_rows_expected"] == 2 * 16
     assert "not a BASELINE.json configuration" in c["workload"]
+
+
+def test_plain_run_measures_the_headline_only():
+    """A plain run skips every measurement the headline does not need; --full brings them back, and a --no-* flag still takes one out of it."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.no_cold and a.no_fp32 and a.no_two_chains and a.no_configs4 and a.no_self_check and a.cpu_sweeps == 0
+    f = bench.parse_args(["--full"])
+    assert f.full and not (f.no_cold or f.no_fp32 or f.no_two_chains or f.no_configs4 or f.no_self_check) and f.cpu_sweeps == -1
+    f = bench.parse_args(["--full", "--no-fp32", "--cpu-sweeps", "3"])
+    assert f.no_fp32 and not f.no_cold and f.cpu_sweeps == 3
+    assert bench.parse_args(["--cpu-sweeps", "0"]).cpu_sweeps == 0
+    with pytest.raises(SystemExit):             # the CPU baseline runs with --full only: not silently dropped
+        bench.parse_args(["--cpu-sweeps", "5"])
+
+
+def test_dump_outputs_writes_float64_arrays_and_samples_large_ones(tmp_path):
+    import numpy as np
+    import bench
+    big = bench.DUMP_MAX_ELEMS + 7
+    state = dict(theta=np.arange(5.0), a=np.ones(3), lambda_=np.full(3, 2.0), beta=None, nu=np.arange(big, dtype=np.float64), sigp=np.eye(2).reshape(-1))
+    mean = dict(state, theta=np.arange(5.0) / 2)
+    bench.dump_outputs(str(tmp_path), "crossqr", state, mean)
+    names = sorted(p.name for p in tmp_path.iterdir())
+    assert names == sorted(f"{p}{k}.npy" for p in ("", "mean_") for k in ("theta", "a", "lambda", "nu", "sigp"))
+    assert np.array_equal(np.load(tmp_path / "lambda.npy"), np.full(3, 2.0)) and np.array_equal(np.load(tmp_path / "mean_theta.npy"), np.arange(5.0) / 2)
+    nu = np.load(tmp_path / "nu.npy")
+    assert nu.dtype == np.float64 and nu.size == bench.DUMP_MAX_ELEMS and np.all(np.diff(nu) > 0)      # a sorted sample of distinct entries
+    bench.dump_outputs(str(tmp_path / "again"), "crossqr", state, mean)
+    assert np.array_equal(np.load(tmp_path / "again" / "nu.npy"), nu)                                   # the same sample every time
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_chain_in_every_run(tmp_path):
+    """--dump-outputs: the state after the last timed step and the posterior means of the timed steps.  The clock warm-up spins a number of sweeps that
+    depends on the clock; the rewind after it makes runs with the same arguments compute the same chain -- here even with warm-ups of different lengths --
+    and that chain is the one an engine driven directly computes: a fresh engine, min(K, 64) sweeps, one call of K sweeps, then the W warm-up and the K
+    timed steps.  K = 70 > 64: the call that captures the timed call's graphs is longer than the rewind's first chunk."""
+    import numpy as np
+    import __graft_entry__ as ge
+    import bench
+    N, J, F, W, K = 20000, 20, 3, 3, 70
+    e = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "ERM_BENCH_LAUNCH_ONLY", "ERM_BENCH_REHEARSE"):
+        e.pop(k, None)
+    dirs = []
+    for k, ms in enumerate(("60", "15")):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--nsubj", str(N), "--nitem", str(J),
+                            "--nfeat", str(F), "--clock-warmup-ms", ms, "--dump-outputs", str(d)], env=e, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][0])
+        assert out["steps"] == K and out["ms_per_step"] > 0 and out["dtype"] == "f64" and out["untimed_clock_warmup"]["sweeps"] > 0
+        assert not {"fp32", "cpu_baseline", "two_chains_one_gpu", "ms_per_step_cold"} & set(out)      # a plain run: the headline only
+        dirs.append(d)
+    # the same chain driven directly through the engine
+    pkg = ge.load_package()
+    L = pkg._lib
+    Y, logT, X = bench.make_data(pkg, "rtirt", N, J, F, seed=1234)
+    eng = L.Engine(model=L.MODEL_RTIRT, n_item=J, n_subj=N, n_feat=F, n_iter=W + K, n_chain=1, n_burnin=W, cov2one=1, q_rt=0.85, seed=1234,
+                   chain_id=pkg.parallel.rank_chain_id(0), device=0, precision=L.PREC_F64, trace_mode=L.TRACE_FULL, profile=1)
+    eng.set_data(Y, logT, X)
+    eng.set_state(**{("lambda_" if k == "lam" else k): v for k, v in bench.init_state("rtirt", N, J, F, 0).items()})
+    for n in (min(K, 64), K):
+        eng.reset_trace()
+        eng.run(n)
+    eng.reset_trace()
+    eng.run(W)
+    eng.run(K)
+    want = {"": eng.get_state(), "mean_": eng.get_mean()}
+    eng.close()
+    for name in bench.output_fields("rtirt"):
+        for p in ("", "mean_"):
+            f = p + name.rstrip("_") + ".npy"
+            x, y = np.load(dirs[0] / f), np.load(dirs[1] / f)
+            assert x.dtype == np.float64 and np.all(np.isfinite(x)) and np.array_equal(x, y), f
+            assert np.array_equal(x, want[p][name]), f
+    assert np.load(dirs[0] / "theta.npy").shape == (N,) and np.load(dirs[0] / "a.npy").shape == (J,)

@@ -7,7 +7,7 @@ ARGS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS+=("$1"); shift; done; s
 for k in 1 2 3; do
   for L in "$@"; do
     if [ "$L" = "-" ]; then unset ERM_LIB_PATH; else export ERM_LIB_PATH=$PWD/$L; fi
-    python bench.py --cpu-sweeps 0 "${ARGS[@]}" 2>/dev/null | python -c "
+    python bench.py --full --cpu-sweeps 0 "${ARGS[@]}" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline()); f=d.get('fp32') or {}
 print('%-40s %s us/sweep %.2f kernel %.2f%s' % ('$L', d['dtype'], 1e3*d['ms_per_step'], d['roofline']['launch_us'], ('   f32 %.2f kernel %.2f' % (1e3*f['ms_per_step'], f['roofline']['launch_us'])) if f else ''))"

@@ -4,7 +4,7 @@
 # Output: gpurun_out/<tag>/lines/<name>.json, one JSON line each.
 TAG=${1:-round2}
 OUT=gpurun_out/$TAG/lines; mkdir -p $OUT
-run() { n=$1; shift; timeout -k 10 500 python bench.py "$@" 2>$OUT/$n.err | tail -1 > $OUT/$n.json; echo "$n $(grep -o '"ms_per_step": [0-9.]*' $OUT/$n.json | head -2 | tr '\n' ' ')"; }
+run() { n=$1; shift; timeout -k 10 500 python bench.py --full "$@" 2>$OUT/$n.err | tail -1 > $OUT/$n.json; echo "$n $(grep -o '"ms_per_step": [0-9.]*' $OUT/$n.json | head -2 | tr '\n' ' ')"; }
 run line
 run driver20 --steps 20 --warmup 5 --cpu-sweeps 0
 for m in mlirt latentqr crossqr null cross latent; do run $m --model $m --cpu-sweeps 0; done
