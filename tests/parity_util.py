@@ -227,3 +227,158 @@ def max_rel_err(res, floor=1e-6):
     e.append(rel_err(res["dev_qr"], res["orc"]["qr"], floor).max())
     e.append(rel_err(res["dev_ll"], res["orc"]["ll"], floor).max())
     return float(max(e))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Adversarial data sets: the regions real data reaches and make_problem's defaults do not (separated items, saturated states, degenerate
+# response patterns, raw log-millisecond times, covariates with a large offset).  Every one is a valid input to erm_set_data / erm_set_state.
+EXTREME_KINDS = ("separated", "saturated", "degenerate", "rt_offset", "x_offset")
+X_MODELS = ("mlirt", "rtirt", "latentqr", "latent")         # the models whose sampler reads Data.X
+
+
+def extreme_models(kind):
+    """The models a kind applies to: rt_offset needs response times, x_offset covariates."""
+    if kind == "rt_offset":
+        return [m for m in MODELS if m != "mlirt"]
+    if kind == "x_offset":
+        return list(X_MODELS)
+    return list(MODELS)
+
+
+def _simulate_y(g, theta, a, b):
+    eta = a[None, :] * (theta[:, None] - b[None, :])
+    return (g.random(eta.shape) < 0.5 * (1.0 + np.tanh(0.5 * eta))).astype(np.uint8)
+
+
+def make_extreme_problem(kind, model, N, J, F=3, seed=11):
+    """make_problem's data set and initial state, pushed into one edge region of the kernels.  Returns (Y, logT, X, init, truth) like
+    make_problem; `init` always holds theta, a and b, so the first sweep's Polya-Gamma arguments z = |a_j (theta_i - b_j)| / 2 are fixed
+    by the generator (pg_cell_coverage).
+      separated   a log-uniform on [2, 8], theta with sd 3 and four subjects at +-10, Y simulated from them; init near the truth
+      saturated   separated, then an injected state: items with a = 100 and 50, subjects at theta = +-20 (|eta| up to ~2 000)
+      degenerate  all-1 and all-0 items, all-1 and all-0 subjects, one item with a single correct response
+      rt_offset   logT in raw log-milliseconds (lambda ~ 8), one item with sigma2_t ~ 1e-4, one constant logT column, zeta offset by +3
+      x_offset    X = [uniform on [20, 70], 0/1 dummy with 5 % ones, N(0, 1)]"""
+    if kind not in EXTREME_KINDS:
+        raise ValueError(kind)
+    if model not in extreme_models(kind):
+        raise ValueError(f"{kind} does not apply to {model}")
+    Y, logT, X, init, tp = make_problem(model, N, J, F, seed=seed)
+    g = np.random.default_rng(seed + 1000 * (EXTREME_KINDS.index(kind) + 1))
+    init = dict(init)
+    init.setdefault("a", np.ones(J))
+    init.setdefault("b", np.zeros(J))
+    Y = np.asfortranarray(Y.copy())
+    if kind in ("separated", "saturated"):
+        a = np.exp(g.uniform(np.log(2.0), np.log(8.0), J))
+        b = g.normal(0.0, 0.5, J)
+        theta = g.normal(0.0, 3.0, N)
+        theta[:4] = (10.0, -10.0, 10.0, -10.0)
+        Y = np.asfortranarray(_simulate_y(g, theta, a, b))
+        tp.a, tp.b, tp.theta = a, b, theta
+        init["theta"] = theta + 0.05 * g.standard_normal(N)
+        init["a"] = a * np.exp(0.02 * g.standard_normal(J))
+        init["b"] = b + 0.02 * g.standard_normal(J)
+        if kind == "saturated":
+            init["a"][:2] = (100.0, 50.0)
+            init["theta"][:4] = (20.0, -20.0, 20.0, -20.0)
+    elif kind == "degenerate":
+        Y[0:3, :] = 1                      # all-correct subjects
+        Y[3:6, :] = 0                      # all-wrong subjects (apart from the all-1 items below: the items are exact)
+        Y[:, 0:2] = 1                      # items every subject answers correctly
+        Y[:, 2:4] = 0                      # items every subject answers wrongly
+        Y[:, 4] = 0
+        Y[N // 2, 4] = 1                   # an item answered correctly by exactly one subject
+    elif kind == "rt_offset":
+        # raw log-milliseconds: every logT shifted to lambda ~ 8; the initial state is the truth with zeta offset by +3 and lambda by the
+        # same +3 (the chain starts consistent with the data, so item 0 keeps its tiny residual variance instead of drifting towards it)
+        lam = np.asarray(tp.lam, dtype=np.float64)
+        shift = 8.0 - lam.mean()
+        logT = np.asfortranarray(logT + shift)
+        theta, zeta = np.asarray(tp.theta, dtype=np.float64), np.asarray(tp.zeta, dtype=np.float64)
+        mu = lam[0] + shift - zeta               # (Cross family: rho_0 = 0, so item 0's residual does not move with each sweep's theta)
+        logT[:, 0] = mu + 1e-2 * g.standard_normal(N)       # within-item residual variance ~1e-4
+        logT[:, 1] = 8.0                                    # a constant column
+        init["theta"] = theta + 1e-3 * g.standard_normal(N)
+        init["zeta"] = zeta + 3.0 + 1e-3 * g.standard_normal(N)
+        init["lam"] = lam + shift + 3.0
+        sig2t = np.array(getattr(tp, "sig2t", None) if np.size(getattr(tp, "sig2t", None)) == J else np.ones(J), dtype=np.float64)
+        sig2t[0] = 1e-4
+        init["sig2t"] = sig2t
+        if model in ("crossqr", "cross"):
+            init["rho"] = np.array(tp.rho, dtype=np.float64)
+            init["rho"][0] = 0.0
+    elif kind == "x_offset":
+        X = np.asfortranarray(np.column_stack([g.uniform(20.0, 70.0, N), (g.random(N) < 0.05).astype(np.float64), g.standard_normal(N)]))
+        if X.shape[1] != F:
+            X = np.asfortranarray(X[:, :F]) if F < 3 else np.asfortranarray(np.column_stack([X, g.standard_normal((N, F - 3))]))
+    return Y, logT, X, init, tp
+
+
+PG_BIN_WIDTH = 1.0 / 16.0       # the proposal table's z-bins (erm_rng.hpp pg_bin: bin k covers [k/16, (k+1)/16), 128 bins below z = 8)
+
+
+def pg_cell_coverage(theta, a, b):
+    """Where a state puts the cells' Polya-Gamma arguments z = |a_j (theta_i - b_j)| / 2: the histogram over the 128 proposal bins (z < 8),
+    the fraction of cells with z >= 8 (the reference form), the counts with z >= 48 (p underflows in the mixture weight) and z > 745 (so
+    does 2 e^{-z}), and the largest z."""
+    theta, a, b = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (theta, a, b))
+    z = 0.5 * np.abs(a[None, :] * (theta[:, None] - b[None, :]))
+    lo = z[z < 8.0]
+    hist = np.bincount(np.minimum((lo / PG_BIN_WIDTH).astype(np.int64), 127), minlength=128)
+    return dict(hist=hist, bins_hit=int(np.count_nonzero(hist)), frac_ge8=float(np.mean(z >= 8.0)), n_ge48=int(np.sum(z >= 48.0)),
+                n_gt745=int(np.sum(z > 745.0)), zmax=float(z.max()), eta_max=float(2.0 * z.max()))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+_TF_NAMES = dict(theta="theta", a="a", b="b", zeta="zeta", lambda_="lambda_", sig2t="sig2t", beta="beta", sigp="Sigp", rho="rho", nu="nu")
+
+
+_MLIRT_UNUSED = ("zeta", "lambda_", "sig2t", "sigp", "rho")
+
+
+def _install_oracle_state(op, model, dev):
+    """The device's state (erm_get_state: everything the next sweep reads, nu included) as the oracle's state."""
+    for k, v in _TF_NAMES.items():
+        if dev.get(k) is None or (model == "mlirt" and k in _MLIRT_UNUSED) or (k == "nu" and model not in ("crossqr", "latentqr")):
+            continue
+        op.arr[v][:] = dev[k]
+
+
+def teacher_forced(model, Y, logT, X, init, T, precision, check, *, chunk=1, qRt=0.85, cov2one=None, seed=1234, **engine_opts):
+    """Teacher forcing: every sweep of the device is compared with ONE oracle sweep from the state that sweep started from, so each
+    conditional is checked on realistic chain states without error accumulation.  T sweeps in blocks of `chunk`; each block starts
+    from the oracle's state (erm_set_state: the prologue's row pass draws omega), and its later sweeps are erm_runs that CONTINUE the chain
+    -- they consume the Polya-Gamma draws the sweep kernel itself made (persistent or per-sweep), not the prologue's -- and are compared with
+    an oracle sweep from the device's own state after the sweep before.  After
+    each run check(t, dev_state, oracle_arrays) is called with t the index of the run's first sweep.
+    Returns dict(engine, dev=(ra, rt, qr, ll) traces as rows x width, orc=the matching oracle rows)."""
+    L = ge.load_package()._lib
+    if cov2one is None:
+        cov2one = model not in ("latentqr", "latent")
+    op = OracleProblem(model, Y, logT, X, init, qRt=qRt, cov2one=cov2one, seed=seed)
+    eng = L.Engine(model=MODELS[model], n_item=Y.shape[1], n_subj=Y.shape[0], n_feat=0 if X is None else X.shape[1], n_iter=T, n_chain=1,
+                   n_burnin=0, cov2one=int(cov2one), q_rt=qRt, seed=seed, precision={"f32": 0, "f64": 1}[precision], trace_mode=1, **engine_opts)
+    eng.set_data(Y, logT, X)
+    orc = []
+    for t in range(0, T, chunk):
+        n = min(chunk, T - t)
+        st = {k: op.arr[v].copy() for k, v in _TF_NAMES.items()}
+        if model not in ("crossqr", "latentqr"):
+            st.pop("nu")
+        if model == "crossqr" and t == 0:
+            st.pop("nu")           # constructors leave nu unset; it is drawn first
+        eng.set_state(**st)
+        for s_ in range(n):
+            if s_ > 0:
+                _install_oracle_state(op, model, dev)      # the run continues: the oracle takes the device's state after its previous sweep
+            eng.run(1)                                      # (a continuing erm_run skips the prologue: its omega is the sweep kernel's own draw)
+            orc.append(op.run(1, with_nu=model in ("crossqr", "latentqr")))
+            dev = eng.get_state()
+        check(t, {k: (None if dev[k] is None or (model == "mlirt" and k in _MLIRT_UNUSED) else dev[k]) for k in _TF_NAMES},
+              {k: op.arr[v] for k, v in _TF_NAMES.items()})
+    out = dict(engine=eng, orc={k: np.concatenate([o[k] for o in orc]) for k in ("ra", "rt", "qr", "ll")})
+    out["dev"] = dict(ra=eng.trace(L.TRACE_RA)[:, :, 0], ll=eng.trace(L.TRACE_LOGLIKE)[:, 0, 0], qr=eng.trace(L.TRACE_QR)[:, :, 0])
+    if model != "mlirt":
+        out["dev"]["rt"] = eng.trace(L.TRACE_RT)[:, :, 0]
+    return out

@@ -113,36 +113,20 @@ def test_teacher_forced(model, precision, tol):
     within 5e-4 (floor 1e-2 absolute)."""
     T, N, J = 8, 600, 11
     Y, logT, X, init, _ = pu.make_problem(model, N, J)
-    L = pu.ge.load_package()._lib
-    cov2one = model not in ("latentqr", "latent")
-    op = pu.OracleProblem(model, Y, logT, X, init, qRt=0.85, cov2one=cov2one)
-    eng = L.Engine(model=pu.MODELS[model], n_item=J, n_subj=N, n_feat=0 if X is None else X.shape[1], n_iter=T, n_chain=1,
-                   n_burnin=0, cov2one=int(cov2one), q_rt=0.85, seed=1234, precision={"f32": 0, "f64": 1}[precision], trace_mode=1)
-    eng.set_data(Y, logT, X)
-    names = dict(theta="theta", a="a", b="b", zeta="zeta", lambda_="lambda_", sig2t="sig2t", beta="beta", sigp="Sigp", rho="rho", nu="nu")
     floor = 1e-6 if precision == "f64" else 1e-2
-    for t in range(T):
-        st = {k: op.arr[v].copy() for k, v in names.items()}
-        if model not in ("crossqr", "latentqr"):
-            st.pop("nu")
-        if model == "crossqr" and t == 0:
-            st.pop("nu")           # constructors leave nu unset; it is drawn first
-        if model == "rtirt":
-            st["beta"] = st["beta"]
-        eng.set_state(**st)
-        eng.run(1)
-        op.run(1)
-        dev = eng.get_state()
-        for k, v in names.items():
-            if dev[k] is None or (model == "mlirt" and k in ("zeta", "lambda_", "sig2t", "sigp", "rho")):
+
+    def check(t, dev, orc):
+        for k in dev:
+            if dev[k] is None:
                 continue
             if k == "nu":
                 continue           # device nu is already next sweep's draw (fused schedule); it is checked through the next sweep
-            e = pu.rel_err(dev[k], op.arr[v], floor)
+            e = pu.rel_err(dev[k], orc[k], floor)
             if k in ("theta", "zeta") and precision == "f32":
                 assert np.mean(e > tol) < 2e-3, (model, t, k, e.max())
             else:
                 assert e.max() < tol, (model, t, k, e.max())
+    pu.teacher_forced(model, Y, logT, X, init, T, precision, check)
 
 
 @pytest.mark.parametrize("model", ["mlirt", "rtirt", "latentqr", "null", "cross", "latent"])

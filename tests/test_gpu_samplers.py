@@ -172,3 +172,55 @@ def test_gig_matches_oracle(p, a, b):
     lib.orc_sample_gig(1234, 15, 1, n, p, a, b, want.ctypes.data)
     got = pu.ge.load_package()._lib.sample_gig(p, a, b, n, seed=1234, site=15, sweep=1)
     assert np.max(np.abs(got - want) / np.abs(want)) < 1e-9
+
+
+def test_pg1_f64_decisions_in_every_bin_and_at_every_edge():
+    """The fast form's fp32 decisions (debug sampler 3) against the reference form (10) across the whole proposal table: z uniform in every
+    bin [k/16, (k+1)/16) with 2^16 draws each, and z at every bin edge k/16 and one ulp either side -- including 8 - ulp (bin 127, the
+    thinnest guard bands: p ~ 1e-11), 8 and 8 + ulp (the reference form).  Same bound as the filtered-decisions test; against the oracle too."""
+    per = 1 << 16
+    g = np.random.default_rng(21)
+    k = np.repeat(np.arange(128), per)
+    z = (k + g.uniform(0.0, 1.0, k.size)) / 16.0
+    fast, ref = _dev(3, z.size, 2.0 * z, sweep=31), _dev(10, z.size, 2.0 * z, sweep=31)
+    assert np.all(np.isfinite(fast)) and np.all(fast > 0)
+    rel = np.abs(fast - ref) / ref
+    assert rel.max() < 1e-13, (z[np.argmax(rel)], rel.max())
+    zs = np.repeat(np.arange(128), 1 << 11)
+    zs = (zs + g.uniform(0.0, 1.0, zs.size)) / 16.0          # against the (single-threaded) oracle: 2^11 draws per bin, every one compared
+    d, o = _dev(3, zs.size, 2.0 * zs, sweep=33), pu.orc_sample(3, zs.size, 2.0 * zs, sweep=33)
+    assert np.max(np.abs(d - o) / o) < 1e-10
+    edges = np.arange(129) / 16.0
+    e = np.concatenate([edges, np.nextafter(edges, np.inf), np.nextafter(edges[1:], 0.0)])
+    e = np.repeat(e, 2048)                     # 2 048 streams per edge value
+    fast, ref = _dev(3, e.size, 2.0 * e, sweep=32), _dev(10, e.size, 2.0 * e, sweep=32)
+    rel = np.abs(fast - ref) / ref
+    assert rel.max() < 1e-13, (e[np.argmax(rel)], rel.max())
+    o = pu.orc_sample(3, e.size, 2.0 * e, sweep=32)
+    assert np.max(np.abs(fast - o) / o) < 1e-10
+
+
+def _pg1_moments(c):
+    """Mean tanh(c/2) / (2c) and variance (sinh c - c) / (4 c^3 cosh^2(c/2)) = (2 tanh(c/2) - c sech^2(c/2)) / (4 c^3) of PG(1, c), in a
+    form that neither overflows nor cancels for large c (sech^2(c/2) = 4 e^{-c} / (1 + e^{-c})^2)."""
+    em = np.exp(-c)
+    sech2 = 4.0 * em / (1.0 + em) ** 2
+    th = np.tanh(0.5 * c)
+    return th / (2.0 * c), (2.0 * th - c * sech2) / (4.0 * c ** 3)
+
+
+@pytest.mark.parametrize("c", [32.0, 96.0, 100.0, 1490.0, 1500.0, 2e4])
+def test_pg1_large_c(c):
+    """z = c/2 >= 16: the reference form's mixture weight p / (p + 2 e^{-z}) with p underflowing (z >= ~48), with 2 e^{-z} underflowing too
+    (z > 745: 0 / 0, the IG proposal is taken) -- draws finite, positive, the oracle's (fp64 to 1e-10; fp32 is the same fp64 draw rounded),
+    and of the right law: mean and variance at 10^6 draws."""
+    n = 1_000_000
+    cc = np.full(n, c)
+    o = pu.orc_sample(3, n, cc, sweep=41)
+    m, v = _pg1_moments(c)
+    for prec, tol in ((1, 1e-10), (0, 1e-6)):
+        d = _dev(3, n, cc, precision=prec, sweep=41)
+        assert np.all(np.isfinite(d)) and np.all(d > 0), prec
+        assert np.max(np.abs(d - o) / o) < tol, prec
+        assert abs(d.mean() - m) < 5.0 * np.sqrt(v / n), (prec, d.mean(), m)
+        assert abs(d.var() / v - 1.0) < 0.02, (prec, d.var(), v)
