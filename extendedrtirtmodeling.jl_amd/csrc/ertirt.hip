@@ -19,6 +19,7 @@
 #include "ertirt.h"
 #include "erm_kernels.hpp"
 #include "erm_geometry.hpp"
+#include "erm_schedule.hpp"
 
 using namespace erm;
 
@@ -464,13 +465,22 @@ template <typename real> struct Engine : EngineBase {
     int64_t n_pass_timed = 0;                        // sweep-kernel launches inside event brackets in the current run
     int64_t n_brackets = 0;                          // event pairs used
     std::vector<int> bracket_launches;               // launches inside each bracket
+    bool bracket_open = false;
+    // The event pair around timed launches: bracket(false) opens one (profile mode, while pairs beyond the calibration's are left), bracket(true, n) closes
+    // the open one, which held n launches of the sweep kernel (n sweeps of a graph or a persistent launch).
+    int bracket(bool close, int64_t launches = 0) {
+        if (close ? !bracket_open : (bracket_open || !cfg.profile || (size_t)(2 * n_brackets + 1) + 64 >= pass_ev.size())) return 0;
+        HIPCHK(hipEventRecord(pass_ev[2 * n_brackets + (close ? 1 : 0)], stream));
+        bracket_open = !close;
+        if (close) { ++n_brackets; n_pass_timed += launches; bracket_launches.push_back((int)launches); }
+        return 0;
+    }
     template <int MODEL, int PHASE> int launch_pass(int mode, bool timed) {
         PassArgs<real> a = pass_args(PHASE, mode);
         TinyArgs t{};
-        const bool ev = timed && cfg.profile && (size_t)(2 * n_brackets + 1) + 64 < pass_ev.size();
-        if (ev) HIPCHK(hipEventRecord(pass_ev[2 * n_brackets], stream));
+        if (timed) { if (int rc = bracket(false)) return rc; }
         hipLaunchKernelGGL((pass_kernel<MODEL, real, PHASE, false>), dim3(grid_blocks), dim3(block_threads), lds_pass[PHASE], stream, a, t);
-        if (ev) { HIPCHK(hipEventRecord(pass_ev[2 * n_brackets + 1], stream)); ++n_brackets; ++n_pass_timed; bracket_launches.push_back(1); }
+        if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(PHASE, a.gslab);
         return 0;
     }
@@ -524,27 +534,22 @@ template <typename real> struct Engine : EngineBase {
     template <int MODEL> int launch_fused(bool timed) {
         PassArgs<real> a = pass_args(0, 1, true);
         TinyArgs t = tiny_args(0, true);
-        const bool ev = timed && cfg.profile && (size_t)(2 * n_brackets + 1) + 64 < pass_ev.size();
-        if (ev) HIPCHK(hipEventRecord(pass_ev[2 * n_brackets], stream));
+        if (timed) { if (int rc = bracket(false)) return rc; }
         hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true>), dim3(grid_blocks), dim3(block_threads), fused_lds(), stream, a, t);
-        if (ev) { HIPCHK(hipEventRecord(pass_ev[2 * n_brackets + 1], stream)); ++n_brackets; ++n_pass_timed; bracket_launches.push_back(1); }
-        cur ^= 1;
+        if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(0, a.gslab);     // a.gslab: the group rows this launch wrote
         return 0;
     }
-    // nsweeps whole sweeps in ONE launch (small data sets): reads buffers [cur] first, alternates inside the launch, leaves cur where nsweeps single launches would
-    template <int MODEL> int launch_persist(int64_t nsweeps) {
+    // nsweeps whole sweeps in ONE launch (small data sets): reads buffers [cur] first, alternates inside the launch
+    template <int MODEL> int launch_persist(int64_t nsweeps, bool timed) {
         PassArgs<real> a = pass_args(0, 1, true);
         TinyArgs t = tiny_args(0, true);
         a.nsweeps = (uint32_t)nsweeps; a.cur0 = (uint32_t)cur;
         if (xtag > 0x7fffffffu - (uint32_t)nsweeps) { HIPCHK(hipMemsetAsync(dXbuf.p, 0, dXbuf.bytes, stream)); xtag = 0; }
         a.tag0 = xtag; xtag += (uint32_t)nsweeps;
-        const bool ev = cfg.profile && (size_t)(2 * n_brackets + 1) + 64 < pass_ev.size();
-        if (ev) HIPCHK(hipEventRecord(pass_ev[2 * n_brackets], stream));
+        if (timed) { if (int rc = bracket(false)) return rc; }
         hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true, true>), dim3(grid_blocks), dim3(block_threads), fused_lds(), stream, a, t);
-        if (ev) { HIPCHK(hipEventRecord(pass_ev[2 * n_brackets + 1], stream)); ++n_brackets; n_pass_timed += nsweeps; bracket_launches.push_back((int)nsweeps); }
-        cur = (int)((cur + nsweeps) & 1);
-        return 0;
+        return bracket(true, nsweeps);
     }
     template <int MODEL, int STEP> int launch_tiny(int mode) {
         TinyArgs t = tiny_args(mode);
@@ -553,24 +558,15 @@ template <typename real> struct Engine : EngineBase {
     }
 
     // One sweep = tiny step + row pass (CrossQr: two of each).  Kernel arguments never change between sweeps -- the sweep / trace-row counters and the
-    // "first sweep of this call" flag live in device memory (Ctl) -- so EVERY sweep of a run is the same launch sequence: blocks of 32 / 16 / 4 / 2
-    // sweeps are captured once into hipGraphs and replayed, at most one sweep per run is enqueued singly.  That removes the per-launch host overhead
-    // and the idle gaps between singly launched kernels (a 20-sweep erm_run: two graph launches instead of one sweep + four graphs + three sweeps).
+    // "first sweep of this call" flag live in device memory (Ctl) -- so EVERY sweep of a run is the same launch sequence and can be captured once into a
+    // hipGraph and replayed.  Which graphs, single sweeps and event brackets a call consists of is decided by plan_run (erm_schedule.hpp) and nowhere else.
 #ifndef ERM_GRAPH_SWEEPS
 #define ERM_GRAPH_SWEEPS 32
 #endif
     static constexpr int GRAPH_SWEEPS = ERM_GRAPH_SWEEPS;
-    static constexpr int PROFILE_STRIDE = 8;
-    static constexpr int NGRAPH = 4;
-    // (every count is even: a fused sweep flips the double buffers, and a graph must be replayed with the buffer parity it was captured with -- every
-    // run starts from buffer 0 and replays its graphs BEFORE its one single sweep)
-    const int graph_sweeps[NGRAPH] = {GRAPH_SWEEPS, 16, 4, 2};
-    hipGraphExec_t graphs[NGRAPH] = {nullptr, nullptr, nullptr, nullptr};
-    // A WHOLE call as graphs (single-pass and Cross samplers on the per-sweep schedule, statistics resident): calls of up to GRAPH_SWEEPS sweeps are ONE graph --
-    // run_begin_kernel, the sweeps, the closing tiny step and run_end_kernel (full[k]) --, longer ones end in tail[r] = r sweeps + tiny step + run_end_kernel behind
-    // their blocks of GRAPH_SWEEPS.  Between a graph and an ordinary launch
-    // the device idles 10-14 us (measured: tools/run_timeline.py), inside a graph 0: a 20-sweep call 1 435 -> 1 400 us of device time.  Built by the first call of each length.
-    hipGraphExec_t graphs_full[GRAPH_SWEEPS + 1] = {}, graphs_tail[GRAPH_SWEEPS + 1] = {};
+    // block[gi]: block_sweeps(gi) sweeps; full[k], tail[r]: see StepKind.  Each is built by the first call whose plan replays it.
+    hipGraphExec_t graphs[NBLOCK] = {}, graphs_full[GRAPH_SWEEPS + 1] = {}, graphs_tail[GRAPH_SWEEPS + 1] = {};
+    hipGraphExec_t* graph_of(const Step& s) { return s.kind == STEP_BLOCK ? &graphs[s.gi] : s.kind == STEP_FULL ? &graphs_full[s.n] : &graphs_tail[s.n]; }
     void drop_graphs() {
         for (auto& g : graphs) { if (g) (void)hipGraphExecDestroy(g); g = nullptr; }
         for (auto* arr : {graphs_full, graphs_tail}) for (int k = 0; k <= GRAPH_SWEEPS; ++k) { if (arr[k]) (void)hipGraphExecDestroy(arr[k]); arr[k] = nullptr; }
@@ -593,16 +589,44 @@ template <typename real> struct Engine : EngineBase {
         hipLaunchKernelGGL(run_end_kernel, dim3(1), dim3(64), 0, stream, dCtlB[0].template as<Ctl>(), dCtlB[1].template as<Ctl>(), dGcnt.as<unsigned int>() + 2 * n_groups,
                            host_ctl_dev + 1, reinterpret_cast<unsigned int*>(host_ctl_dev + 3));
     }
-    // nsw sweeps; `begin`: run_begin_kernel first; `end`: the closing tiny step and run_end_kernel last.
-    // The capture starts at buffer parity 0 (every call does) and -- a graph is only ever replayed at that parity -- restores it afterwards.
-    template <int MODEL> int build_graph(int nsw, hipGraphExec_t* out, bool begin = false, bool end = false) {
+    Plan plan;                                       // the call being enqueued
+    // run_steps' executor: one launch per step kind, the graphs, the event brackets, the buffer parity
+    template <int MODEL> struct Exec {
+        Engine& e;
+        bool built(const Step& s) const { return *e.graph_of(s) != nullptr; }
+        int build(const Step& s) { return e.template build_graph<MODEL>(s); }
+        int bracket(bool close, int64_t sweeps) { return e.bracket(close, sweeps); }
+        void flip(int64_t sweeps) { e.cur = (int)((e.cur + sweeps) & 1); }
+        int launch(const Step& s, bool timed) {
+            switch (s.kind) {
+            case STEP_RUN_BEGIN: e.launch_run_begin(); return 0;
+            case STEP_RUN_END: e.launch_run_end(); return 0;
+            case STEP_PROLOGUE:
+                if (int rc = e.template launch_pass<MODEL, 0>(0, false)) return rc;
+                if constexpr (fam_cq(MODEL)) return e.template launch_pass<MODEL, 1>(0, false);
+                return 0;
+            case STEP_PERSIST:
+                if constexpr (!fam_cq(MODEL)) return e.template launch_persist<MODEL>(s.n, timed);
+                return fail(ERM_ERR_STATE, "internal: a persistent step in a Cross-family plan");
+            case STEP_SINGLE: return e.template enqueue_sweep<MODEL>(timed);
+            case STEP_TINY_CLOSE: return e.template launch_tiny<MODEL, 0>(1);
+            default: HIPCHK(hipGraphLaunch(*e.graph_of(s), e.stream)); return 0;
+            }
+        }
+    };
+    int run_model(const Plan& P, int from, int to) {
+        return dispatch([&](auto m) -> int { Exec<decltype(m)::value> x{*this}; return run_steps(P, from, to, x); });
+    }
+    // Captures what graph step `s` stands for (graph_body).  The capture starts at buffer parity 0 -- a graph is only ever replayed there -- and leaves the
+    // parity alone, also when it fails: the replay moves it.
+    template <int MODEL> int build_graph(const Step& s) {
+        hipGraphExec_t* out = graph_of(s);
         hipGraph_t g = nullptr;
-        const int cur0 = cur;                        // a fused sweep flips the double buffers while it is being captured: a failed capture -- and a whole-call
-        HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));       // graph, whose sweeps the caller does not count -- must not leave the parity changed
-        int rc = 0;
-        if (begin) launch_run_begin();
-        for (int k = 0; k < nsw && !rc; ++k) rc = enqueue_sweep<MODEL>(false);
-        if (end && !rc) { rc = launch_tiny<MODEL, 0>(1); launch_run_end(); }
+        const int cur0 = cur;
+        const Plan body = graph_body(plan, s);
+        HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+        Exec<MODEL> x{*this};
+        int rc = run_steps(body, 0, body.n, x);
         const hipError_t e = hipStreamEndCapture(stream, &g);      // always ends the capture, also after a failed enqueue
         if (!rc && e != hipSuccess) rc = fail(ERM_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
         if (!rc) {
@@ -610,113 +634,8 @@ template <typename real> struct Engine : EngineBase {
             if (ei != hipSuccess) { *out = nullptr; rc = fail(ERM_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei)); }
         }
         if (g) (void)hipGraphDestroy(g);             // on every exit
-        if (rc || end) cur = cur0;                   // (a whole-call graph: run_model moves the parity when it replays it)
+        cur = cur0;
         return rc;
-    }
-    // whole: 0 = the caller launches run_begin_kernel / run_end_kernel around this; 1 = the call is ONE graph (built by the caller: graphs_full[_ev][nsweeps]);
-    // 2 = run_begin_kernel is enqueued, the call's last graph (graphs_tail) carries the closing tiny step and run_end_kernel
-    template <int MODEL> int run_model(int64_t nsweeps, int whole = 0) {
-        // prologue: omega_{t+1} (and nu_{t+1}) and the statistics of the current state.  A run that CONTINUES the previous one finds both
-        // in place -- the last pass drew omega_{t+1} from the same addressed streams and left the same statistics -- and skips it.
-        if (!stats_valid) {
-            if (int rc = launch_pass<MODEL, 0>(0, false)) return rc;
-            if constexpr (fam_cq(MODEL)) { if (int rc = launch_pass<MODEL, 1>(0, false)) return rc; }
-        }
-        int64_t k = 0;
-        if constexpr (!fam_cq(MODEL)) {
-            if (persist && !sharded() && nsweeps > 0) {
-                // blocks of 2^20 sweeps (packet tags are 32 bits and only grow)
-                for (int64_t done = 0; done < nsweeps; ) {
-                    const int64_t nb = std::min<int64_t>(nsweeps - done, 1 << 20);
-                    if (int rc = launch_persist<MODEL>(nb)) return rc;
-                    done += nb;
-                }
-                if (int rc = launch_tiny<MODEL, 0>(1)) return rc;
-                return 0;
-            }
-        }
-        // (a callback exchange synchronises with the host once per pass and cannot be captured; RCCL's all-gather is a stream operation)
-        const bool use_graph = exch == nullptr && (cfg.flags & ERM_FLAG_NO_GRAPH) == 0;
-        // profile mode (erm_get_timing: the live kernel time of bench.py's roofline).  Single-pass models: every replayed graph holds launches of the sweep
-        // kernel and nothing else, so the event pairs go around (up to four consecutive) graph launches and every sweep of the run is inside a bracket while
-        // the run still proceeds at graph-replay speed.  The Cross family's sweeps hold tiny kernels too, a sharded sweep its pack kernel and all-gather:
-        // those are bracketed launch by launch on singly enqueued sweeps -- all sweeps of a short run, two (the first one timed; two keep the buffer
-        // parity) before every replayed block of a long one.
-        const bool graph_timing = cfg.profile && !fam_cq(MODEL) && fused() && !sharded();
-        const bool single_timing = cfg.profile && !graph_timing;
-        const bool flips = !fam_cq(MODEL) && fused();      // a fused sweep flips the double buffers (launch_fused); the two-kernel schedules do not
-        if (whole == 1) {
-            // (profile mode: the bracket's events go around the graph on the stream -- event records captured INTO a graph do not time its kernels on this runtime:
-            // tried, 13.9 us per sweep -- so it also holds the three small kernels, ~12 us per call; as two launches, run_begin_kernel and a tail graph, it held the
-            // 10.7 us gap between them instead of the 3.5 us kernel)
-            const bool ev = graph_timing && (size_t)(2 * n_brackets + 1) + 64 < pass_ev.size();
-            if (ev) HIPCHK(hipEventRecord(pass_ev[2 * n_brackets], stream));
-            HIPCHK(hipGraphLaunch(graphs_full[nsweeps], stream));
-            if (ev) { HIPCHK(hipEventRecord(pass_ev[2 * n_brackets + 1], stream)); ++n_brackets; n_pass_timed += nsweeps; bracket_launches.push_back((int)nsweeps); }
-            if (flips) cur = (int)((cur + nsweeps) & 1);
-            return 0;
-        }
-        if (whole == 2) {
-            const int r = (nsweeps % GRAPH_SWEEPS) == 0 ? GRAPH_SWEEPS : (int)(nsweeps % GRAPH_SWEEPS);
-            if (nsweeps > r && !graphs[0]) { if (int rc = build_graph<MODEL>(GRAPH_SWEEPS, &graphs[0])) return rc; }
-            if (!graphs_tail[r]) { if (int rc = build_graph<MODEL>(r, &graphs_tail[r], false, true)) return rc; }
-            int in_bracket = 0, launches = 0;
-            bool open = false;
-            auto close = [&]() -> int {
-                if (!open) return 0;
-                HIPCHK(hipEventRecord(pass_ev[2 * n_brackets + 1], stream));
-                ++n_brackets; n_pass_timed += launches; bracket_launches.push_back(launches);
-                open = false; in_bracket = 0; launches = 0;
-                return 0;
-            };
-            auto replay = [&](hipGraphExec_t g, int nsw) -> int {
-                if (graph_timing && !open && (size_t)(2 * n_brackets + 1) + 64 < pass_ev.size()) { HIPCHK(hipEventRecord(pass_ev[2 * n_brackets], stream)); open = true; }
-                HIPCHK(hipGraphLaunch(g, stream));
-                k += nsw; launches += nsw; ++in_bracket;
-                if (in_bracket >= 4) return close();
-                return 0;
-            };
-            while (nsweeps - k > r) { if (int rc = replay(graphs[0], GRAPH_SWEEPS)) return rc; }
-            if (int rc = replay(graphs_tail[r], r)) return rc;      // (its bracket also holds the closing tiny step and run_end_kernel: ~8 us once per call)
-            if (flips) cur = (int)((cur + r) & 1);
-            return close();
-        }
-        if (use_graph && !single_timing) {
-            bool open = false;
-            int in_bracket = 0, launches = 0;
-            auto close = [&]() -> int {
-                if (!open) return 0;
-                HIPCHK(hipEventRecord(pass_ev[2 * n_brackets + 1], stream));
-                ++n_brackets; n_pass_timed += launches; bracket_launches.push_back(launches);
-                open = false; in_bracket = 0; launches = 0;
-                return 0;
-            };
-            for (int gi = 0; gi < NGRAPH; ++gi) {
-                const int nsw = graph_sweeps[gi];
-                while (nsweeps - k >= nsw) {
-                    if (!graphs[gi]) {       // built by the first run that needs it (a benchmark's warm-up), never inside an event bracket
-                        if (int rc = close()) return rc;
-                        if (int rc = build_graph<MODEL>(nsw, &graphs[gi])) return rc;
-                    }
-                    if (graph_timing && !open && (size_t)(2 * n_brackets + 1) + 64 < pass_ev.size()) { HIPCHK(hipEventRecord(pass_ev[2 * n_brackets], stream)); open = true; }
-                    HIPCHK(hipGraphLaunch(graphs[gi], stream));
-                    k += nsw; launches += nsw; ++in_bracket;
-                    if (in_bracket >= 4) { if (int rc = close()) return rc; }
-                }
-            }
-            if (int rc = close()) return rc;
-        } else if (use_graph && nsweeps >= 2 * (GRAPH_SWEEPS + 2)) {
-            for (; nsweeps - k >= GRAPH_SWEEPS + 2; k += GRAPH_SWEEPS + 2) {
-                if (int rc = enqueue_sweep<MODEL>(true)) return rc;
-                if (int rc = enqueue_sweep<MODEL>(false)) return rc;
-                if (!graphs[0]) { if (int rc = build_graph<MODEL>(GRAPH_SWEEPS, &graphs[0])) return rc; }
-                HIPCHK(hipGraphLaunch(graphs[0], stream));
-            }
-        }
-        const bool short_run = nsweeps < 2 * (GRAPH_SWEEPS + 2);
-        for (int64_t r = 0; k < nsweeps; ++k, ++r) { if (int rc = enqueue_sweep<MODEL>(graph_timing || (single_timing && (short_run || (r % PROFILE_STRIDE) == 0)))) return rc; }
-        if (int rc = launch_tiny<MODEL, 0>(1)) return rc;      // the log-likelihood of the last sweep (a call without sweeps: nothing to reduce, the step returns at once)
-        return 0;
     }
 
     // ---- the state an erm_run changes in place (persistent launches save it first: a launch that times out is replayed per sweep from the copy).
@@ -800,23 +719,30 @@ template <typename real> struct Engine : EngineBase {
             if (stats_valid) HIPCHK(hipMemcpyAsync(dGslab0B[0].p, dGslab0B[1].p, dGslab0B[0].bytes, hipMemcpyDeviceToDevice, stream));
             cur = 0;
         }
-        const bool persistent_run = persist && !sharded() && nsweeps > 0 && !m_cq();
+        const bool calibrate = cfg.profile && pass_ev.size() >= 64 && !ev_calibrated;
+        {
+            RunIn in;
+            in.nsweeps = nsweeps; in.cq = m_cq(); in.fused = fused(); in.persist = persist; in.shard = exch ? SHARD_CALLBACK : comm ? SHARD_RCCL : SHARD_NONE;
+            in.no_graph = (cfg.flags & ERM_FLAG_NO_GRAPH) != 0; in.profile = cfg.profile != 0; in.stats_valid = stats_valid; in.calibrate = calibrate; in.graph_sweeps = GRAPH_SWEEPS;
+            plan = plan_run(in);
+        }
+        const Plan& P = plan;
+        const bool persistent_run = P.persistent;
         // counters, tickets, the persistent launch's wait bound (1 s of the 100 MHz wall clock; 2 ms under the test hook) in ONE small launch, its parameters in pinned memory
         const bool fault = persistent_run && persist_fault_countdown > 0 && --persist_fault_countdown == 0;
         host_run->v = c; host_run->tmo_ticks = fault ? 200000u : 100000000u; host_run->tmo_fault = fault ? 1u : 0u;
         volatile unsigned int* h_tmo = reinterpret_cast<volatile unsigned int*>(&host_ctl[3]);
         *h_tmo = 0u;
-        n_pass_timed = 0; n_brackets = 0; bracket_launches.clear();
-        const bool calibrate = cfg.profile && pass_ev.size() >= 64 && !ev_calibrated;
-        // the whole call as graphs (see graphs_full): per-sweep schedule, statistics resident, nothing that has to be bracketed launch by launch
-        const bool graph_timing = cfg.profile && !m_cq() && fused() && !sharded();
-        int whole = 0;
-        if (exch == nullptr && (cfg.flags & ERM_FLAG_NO_GRAPH) == 0 && !sharded() && !persistent_run && stats_valid && !calibrate && nsweeps >= 1 && !(cfg.profile && !graph_timing))
-            whole = nsweeps <= GRAPH_SWEEPS ? 1 : 2;
-        if (whole == 1 && !graphs_full[nsweeps]) {
-            if (int rcb = dispatch([&](auto m) -> int { return build_graph<decltype(m)::value>((int)nsweeps, &graphs_full[nsweeps], true, true); })) return rcb;
-        }
-        if (whole != 1) { launch_run_begin(); HIPCHK(hipGetLastError()); }
+        n_pass_timed = 0; n_brackets = 0; bracket_launches.clear(); bracket_open = false;
+        // run-begin and run-end stand outside the call's own event pair when they are launches of their own (inside it when the call's graphs hold them)
+        const int first = P.step[0].kind == STEP_RUN_BEGIN ? 1 : 0, last = P.step[P.n - 1].kind == STEP_RUN_END ? P.n - 1 : P.n;
+        auto enqueue = [&](int from, int to) -> int {
+            if (from == to) return 0;
+            if (int rc = run_model(P, from, to)) return rc;
+            HIPCHK(hipGetLastError());
+            return 0;
+        };
+        if (int rc = enqueue(0, first)) return rc;
         if (persistent_run) { snap_stats_valid = stats_valid; if (int rc = snap_copy(false)) return rc; }
         if (calibrate) {   // empty event pairs, once per engine: the bracketing overhead that is subtracted from every timed launch
             for (int k = 0; k < 16; ++k) { HIPCHK(hipEventRecord(pass_ev[pass_ev.size() - 2 - 2 * k], stream)); HIPCHK(hipEventRecord(pass_ev[pass_ev.size() - 1 - 2 * k], stream)); }
@@ -825,13 +751,12 @@ template <typename real> struct Engine : EngineBase {
         std::unique_lock<std::mutex> turn;
         if (persistent_run) turn = std::unique_lock<std::mutex>(g_persist_mu[(unsigned)cfg.device % 64u]);
         // (a one-graph call in profile mode: its bracket IS the call -- two event records ahead of the graph's launch instead of one keep the device idle 4 us longer)
-        const bool own_events = !(whole == 1 && graph_timing && pass_ev.size() >= 66);
+        const bool own_events = !(P.step[0].kind == STEP_FULL && P.step[0].stride > 0 && pass_ev.size() >= 66);
         if (own_events) HIPCHK(hipEventRecord(ev0, stream));
-        if (int rc = dispatch([&](auto m) -> int { return run_model<decltype(m)::value>(nsweeps, whole); })) return rc;
+        if (int rc = enqueue(first, last)) return rc;
         if (own_events) HIPCHK(hipEventRecord(ev1, stream));
-        HIPCHK(hipGetLastError());
-        // the counters of both buffers and the time-out word, stored into pinned host memory by one small launch (no copy operations; inside the call's last graph when it has one)
-        if (!whole) { launch_run_end(); HIPCHK(hipGetLastError()); }
+        // the counters of both buffers and the time-out word, stored into pinned host memory by one small launch (no copy operations)
+        if (int rc = enqueue(last, P.n)) return rc;
         HIPCHK(hipStreamSynchronize(stream));
         if (turn.owns_lock()) turn.unlock();
         if (*h_tmo != 0u) {
@@ -848,7 +773,7 @@ template <typename real> struct Engine : EngineBase {
         }
         const double null_ms = ev_null_ms;
         timing.event_overhead_ms = null_ms;
-        for (int64_t k = 0; k < n_brackets; ++k) {   // a bracket holds 1 launch, or the TAIL_SWEEPS launches of one replayed graph
+        for (int64_t k = 0; k < n_brackets; ++k) {   // a bracket holds 1 kernel, one persistent launch, or up to BRACKET_REPLAYS replayed graphs
             float t = 0.f;
             HIPCHK(hipEventElapsedTime(&t, pass_ev[2 * k], pass_ev[2 * k + 1]));
             timing.pass_ms_total += std::max(0.0, (double)t - null_ms);

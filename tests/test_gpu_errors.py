@@ -126,6 +126,13 @@ def test_schedule_flags_change_the_schedule_not_the_chain(model):
     for flags in (L.FLAG_NO_GRAPH, L.FLAG_NO_PERSIST, L.FLAG_NO_PERSIST | L.FLAG_NO_GRAPH, L.FLAG_NO_FUSE, L.FLAG_NO_FUSE | L.FLAG_NO_GRAPH):
         got = pu.run_device(model, Y, logT, X, init, T, precision="f64", flags=flags, **geom)
         assert np.array_equal(got["ra"], ref["ra"]) and np.array_equal(got["item"], ref["item"]) and np.array_equal(got["ll"], ref["ll"]), flags
+        tm = got["engine"].timing()
+        assert (tm["pass_launches"], tm["sweeps"]) == (0, T), (flags, tm)      # no profile mode: nothing is timed
+        # profile mode: every schedule of a single-pass sampler has each sweep of a call this short inside a bracket, one sweep kernel per sweep
+        got = pu.run_device(model, Y, logT, X, init, T, precision="f64", flags=flags, profile=1, **geom)
+        assert np.array_equal(got["ra"], ref["ra"]) and np.array_equal(got["item"], ref["item"]) and np.array_equal(got["ll"], ref["ll"]), flags
+        tm = got["engine"].timing()
+        assert (tm["pass_launches"], tm["sweeps"]) == (T, T), (flags, tm)
 
 
 def test_nu_trace_budget_is_a_config_field():

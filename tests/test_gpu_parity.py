@@ -240,4 +240,18 @@ def test_graph_replay_and_continuation(model):
     # profile mode (bench.py) interleaves event-bracketed single sweeps with the replayed blocks: same chain, and launches were timed
     b = pu.run_device(model, Y, logT, X, init, 88, precision="f32", profile=1)
     assert np.array_equal(b["ra"], a["ra"]) and np.array_equal(b["ll"], a["ll"]) and np.array_equal(b["item"], a["item"])
-    assert b["engine"].timing()["pass_launches"] >= 2
+    # (a calibrating first call: the single-pass sampler's 88 sweeps are all inside brackets -- one persistent launch at this size --; CrossQr times the first of
+    # the two sweeps ahead of each of its two 32-sweep graphs and sweeps 0, 8, 16 of the last 20, two row-pass kernels each)
+    tm = b["engine"].timing()
+    assert (tm["pass_launches"], tm["sweeps"]) == ({"rtirt": 88, "crossqr": 10}[model], 88)
+    # calls that continue a profiled engine (statistics resident): 20 and 33 sweeps of CrossQr are timed kernel by kernel, its 88 as above
+    eng = L.Engine(model=pu.MODELS[model], n_item=9, n_subj=500, n_feat=0 if X is None else 3, n_iter=161, n_chain=1, n_burnin=44, cov2one=1, q_rt=0.85,
+                   seed=1234, precision=0, trace_mode=1, profile=1)
+    eng.set_data(Y, logT, X)
+    eng.set_state(**{("lambda_" if k == "lam" else k): v for k, v in init.items()})
+    eng.run(20)
+    for n, timed in ((20, {"rtirt": 20, "crossqr": 40}), (33, {"rtirt": 33, "crossqr": 66}), (88, {"rtirt": 88, "crossqr": 10})):
+        eng.run(n)
+        tm = eng.timing()
+        assert (tm["pass_launches"], tm["sweeps"]) == (timed[model], n), (n, tm)
+    assert np.array_equal(eng.trace(L.TRACE_RA)[:88], a["ra"]) and np.array_equal(eng.item_trace()[:88], a["item"])
