@@ -115,7 +115,10 @@ int erm_simulate_data(erm_handle h, const erm_state* truth, uint64_t seed, int n
 int erm_get_truth(erm_handle h, double* theta, double* zeta);
 int erm_get_data(erm_handle h, uint8_t* Y, double* logT, double* X);
 
-/* Para in / out (setInitialValues: src/GibbsRtIrt.pl.jl:84-93,122-133; Cross :123-134; Latent :113-124). */
+/* Para in / out (setInitialValues: src/GibbsRtIrt.pl.jl:84-93,122-133; Cross :123-134; Latent :113-124).
+ * After erm_run, erm_get_state returns the last recorded trace row bit for bit -- except nu (the quantile models): every schedule draws
+ * nu_{t+1} at the end of sweep t (it depends on sweep t's draws only), so the state holds the nu that the NEXT sweep reads and records,
+ * not the nu of the last trace row.  Post.mean and the traces hold nu_t; the next erm_run of the engine records state-nu as its first nu row. */
 int erm_set_state(erm_handle h, const erm_state* st);
 int erm_get_state(erm_handle h, erm_state* st);
 

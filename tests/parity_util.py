@@ -382,3 +382,88 @@ def teacher_forced(model, Y, logT, X, init, T, precision, check, *, chunk=1, qRt
     if model != "mlirt":
         out["dev"]["rt"] = eng.trace(L.TRACE_RT)[:, :, 0]
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Post.mean from the traces.  The column layouts are restated here from the interface (include/ertirt.h: erm_state, erm_get_trace) and the
+# reference's Post.ra / rt / qr rows; nothing is imported from the code under test.
+NU_MODELS = ("crossqr", "latentqr")
+U53 = 2.0 ** -53                 # unit round-off of fp64
+
+
+def trace_rows(tr):
+    """A trace in Julia layout (nIter, width, nChain) as rows x width in the order the sweeps ran: sweep (m, l) is row m * nChain + l."""
+    tr = np.asarray(tr)
+    if tr.ndim == 2:
+        return tr
+    return np.ascontiguousarray(tr.transpose(0, 2, 1).reshape(tr.shape[0] * tr.shape[2], tr.shape[1]))
+
+
+def decode_rows(model, N, J, F, ra, rt, qr):
+    """Trace rows (rows x width) -> the fields of erm_state, each rows x size:
+      ra = [theta (N); a (J); b (J)], rt = [zeta (N); lambda (J); sig2t (J)] (MlIrt has no rt: pass None),
+      qr: MlIrt beta (F+1); RtIrt vec(beta) (2(F+1)), vec(Sigp) (4); Null the same with beta = 0; Cross rho (J), vec(Sigp);
+          CrossQr rho, vec(Sigp), vec(nu) (N*J, column-major); Latent beta (F+2), vec(Sigp); LatentQr beta (F+2), vec(Sigp), nu (N).
+    A quantile model's qr without its nu block (width J+4 / F+6) decodes without `nu`."""
+    ra, qr = np.atleast_2d(np.asarray(ra, dtype=np.float64)), np.atleast_2d(np.asarray(qr, dtype=np.float64))
+    if ra.shape[1] != N + 2 * J:
+        raise ValueError(f"ra has {ra.shape[1]} columns, expected {N + 2 * J}")
+    f = dict(theta=ra[:, :N], a=ra[:, N:N + J], b=ra[:, N + J:])
+    if model != "mlirt":
+        rt = np.atleast_2d(np.asarray(rt, dtype=np.float64))
+        if rt.shape != ra.shape:
+            raise ValueError(f"rt is {rt.shape}, expected {ra.shape}")
+        f.update(zeta=rt[:, :N], lambda_=rt[:, N:N + J], sig2t=rt[:, N + J:])
+    nb = {"mlirt": F + 1, "rtirt": 2 * (F + 1), "null": 2 * (F + 1), "cross": 0, "crossqr": 0, "latent": F + 2, "latentqr": F + 2}[model]
+    nnu = {"crossqr": N * J, "latentqr": N}.get(model, 0)
+    base = nb + (J if model in ("cross", "crossqr") else 0) + (0 if model == "mlirt" else 4)
+    if qr.shape[0] != ra.shape[0] or qr.shape[1] not in (base, base + nnu):
+        raise ValueError(f"qr is {qr.shape}, expected {ra.shape[0]} x {base}" + (f" or {base + nnu}" if nnu else ""))
+    o = 0
+    if model in ("cross", "crossqr"):
+        f["rho"] = qr[:, :J]
+        o = J
+    elif model == "null":
+        f["beta"] = np.zeros((qr.shape[0], nb))
+        o = nb
+    else:
+        f["beta"] = qr[:, :nb]
+        o = nb
+    if model != "mlirt":
+        f["sigp"] = qr[:, o:o + 4]
+        o += 4
+    if nnu and qr.shape[1] == base + nnu:
+        f["nu"] = qr[:, o:]
+    return f
+
+
+def expected_mean(fields, n_burnin, n_chain):
+    """Post.mean of decoded trace rows: the reference's joint mean over iterations m > nBurnin and all chains, i.e. over rows
+    r >= n_burnin * n_chain.  Summed and divided in np.longdouble (64-bit significand: adding a few thousand fp64 values loses
+    less than 2^-11 of one fp64 round-off), so the reference side carries no summation error an fp64 bound would see.
+    Returns (mean, abs_sum, n): dicts of longdouble vectors -- the mean and sum |x_t| over the same rows -- and the row count."""
+    if np.finfo(np.longdouble).nmant < 63:
+        raise RuntimeError("np.longdouble is not wider than fp64 on this platform")
+    lo = int(n_burnin) * int(n_chain)
+    mean, asum, n = {}, {}, 0
+    for k, v in fields.items():
+        x = np.asarray(v)[lo:].astype(np.longdouble)
+        n = x.shape[0]
+        if n <= 0:
+            raise ValueError("no post-burn-in rows")
+        mean[k] = x.sum(axis=0) / np.longdouble(n)
+        asum[k] = np.abs(x).sum(axis=0)
+    return mean, asum, n
+
+
+def mean_excess(dev, mean, abs_sum, n, extra=2):
+    """How far a device mean is outside its rounding bound, in units of the bound (<= 1 passes).  The device adds n post-burn-in draws in
+    fp64 in row order (error <= (n - 1) u sum|x_t|) and multiplies by the rounded 1 / n (two more roundings):
+    |dev - ref| <= (n + extra) u sum|x_t| / n, entry by entry.  An entry whose draws are all zero must be exactly zero."""
+    d = np.abs(np.asarray(dev).astype(np.longdouble) - mean)
+    bound = np.longdouble(n + extra) * np.longdouble(U53) * abs_sum / np.longdouble(n)
+    out = np.zeros(d.shape, dtype=np.float64)
+    nz = bound > 0
+    out[nz] = (d[nz] / bound[nz]).astype(np.float64)
+    out[~nz & (d > 0)] = np.inf
+    return out

@@ -19,9 +19,24 @@ def _sampler(pkg, model, N, J, *, precision, nIter=20, nChain=2, seed=11):
     return getattr(pkg, CLS[model])(Cond, Data=D, precision=precision), (Y, logT, X)
 
 
-def _oracle_loglik_at_mean(model, M, data):
+def _trace_mean(model, M):
+    """Post.mean recomputed from Post.ra / rt / qr (parity_util.expected_mean: rows >= nBurnin * nChain, extended precision), as an InputPara-like
+    namespace: independent of the device's running sums and of its row count."""
+    import types
+    C, P = M.Cond, M.Post
+    f = pu.decode_rows(model, C.nSubj, C.nItem, 0 if model in ("crossqr", "cross") else C.nFeat, pu.trace_rows(P.ra),
+                       None if model == "mlirt" else pu.trace_rows(P.rt), pu.trace_rows(P.qr))
+    mean, _, n = pu.expected_mean(f, C.nBurnin, C.nChain)
+    assert n == (C.nIter - C.nBurnin) * C.nChain
+    m = {k: v.astype(np.float64) for k, v in mean.items()}
+    e = np.zeros(0)
+    return types.SimpleNamespace(theta=m["theta"], a=m["a"], b=m["b"], zeta=m.get("zeta", e), lam=m.get("lambda_", e), sig2t=m.get("sig2t", e), Sigp=m.get("sigp", e),
+                                 beta=m.get("beta", e), rho=m.get("rho", e), nu=m.get("nu", e))
+
+
+def _oracle_loglik_at_mean(model, M, data, P=None):
     Y, logT, X = data
-    P = M.Post.mean
+    P = M.Post.mean if P is None else P
     st = dict(theta=P.theta, a=P.a, b=P.b)
     if model != "mlirt":
         st.update(zeta=P.zeta, lam=P.lam, sig2t=P.sig2t, sigp=P.Sigp)
@@ -50,6 +65,10 @@ def test_device_dic_equals_the_host_evaluation_and_the_oracle(model, precision):
     assert abs(d["Dbar"] - Dbar_host) <= 1e-12 * abs(Dbar_host)
     assert abs(d["Dhat"] - Dhat_host) <= tol * abs(Dhat_host)
     assert abs(d["Dhat"] + 2.0 * _oracle_loglik_at_mean(model, M, data)) <= tol * abs(Dhat_host)
+    # ... and at the mean of the post-burn-in TRACE rows: the three evaluations above all start from the device's own Post.mean
+    Dhat_trace = -2.0 * _oracle_loglik_at_mean(model, M, data, _trace_mean(model, M))
+    print(f"{model} {precision}: Dhat {d['Dhat']!r}, oracle at the trace mean {Dhat_trace!r}, rel {abs(d['Dhat'] - Dhat_trace) / abs(Dhat_host):.3g}")
+    assert abs(d["Dhat"] - Dhat_trace) <= tol * abs(Dhat_host)
     assert abs(d["pD"] - (d["Dbar"] - d["Dhat"])) <= 1e-9 * abs(d["Dbar"]) and abs(d["DIC"] - (d["Dbar"] + d["pD"])) <= 1e-9 * abs(d["Dbar"])
     got = pkg.getDic(M)                       # the public getDic takes the device path
     assert got.DIC == d["DIC"] and got.pD == d["pD"]

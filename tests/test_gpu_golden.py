@@ -9,6 +9,21 @@ from test_oracle_sweeps import load_golden
 pytestmark = pytest.mark.gpu
 
 
+def _assert_post_mean(model, M, names):
+    """Post.mean against the mean of the post-burn-in rows of Post.ra / rt / qr within the rounding bound of an fp64 running sum
+    (parity_util.expected_mean / mean_excess; derived in test_gpu_post_mean.py), for every field the sampler has."""
+    C, P = M.Cond, M.Post
+    f = pu.decode_rows(model, C.nSubj, C.nItem, 0 if model in ("crossqr", "cross") else C.nFeat, pu.trace_rows(P.ra),
+                       None if model == "mlirt" else pu.trace_rows(P.rt), pu.trace_rows(P.qr))
+    mean, asum, n = pu.expected_mean(f, C.nBurnin, C.nChain)
+    assert n == (C.nIter - C.nBurnin) * C.nChain and set(names) <= set(f)
+    for k in f:
+        got = np.asarray(getattr(P.mean, {"lambda_": "lam", "sigp": "Sigp"}.get(k, k)), dtype=np.float64).reshape(-1, order="F")
+        assert got.shape == mean[k].shape, k
+        ex = pu.mean_excess(got, mean[k], asum[k], n).max()
+        assert ex <= 1.0, (model, k, ex)
+
+
 @pytest.mark.parametrize("model", ["mlirt", "rtirt", "latentqr", "crossqr", "null", "cross", "latent"])
 def test_engine_reproduces_golden_traces(model):
     z, Y, logT, X, init = load_golden(model)
@@ -33,8 +48,8 @@ def test_sample_bang_fills_post_like_the_reference():
     assert pkg.sample_b(M) is M
     P = M.Post
     assert P.ra.shape == (6, N + 2 * J, 2) and P.rt.shape == (6, N + 2 * J, 2) and P.qr.shape == (6, 12, 2) and P.logLike.shape == (6, 1, 2)
-    assert np.allclose(P.mean.theta, P.ra[3:, :N, :].mean(axis=(0, 2))) and np.allclose(P.mean.sig2t, P.rt[3:, N + J:, :].mean(axis=(0, 2)))
-    assert np.allclose(P.mean.beta, P.qr[3:, :8, :].mean(axis=(0, 2))) and P.mean.Sigp.shape == (4,)
+    assert Cond.nBurnin == 3 and P.mean.Sigp.shape == (4,)
+    _assert_post_mean("rtirt", M, ("theta", "sig2t", "beta"))
     assert np.array_equal(M.Para.theta, P.ra[5, :N, 1]) and np.array_equal(M.Para.b, P.ra[5, N + J:, 1])
     assert np.all(P.qr[:, 0, :] == 0) and np.all(P.qr[:, 4, :] == 0)          # intercept=false
     assert np.all(P.qr[:, 8, :] == 1) and np.all(P.qr[:, 11, :] == 1)         # cov2one=true
@@ -64,13 +79,14 @@ def test_variant_samplers_fill_post_like_the_reference(name, model):
     P = M.Post
     wq = {"null": 12, "cross": J + 4, "latent": 9}[model]
     assert P.ra.shape == (6, N + 2 * J, 2) and P.rt.shape == (6, N + 2 * J, 2) and P.qr.shape == (6, wq, 2) and P.logLike.shape == (6, 1, 2)
-    assert np.allclose(P.mean.theta, P.ra[3:, :N, :].mean(axis=(0, 2))) and np.allclose(P.mean.lam, P.rt[3:, N:N + J, :].mean(axis=(0, 2)))
+    assert Cond.nBurnin == 3
+    _assert_post_mean(model, M, {"null": ("theta", "lambda_", "sigp"), "cross": ("theta", "lambda_", "rho"), "latent": ("theta", "lambda_", "beta")}[model])
     if model == "null":
-        assert np.all(P.qr[:, :8, :] == 0) and np.all(P.mean.beta == 0) and np.allclose(P.mean.Sigp, P.qr[3:, 8:, :].mean(axis=(0, 2)))
+        assert np.all(P.qr[:, :8, :] == 0) and np.all(P.mean.beta == 0)
     if model == "cross":
-        assert np.allclose(P.mean.rho, P.qr[3:, :J, :].mean(axis=(0, 2))) and np.all(P.qr[:, J:, :] == np.array([1, 0, 0, 1])[None, :, None])
+        assert np.all(P.qr[:, J:, :] == np.array([1, 0, 0, 1])[None, :, None])
     if model == "latent":
-        assert np.allclose(P.mean.beta, P.qr[3:, :5, :].mean(axis=(0, 2))) and np.all(P.qr[:, 0, :] == 0) and np.all(P.qr[:, 5, :] == 1)
+        assert np.all(P.qr[:, 0, :] == 0) and np.all(P.qr[:, 5, :] == 1)
         assert not np.all(P.qr[:, 8, :] == 1)                                  # cov2one defaults to false for Latent
     d = pkg.getDic(M)
     assert np.isfinite(d.DIC) and np.isfinite(d.pD)
@@ -88,8 +104,8 @@ def test_crossqr_post_qr_carries_rho_sigp_and_vec_nu():
     P = M.Post
     assert P.qr.shape == (6, J + 4 + N * J, 1)
     assert np.all(P.qr[:, J + 4:, 0] > 0)
-    assert np.allclose(np.asarray(P.mean.nu).reshape(-1, order="F"), P.qr[3:, J + 4:, 0].mean(axis=0), rtol=1e-12)
-    assert np.allclose(P.mean.rho, P.qr[3:, :J, 0].mean(axis=0))
+    assert Cond.nBurnin == 3 and np.asarray(P.mean.nu).size == N * J
+    _assert_post_mean("crossqr", M, ("nu", "rho"))
 
 
 @pytest.mark.parametrize("name,model,nchain", [("GibbsRtIrt", "rtirt", 1), ("GibbsRtIrt", "rtirt", 2), ("GibbsRtIrtLatentQr", "latentqr", 1),
