@@ -41,7 +41,8 @@ enum { ERM_TRACE_RA = 0, ERM_TRACE_RT = 1, ERM_TRACE_QR = 2, ERM_TRACE_LOGLIKE =
  * (intercept, itemtype, cov2one: src/GibbsRtIrt.pl.jl:210,278; src/GibbsRtIrtCross.pl.jl:265; src/GibbsRtIrtLatent.pl.jl:271). */
 typedef struct {
     int32_t model;          /* ERM_MODEL_* */
-    int32_t n_item;         /* Cond.nItem; 1 .. 896 (the fused sweep kernel keeps per-wave item accumulators in LDS; beyond ~400 items the engine takes the two-kernel schedule) */
+    int32_t n_item;         /* Cond.nItem; 1 .. 896 (the fused sweep kernel keeps per-wave item accumulators in LDS; the single-pass models keep the fused sweep up to 512 items in fp64
+                             * and 640 in fp32 (GibbsMlIrt, with four statistics per item, a little further); beyond that, and always for the Cross family, the engine takes the two-kernel schedule) */
     int64_t n_subj;         /* Cond.nSubj */
     int32_t n_feat;         /* Cond.nFeat (columns of Data.X; ignored by the Cross family and Null); 0 .. 14 (the structural draws hold the <= 16-column design [1 X theta] in LDS) */
     int32_t n_iter;         /* Cond.nIter */

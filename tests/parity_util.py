@@ -2,8 +2,10 @@
 inputs through the HIP library (via its C ABI) and through the oracle.  Test infrastructure only."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -215,6 +217,16 @@ def run_pair(model, N, J, nsweeps, *, F=3, precision="f64", seed=7, qRt=0.85, **
     return d
 
 
+@contextlib.contextmanager
+def oracle_threads(n):
+    """The oracle's OpenMP mode for the enclosed runs (bit-identical to its single-thread run: tests/test_oracle_sweeps.py)."""
+    oracle().orc_set_threads(int(n))
+    try:
+        yield
+    finally:
+        oracle().orc_set_threads(1)
+
+
 def rel_err(x, y, floor=1e-6):
     x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
     return np.abs(x - y) / np.maximum(np.abs(y), floor)
@@ -227,6 +239,74 @@ def max_rel_err(res, floor=1e-6):
     e.append(rel_err(res["dev_qr"], res["orc"]["qr"], floor).max())
     e.append(rel_err(res["dev_ll"], res["orc"]["ll"], floor).max())
     return float(max(e))
+
+
+def rel_err_by_part(res, floor=1e-6):
+    """max_rel_err taken apart: {part: (largest error, sweep, column)} for the ra, rt, qr and ll traces of a run_pair result."""
+    parts = [("ra", res["dev_ra"], res["orc"]["ra"])]
+    if res["model"] != "mlirt":
+        parts.append(("rt", res["dev_rt"], res["orc"]["rt"]))
+    parts += [("qr", res["dev_qr"], res["orc"]["qr"]), ("ll", res["dev_ll"][:, None], np.asarray(res["orc"]["ll"])[:, None])]
+    out = {}
+    for name, d, o in parts:
+        e = rel_err(d, o, floor)
+        t, k = np.unravel_index(int(np.argmax(e)), e.shape)
+        out[name] = (float(e[t, k]), int(t), int(k))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The launch-geometry planner on the CPU: tests/geometry_check.cpp compiled against extendedrtirtmodeling.jl_amd/csrc/erm_geometry.hpp, the header
+# Engine::init plans with.  `exe` is a pytest fixture (test modules import it by name); plan() runs the checker's `case` mode.
+GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")
+GEOMETRY_INC = os.path.join(ROOT, "extendedrtirtmodeling.jl_amd", "csrc")
+ITEM_STRIDE = 128               # erm_layout.hpp: item_stride(J) is this constant for J <= 128 and J beyond
+CQ_MODELS = ("crossqr", "cross")            # two row passes per sweep: never fused, never persistent
+
+
+def build_geometry_check(out):
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=all", "-ftrapv", "-I", GEOMETRY_INC, GEOMETRY_SRC, "-o", out], check=True)
+    return out
+
+
+try:
+    import pytest
+except ImportError:             # smoke() and bench.py use this module without pytest
+    pytest = None
+if pytest is not None:
+    @pytest.fixture(scope="module")
+    def exe(tmp_path_factory):
+        return build_geometry_check(str(tmp_path_factory.mktemp("geom") / "geometry_check"))
+
+
+def plan(exe, model, f64, N, J, Fk, bt=0, gb=0, W=0, cus=256, nofuse=0, nopersist=0):
+    r = subprocess.run([exe, "case"] + [str(v) for v in (model, f64, N, J, Fk, bt, gb, W, cus, nofuse, nopersist)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    out = r.stdout.strip()
+    if out.startswith("error="):
+        return {"error": out[6:]}
+    return dict(kv.split("=", 1) for kv in out.split())
+
+
+def kernel_feat(model, F):
+    """Covariate columns the kernels see (GeomIn.Fk): the Cross family and Null never read Data.X."""
+    return 0 if model in CQ_MODELS or model == "null" else F
+
+
+def engine_plan(exe, model, precision, N, J, F, cu_count, *, lanes_per_row=0, block_threads=0, grid_blocks=0, flags=0):
+    """The CPU planner's plan for an engine's (model, precision, N, J, F, overrides, schedule flags) on a card with `cu_count` compute units, as integers."""
+    p = plan(exe, MODELS[model], int(precision == "f64"), N, J, kernel_feat(model, F), bt=block_threads, gb=grid_blocks, W=lanes_per_row, cus=cu_count,
+             nofuse=int(bool(flags & 1)), nopersist=int(bool(flags & 8)))          # ERM_FLAG_NO_FUSE = 1, ERM_FLAG_NO_PERSIST = 8 (include/ertirt.h)
+    assert "error" not in p, p
+    return {k: int(v) for k, v in p.items()}
+
+
+def assert_engine_runs_plan(tm, p):
+    """erm_get_timing of an engine against the CPU planner's plan for the same inputs: the launch geometry, the LDS request and the schedule."""
+    got = (tm["lanes_per_row"], tm["block_threads"], tm["grid_blocks"], tm["lds_bytes"], tm["persistent"])
+    want = (p["W"], p["block_threads"], p["grid_blocks"], max(p["lds0"], p["lds1"]), p["persist"])
+    assert got == want, f"engine runs (W, threads, grid, lds, persistent) = {got}, the planner says {want}"
+    assert tm["persist_fallbacks"] == 0, tm
 
 
 # ---------------------------------------------------------------------------------------------------------------

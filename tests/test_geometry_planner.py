@@ -3,31 +3,11 @@ with UndefinedBehaviorSanitizer and -ftrapv (division by zero, signed overflow a
 N in 1 ... 2^32, J in 1 ... 896, F in 0 ... 14, every model and precision, the caller's overrides and odd compute-unit counts; every accepted plan
 must satisfy the invariants the kernels rely on (LDS dynamic + static <= 160 KB, < 2^22 cells per workgroup, slices that hold the workgroup's
 subjects, an 8-byte aligned accumulator region inside the allocation).  Named cases below are the geometry failures of earlier rounds."""
-import os
 import subprocess
 
 import pytest
 
-import parity_util as pu
-
-SRC = os.path.join(pu.ROOT, "tests", "geometry_check.cpp")
-INC = os.path.join(pu.ROOT, "extendedrtirtmodeling.jl_amd", "csrc")
-
-
-@pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("geom") / "geometry_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=all", "-ftrapv", "-I", INC, SRC, "-o", out], check=True)
-    return out
-
-
-def plan(exe, model, f64, N, J, Fk, bt=0, gb=0, W=0, cus=256, nofuse=0, nopersist=0):
-    r = subprocess.run([exe, "case"] + [str(v) for v in (model, f64, N, J, Fk, bt, gb, W, cus, nofuse, nopersist)], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    out = r.stdout.strip()
-    if out.startswith("error="):
-        return {"error": out[6:]}
-    return dict(kv.split("=", 1) for kv in out.split())
+from parity_util import exe, plan  # noqa: F401  (exe is the compiled-checker fixture)
 
 
 def test_sweep_has_no_undefined_behaviour_and_every_plan_keeps_the_invariants(exe):
