@@ -26,6 +26,7 @@ EXPORTS = [
     "erm_farm_create", "erm_farm_destroy", "erm_farm_chains", "erm_farm_engine", "erm_farm_set_data", "erm_farm_set_state", "erm_farm_get_state",
     "erm_farm_run", "erm_farm_reset_trace", "erm_farm_get_trace", "erm_farm_get_mean", "erm_farm_post_count", "erm_farm_used_rccl", "erm_farm_get_timing",
     "erm_get_dic", "erm_set_seed", "erm_farm_get_dic", "erm_farm_set_seed", "erm_abi_version", "erm_debug_invwishart", "erm_get_convergence",
+    "erm_set_pointwise", "erm_get_waic", "erm_pointwise_units", "erm_get_pointwise",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -45,6 +46,8 @@ class erm_config(C.Structure):
     ]
 
 
+POINTWISE_OFF, POINTWISE_SUBJECT, POINTWISE_CELL = 0, 1, 2      # erm_set_pointwise: the unit of WAIC
+POINTWISE_UNITS = {None: POINTWISE_OFF, "subject": POINTWISE_SUBJECT, "cell": POINTWISE_CELL}
 FLAG_NO_FUSE, FLAG_NO_GRAPH, FLAG_FARM_FORCE_RCCL, FLAG_NO_PERSIST, FLAG_TEST_PERSIST_TIMEOUT = 1, 2, 4, 8, 16
 
 
@@ -138,6 +141,11 @@ def load():
     lib.erm_farm_get_timing.argtypes = [H, C.POINTER(erm_farm_timing), C.c_void_p]
     lib.erm_get_dic.argtypes = [H, C.c_void_p]
     lib.erm_get_convergence.argtypes = [H, C.c_int, C.c_void_p]
+    lib.erm_set_pointwise.argtypes = [H, C.c_int]
+    lib.erm_get_waic.argtypes = [H, C.c_void_p]
+    lib.erm_pointwise_units.argtypes = [H]
+    lib.erm_pointwise_units.restype = C.c_int64
+    lib.erm_get_pointwise.argtypes = [H, C.c_void_p, C.c_void_p]
     lib.erm_set_seed.argtypes = [H, C.c_uint64]
     lib.erm_farm_get_dic.argtypes = [H, C.c_void_p]
     lib.erm_farm_set_seed.argtypes = [H, C.c_uint64]
@@ -297,6 +305,36 @@ class Engine:
         out = np.empty(4, dtype=np.float64)
         check(self._lib.erm_get_dic(self._h, out.ctypes.data))
         return dict(Dbar=float(out[0]), Dhat=float(out[1]), pD=float(out[2]), DIC=float(out[3]))
+
+    # ---- WAIC (erm_set_pointwise / erm_get_waic / erm_get_pointwise)
+    def set_pointwise(self, unit):
+        """Enable WAIC with unit "subject" or "cell" (or a POINTWISE_* code), None / POINTWISE_OFF turns it off; only while no trace row is recorded."""
+        if unit is None or isinstance(unit, str):
+            if unit not in POINTWISE_UNITS:
+                raise ValueError("waic must be None, 'subject' or 'cell'")
+            unit = POINTWISE_UNITS[unit]
+        check(self._lib.erm_set_pointwise(self._h, int(unit)))
+
+    @property
+    def pointwise_units(self):
+        return int(self._lib.erm_pointwise_units(self._h))
+
+    def waic(self):
+        """erm_get_waic: the totals, finished and summed on the device."""
+        out = np.empty(8, dtype=np.float64)
+        check(self._lib.erm_get_waic(self._h, out.ctypes.data))
+        return dict(elpd=float(out[0]), pWaic=float(out[1]), WAIC=float(out[2]), se=float(out[3]), lppd=float(out[4]), nUnits=int(out[5]), nRows=int(out[6]),
+                    nHighVar=int(out[7]))
+
+    def pointwise(self):
+        """erm_get_pointwise: (lppd_u, p_u); subjects in order, cells as an (nSubj, nItem) Fortran-ordered array."""
+        U = self.pointwise_units
+        lppd, p = np.empty(U, dtype=np.float64), np.empty(U, dtype=np.float64)
+        check(self._lib.erm_get_pointwise(self._h, lppd.ctypes.data, p.ctypes.data))
+        if U == self.cfg.n_subj * self.cfg.n_item and U != self.cfg.n_subj:
+            sh = (self.cfg.n_subj, self.cfg.n_item)
+            return lppd.reshape(sh, order="F"), p.reshape(sh, order="F")
+        return lppd, p
 
     @property
     def rows_done(self):

@@ -97,3 +97,21 @@ class OutputDic:
 
     def __repr__(self):
         return f"OutputDic(pD={self.pD}, DIC={self.DIC})"
+
+
+class OutputWaic:
+    """WAIC of a fit (getWaic; the reference offers DIC only): elpd = sum_u (lppd_u - p_u), pWaic = sum_u p_u, WAIC = -2 elpd, se = 2 sqrt(U Var_u(elpd_u)),
+    nHighVar = number of units with p_u > 0.4; unit is "subject" or "cell", nUnits = U, nRows = the post-burn-in rows behind it.  lppd_u / p_u (pointwise=True):
+    subjects in order, cells as (nSubj, nItem)."""
+
+    def __init__(self, elpd=None, pWaic=None, WAIC=None, se=None, nHighVar=None, lppd=None, unit=None, nUnits=None, nRows=None, lppd_u=None, p_u=None):
+        self.elpd, self.pWaic, self.WAIC, self.se, self.nHighVar = elpd, pWaic, WAIC, se, nHighVar
+        self.lppd, self.unit, self.nUnits, self.nRows = lppd, unit, nUnits, nRows
+        self.lppd_u, self.p_u = lppd_u, p_u
+
+    @property
+    def elpd_u(self):
+        return None if self.lppd_u is None else self.lppd_u - self.p_u
+
+    def __repr__(self):
+        return f"OutputWaic(unit={self.unit!r}, elpd={self.elpd}, pWaic={self.pWaic}, WAIC={self.WAIC}, se={self.se}, nHighVar={self.nHighVar})"

@@ -2511,3 +2511,5 @@ __global__ void gig_batch_kernel(uint64_t seed, uint32_t site, uint32_t sweep, l
 }
 
 }  // namespace erm
+
+#include "erm_waic_kernels.hpp"     // WAIC: the pointwise log-likelihood pass behind every sweep and its finish

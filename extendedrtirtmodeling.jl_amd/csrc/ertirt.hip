@@ -117,6 +117,11 @@ struct EngineBase {
     virtual int get_diagnostics(int, double*, double*) = 0;
     virtual int get_convergence(int, int64_t*) = 0;
     virtual int get_dic(double*) = 0;
+    // WAIC (erm_set_pointwise / erm_get_waic / erm_pointwise_units / erm_get_pointwise)
+    virtual int set_pointwise(int unit) = 0;
+    virtual int get_waic(double* out8) = 0;
+    virtual int64_t pointwise_units() const = 0;
+    virtual int get_pointwise(double* lppd_u, double* p_u) = 0;
     virtual int set_seed(uint64_t) = 0;
     // DIC pieces for the chain farm: the log-likelihood at sum * inv (sum: a device vector in the summary layout) and the sum of the recorded logLike rows
     virtual int loglik_at(const double* dsum, double inv, double* ll) = 0;
@@ -202,6 +207,12 @@ template <typename real> struct Engine : EngineBase {
     bool fuse_ok = true;                              // false when the fused kernel's LDS layout cannot fit (very long tests): two kernels per sweep then
     bool fused() const { return !m_cq() && fuse_ok; }  // single-pass models run the tiny step inside the row-pass kernel
     DevBuf dSumTheta, dSumZeta, dSumNu, dTrTheta, dTrZeta, dTrNu, dTrItem, dTrLl;
+    // WAIC (erm_set_pointwise): the unit, the accumulators {m, s}[units] and {mean, m2}[units] (erm_pointwise.hpp), GibbsRtIrtCrossQr's copy of nu_t
+    // (taken ahead of pass B of every sweep, which overwrites nu_t with nu_{t+1}: N * J values of the engine's cell type)
+    int pw_unit = PW_OFF;
+    DevBuf dPwMs, dPwW, dNuSnap;
+    bool persist_avail = false;                       // the persistent schedule as init() / erm_set_shard / a time-out left it: an engine with WAIC enabled plans
+                                                      // per-sweep launches at the same geometry (as ERM_FLAG_NO_PERSIST does) and returns to it when WAIC is turned off
 
     ~Engine() override {
         drop_graphs();
@@ -359,7 +370,9 @@ template <typename real> struct Engine : EngineBase {
         persist_fault_countdown = (cfg.flags & ERM_FLAG_TEST_PERSIST_TIMEOUT) ? 2 : 0;
         timing.lanes_per_row = W; timing.block_threads = block_threads; timing.grid_blocks = grid_blocks;
         timing.lds_bytes = (int32_t)std::max(lds_pass[0], lds_pass[1]); timing.cu_count = cu_count; timing.persistent = persist ? 1 : 0;
-        return configure_kernels();
+        if (int rc = configure_kernels()) return rc;
+        persist_avail = persist;
+        return 0;
     }
 
     // -------------------------------------------------------------------------------------------- kernels
@@ -475,11 +488,13 @@ template <typename real> struct Engine : EngineBase {
         if (close) { ++n_brackets; n_pass_timed += launches; bracket_launches.push_back((int)launches); }
         return 0;
     }
-    template <int MODEL, int PHASE> int launch_pass(int mode, bool timed) {
+    // (pw: this launch completes a sweep -- the pointwise pass of an engine with WAIC enabled follows it, inside the launch's event bracket)
+    template <int MODEL, int PHASE> int launch_pass(int mode, bool timed, bool pw = false) {
         PassArgs<real> a = pass_args(PHASE, mode);
         TinyArgs t{};
         if (timed) { if (int rc = bracket(false)) return rc; }
         hipLaunchKernelGGL((pass_kernel<MODEL, real, PHASE, false>), dim3(grid_blocks), dim3(block_threads), lds_pass[PHASE], stream, a, t);
+        if (pw) { if (int rc = launch_pointwise<MODEL>(cur)) return rc; }
         if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(PHASE, a.gslab);
         return 0;
@@ -512,6 +527,7 @@ template <typename real> struct Engine : EngineBase {
     }
     int set_shard(int rank, int count, int64_t ntot, int64_t base, erm_exchange_fn fn, void* user, const void* rccl_id) override {
         if (has_data || rows_done > 0 || sharded()) return fail(ERM_ERR_STATE, "erm_set_shard must precede erm_set_data and be called once");
+        if (pw_unit != PW_OFF) return fail(ERM_ERR_STATE, "an engine with WAIC enabled cannot become a shard (sharding: erm_set_pointwise)");
         if (count < 1 || rank < 0 || rank >= count) return fail(ERM_ERR_ARG, "bad shard rank / count");
         if (!fn && !rccl_id) return fail(ERM_ERR_ARG, "exchange callback / RCCL id is NULL");
         if (base < 0 || ntot < N || base + N > ntot) return fail(ERM_ERR_ARG, "local subjects must lie inside [0, n_subj_total)");
@@ -527,7 +543,7 @@ template <typename real> struct Engine : EngineBase {
             RCCLCHK(g_rccl.CommInitRank(&comm, count, id, rank));
         }
         shard_rank = rank; shard_count = count; n_total = ntot; row_base = base; exch = fn; exch_user = user;
-        persist = false; timing.persistent = 0;          // a sharded sweep exchanges its statistics rows on the host side of every launch
+        persist = false; persist_avail = false; timing.persistent = 0;          // a sharded sweep exchanges its statistics rows on the host side of every launch
         return 0;
     }
     // one whole sweep of a single-pass model: tiny step + row pass in one launch; reads buffers [cur], writes [1 - cur]
@@ -536,6 +552,7 @@ template <typename real> struct Engine : EngineBase {
         TinyArgs t = tiny_args(0, true);
         if (timed) { if (int rc = bracket(false)) return rc; }
         hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true>), dim3(grid_blocks), dim3(block_threads), fused_lds(), stream, a, t);
+        if (int rc = launch_pointwise<MODEL>(1 - cur)) return rc;      // the sweep published its parameter block and counters in buffer [1 - cur]
         if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(0, a.gslab);     // a.gslab: the group rows this launch wrote
         return 0;
@@ -575,12 +592,129 @@ template <typename real> struct Engine : EngineBase {
     template <int MODEL> int enqueue_sweep(bool timed) {
         if constexpr (!fam_cq(MODEL)) { if (fused()) return launch_fused<MODEL>(timed); }
         if (int rc = launch_tiny<MODEL, 0>(0)) return rc;
-        if (int rc = launch_pass<MODEL, 0>(1, timed)) return rc;
+        if (int rc = launch_pass<MODEL, 0>(1, timed, !fam_cq(MODEL))) return rc;
         if constexpr (fam_cq(MODEL)) {
             if (int rc = launch_tiny<MODEL, 1>(0)) return rc;
-            if (int rc = launch_pass<MODEL, 1>(1, timed)) return rc;
+            // WAIC on GibbsRtIrtCrossQr: pass B overwrites nu_t with nu_{t+1} in the phase that uses it, so nu_t is copied first (a memcpy node inside a graph)
+            if (MODEL == CROSSQR && pw_unit != PW_OFF) HIPCHK(hipMemcpyAsync(dNuSnap.p, dNu.p, dNu.bytes, hipMemcpyDeviceToDevice, stream));
+            if (int rc = launch_pass<MODEL, 1>(1, timed, true)) return rc;
         }
         return 0;
+    }
+    // ---- WAIC: the pointwise pass behind a sweep (erm_waic_kernels.hpp).  buf: the half of the double buffers the sweep published its parameter block and
+    // counters in.  The same launch for every sweep (the kernel itself skips burn-in rows), so it sits inside the captured graphs like the sweep's own kernels.
+    int64_t pw_units(int unit) const { return unit == PW_SUBJECT ? N : unit == PW_CELL ? N * (int64_t)J : 0; }
+    template <int MODEL> int launch_pointwise(int buf) {
+        if (pw_unit == PW_OFF) return 0;
+        PwArgs a{};
+        a.Y = dY.as<uint8_t>(); a.C = dC.p; a.nu = MODEL == CROSSQR ? dNuSnap.p : nullptr; a.theta = dTheta.p; a.zeta = dZeta.p;
+        a.par = dParB[buf].template as<double>(); a.cm = dCst.as<double>() + cst_off_m(J); a.ctl = dCtlB[buf].template as<Ctl>();
+        a.acc_ms = dPwMs.as<double2>(); a.acc_w = dPwW.as<double2>();
+        a.N = N; a.J = J;
+        int lw = 0;
+        while ((1 << lw) < 64 && (4 << lw) < J) ++lw;      // lanes per subject: the smallest power of two that leaves a lane at most four items (64 at most)
+        a.logW = lw;
+        const double q = cfg.q_rt;
+        a.k1 = m_nu() ? (1.0 - 2.0 * q) / (q * (1.0 - q)) : 0.0; a.k2 = m_nu() ? 2.0 / (q * (1.0 - q)) : 1.0;
+        const size_t lds = (size_t)7 * J * sizeof(double);
+        if (pw_unit == PW_SUBJECT) {
+            const int64_t R = 256 >> lw;
+            const int nb = (int)std::min<int64_t>((N + R - 1) / R, (int64_t)cu_count * 8);
+            hipLaunchKernelGGL((pointwise_kernel<MODEL, real, PW_SUBJECT>), dim3(nb), dim3(256), lds, stream, a);
+        } else {
+            const int nb = (int)std::min<int64_t>((N * (int64_t)J + 255) / 256, (int64_t)cu_count * 16);
+            hipLaunchKernelGGL((pointwise_kernel<MODEL, real, PW_CELL>), dim3(nb), dim3(256), lds, stream, a);
+        }
+        return 0;
+    }
+    static int alloc_or_nomem(DevBuf& d, size_t n) {
+        void* q = nullptr;
+        if (hipMalloc(&q, n) != hipSuccess) { (void)hipGetLastError(); return fail(ERM_ERR_NOMEM, "out of device memory for the WAIC accumulators (" + std::to_string(n) + " bytes)"); }
+        if (d.p) (void)hipFree(d.p);
+        d.p = q; d.bytes = n;
+        return 0;
+    }
+    int pw_clear() {
+        if (dPwMs.p) { HIPCHK(hipMemsetAsync(dPwMs.p, 0, dPwMs.bytes, stream)); HIPCHK(hipMemsetAsync(dPwW.p, 0, dPwW.bytes, stream)); }
+        return 0;
+    }
+    int set_pointwise(int unit) override {
+        if (unit != PW_OFF && unit != PW_SUBJECT && unit != PW_CELL) return fail(ERM_ERR_ARG, "unknown pointwise unit (ERM_POINTWISE_OFF / _SUBJECT / _CELL)");
+        if (rows_done > 0) return fail(ERM_ERR_STATE, "erm_set_pointwise is allowed only while no trace row is recorded (after erm_create or erm_reset_trace)");
+        if (unit != PW_OFF && sharded()) return fail(ERM_ERR_STATE, "WAIC is not available under subject sharding (the accumulators of the shards would have to be merged across devices)");
+        HIPCHK(hipSetDevice(cfg.device));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (unit != PW_OFF) {
+            // the new buffers first: a failed allocation leaves the engine exactly as it was
+            const size_t nb = (size_t)pw_units(unit) * sizeof(double2);
+            DevBuf ms, w, snap;
+            if (nb != dPwMs.bytes) { if (int rc = alloc_or_nomem(ms, nb)) return rc; if (int rc = alloc_or_nomem(w, nb)) return rc; }
+            if (cfg.model == ERM_MODEL_CROSSQR && !dNuSnap.p) { if (int rc = alloc_or_nomem(snap, dNu.bytes)) return rc; }
+            if (ms.p) { std::swap(ms.p, dPwMs.p); std::swap(ms.bytes, dPwMs.bytes); std::swap(w.p, dPwW.p); std::swap(w.bytes, dPwW.bytes); }
+            if (snap.p) { std::swap(snap.p, dNuSnap.p); std::swap(snap.bytes, dNuSnap.bytes); }
+        } else {
+            (void)dPwMs.alloc(0); (void)dPwW.alloc(0); (void)dNuSnap.alloc(0);
+        }
+        if (unit != pw_unit) drop_graphs();          // the captured sweeps hold (or lack) the pointwise launch
+        pw_unit = unit;
+        persist = unit == PW_OFF ? persist_avail : false;      // a persistent launch cannot interleave another kernel between its sweeps
+        timing.persistent = persist ? 1 : 0;
+        return pw_clear();
+    }
+    int64_t pointwise_units() const override { return pw_units(pw_unit); }
+    int pw_ready() {
+        if (pw_unit == PW_OFF) return fail(ERM_ERR_STATE, "WAIC is not enabled on this engine (erm_set_pointwise)");
+        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
+        if (post_rows < 2) return fail(ERM_ERR_STATE, "WAIC needs at least two post-burn-in rows");
+        HIPCHK(hipSetDevice(cfg.device));
+        return 0;
+    }
+    // one launch of the finish kernel; sums[0..4]: its columns added over the workgroups in order
+    int pw_finish(double center, double* lppd_out, double* p_out, double* sums) {
+        const int64_t U = pointwise_units();
+        const int nb = (int)std::min<int64_t>(1024, (U + 255) / 256);
+        DevBuf dPart;
+        if (int rc = dPart.alloc((size_t)nb * PW_FIN_COLS * sizeof(double))) return rc;
+        PwFinArgs a{};
+        a.acc_ms = dPwMs.as<double2>(); a.acc_w = dPwW.as<double2>(); a.U = U; a.n = post_rows; a.center = center;
+        a.lppd_out = lppd_out; a.p_out = p_out; a.part = dPart.as<double>();
+        hipLaunchKernelGGL(pointwise_finish_kernel, dim3(nb), dim3(256), 0, stream, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        std::vector<double> part((size_t)nb * PW_FIN_COLS);
+        HIPCHK(hipMemcpy(part.data(), dPart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int q = 0; q < PW_FIN_COLS; ++q) { double t = 0.0; for (int b = 0; b < nb; ++b) t += part[(size_t)b * PW_FIN_COLS + q]; sums[q] = t; }
+        return 0;
+    }
+    int get_waic(double* out8) override {
+        if (int rc = pw_ready()) return rc;
+        const double U = (double)pointwise_units();
+        double s0[PW_FIN_COLS], s1[PW_FIN_COLS];
+        if (int rc = pw_finish(0.0, nullptr, nullptr, s0)) return rc;
+        if (int rc = pw_finish(s0[2] / U, nullptr, nullptr, s1)) return rc;      // second pass: squared deviations of elpd_u from its mean over the units
+        const double var_u = U > 1.0 ? s1[3] / (U - 1.0) : 0.0;
+        out8[0] = s0[2]; out8[1] = s0[1]; out8[2] = -2.0 * s0[2]; out8[3] = 2.0 * std::sqrt(U * var_u);
+        out8[4] = s0[0]; out8[5] = U; out8[6] = (double)post_rows; out8[7] = s0[4];
+        return 0;
+    }
+    int get_pointwise(double* lppd_u, double* p_u) override {
+        if (int rc = pw_ready()) return rc;
+        const int64_t U = pointwise_units();
+        DevBuf dL, dP;
+        if (lppd_u) { if (int rc = dL.alloc((size_t)U * sizeof(double))) return rc; }
+        if (p_u) { if (int rc = dP.alloc((size_t)U * sizeof(double))) return rc; }
+        double sums[PW_FIN_COLS];
+        if (int rc = pw_finish(0.0, dL.as<double>(), dP.as<double>(), sums)) return rc;
+        auto down = [&](const DevBuf& d, double* dst) -> int {
+            if (!dst) return 0;
+            if (pw_unit == PW_SUBJECT) { HIPCHK(hipMemcpy(dst, d.p, (size_t)U * sizeof(double), hipMemcpyDeviceToHost)); return 0; }
+            std::vector<double> t((size_t)U);      // cells: device order (row-major) -> the caller's column-major [nSubj][nItem]
+            HIPCHK(hipMemcpy(t.data(), d.p, t.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) dst[(size_t)j * N + i] = t[(size_t)i * J + j];
+            return 0;
+        };
+        if (int rc = down(dL, lppd_u)) return rc;
+        return down(dP, p_u);
     }
     void launch_run_begin() {
         hipLaunchKernelGGL(run_begin_kernel, dim3(1), dim3(256), 0, stream, dCtlB[0].template as<Ctl>(), dCtlB[1].template as<Ctl>(), host_run_dev, dGcnt.as<unsigned int>(), 2 * n_groups + 4);
@@ -691,7 +825,7 @@ template <typename real> struct Engine : EngineBase {
             // the persistent launch never had all its workgroups resident (another process holds compute units): every workgroup has left the launch;
             // put back what the call found, leave the persistent schedule for good and run the call again, one launch per sweep at the same geometry
             // (bit for bit the chain the persistent launch would have produced)
-            persist = false; timing.persistent = 0; ++timing.persist_fallbacks;
+            persist = false; persist_avail = false; timing.persistent = 0; ++timing.persist_fallbacks;
             rc = snap_copy(true);
             if (rc == 0) { cur = 0; stats_valid = snap_stats_valid; rc = run_checked(nsweeps); }
             if (rc == ERM_PERSIST_TIMEOUT) rc = fail(ERM_ERR_STATE, "internal: persistent time-out reported by a per-sweep run");
@@ -827,7 +961,7 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipMemsetAsync(dSumTheta.p, 0, dSumTheta.bytes, stream));
         HIPCHK(hipMemsetAsync(dSumZeta.p, 0, dSumZeta.bytes, stream));
         if (dSumNu.p) HIPCHK(hipMemsetAsync(dSumNu.p, 0, dSumNu.bytes, stream));
-        return 0;
+        return pw_clear();
     }
 
     // -------------------------------------------------------------------------------------------- data
@@ -1581,6 +1715,10 @@ int erm_get_truth(erm_handle h, double* theta, double* zeta) { CHK_H; return h->
 int erm_get_diagnostics(erm_handle h, int which, double* ess, double* rhat) { CHK_H; if (!ess || !rhat) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_diagnostics(which, ess, rhat); }
 int erm_get_convergence(erm_handle h, int which, int64_t* counts4) { CHK_H; if (!counts4) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_convergence(which, counts4); }
 int erm_get_dic(erm_handle h, double* out4) { CHK_H; if (!out4) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_dic(out4); }
+int erm_set_pointwise(erm_handle h, int unit) { CHK_H; return h->e->set_pointwise(unit); }
+int erm_get_waic(erm_handle h, double* out_eight) { CHK_H; if (!out_eight) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_waic(out_eight); }
+int64_t erm_pointwise_units(erm_handle h) { return h ? h->e->pointwise_units() : -1; }
+int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u) { CHK_H; return h->e->get_pointwise(lppd_u, p_u); }
 int erm_set_seed(erm_handle h, uint64_t seed) { CHK_H; return h->e->set_seed(seed); }
 int erm_get_timing(erm_handle h, erm_timing* out) { CHK_H; if (!out) return fail(ERM_ERR_ARG, "out is NULL"); *out = h->e->timing; return 0; }
 int erm_set_shard(erm_handle h, int rank, int count, int64_t n_subj_total, int64_t row_base, erm_exchange_fn exchange, void* user)

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import InputPara, OutputDic, SimConditions
+from .base import InputPara, OutputDic, OutputWaic, SimConditions
 
 _PREC = {"f32": _lib.PREC_F32, "f64": _lib.PREC_F64}
 _TRACE = {"summary": _lib.TRACE_SUMMARY, "full": _lib.TRACE_FULL}
@@ -270,13 +270,19 @@ def _sample_farm(MCMC: _GibbsBase, intercept, onepl, cov2one, devices):
     return MCMC
 
 
-def sample_b(MCMC: _GibbsBase, *, intercept=False, itemtype="2pl", cov2one=None, devices=None, fill=True):
+def sample_b(MCMC: _GibbsBase, *, intercept=False, itemtype="2pl", cov2one=None, devices=None, fill=True, waic=None):
     """sample!(MCMC; intercept, itemtype, cov2one) -- src/GibbsRtIrt.pl.jl:210,278; Cross :265; Latent :271.
     Runs Cond.nIter * Cond.nChain sweeps (the reference's interleaved `for m in 1:nIter, l in 1:nChain` loop over ONE
     shared Para), fills MCMC.Post, leaves the final state in MCMC.Para and returns MCMC.
     devices = [gpu ordinals]: the nChain chains become INDEPENDENT chains farmed over those GPUs instead (see _sample_farm).
     fill = False leaves Post and Para untouched: traces, running means and the final state stay on the device, where getDic,
-    checkConvergence and MCMC._engine.get_mean(which) read them (runSimulation's replications cross the boundary with summaries only)."""
+    checkConvergence and MCMC._engine.get_mean(which) read them (runSimulation's replications cross the boundary with summaries only).
+    waic = "subject" | "cell": the engine also accumulates the pointwise log-likelihood of every subject / cell over the post-burn-in sweeps (erm_set_pointwise;
+    one more streaming pass per sweep, the chain itself is unchanged); getWaic reads it.  Not available with devices=."""
+    if waic not in _lib.POINTWISE_UNITS:
+        raise ValueError("waic must be None, 'subject' or 'cell'")
+    if waic is not None and (devices is not None or MCMC.shard is not None):
+        raise ValueError("WAIC is not available for a chain farm (devices=) or a subject-sharded sampler: the accumulators of several devices are not merged")
     if itemtype not in ("1pl", "2pl"):
         raise ValueError("Invalid input: the item type must be '1pl' or '2pl'.")   # same text as :213,281
     if cov2one is None:
@@ -290,6 +296,9 @@ def sample_b(MCMC: _GibbsBase, *, intercept=False, itemtype="2pl", cov2one=None,
         MCMC.farm = None
     eng = MCMC._engine_for(intercept, itemtype == "1pl", cov2one)
     eng.reset_trace()
+    if waic is not None or eng.pointwise_units:
+        eng.set_pointwise(waic)
+    MCMC._waic_unit = waic
     eng.set_state(**MCMC._state_for_engine())
     eng.run(MCMC.Cond.nIter * MCMC.Cond.nChain)
     if fill:
@@ -466,6 +475,99 @@ def getDic(MCMC: _GibbsBase) -> OutputDic:
         raise ValueError("run sample! first (getDic reads the engine's resident state)")
     d = src.dic()
     return OutputDic(pD=d["pD"], DIC=d["DIC"])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# WAIC.  Unit u = a subject or a cell; l_u^(s) = the unit's part of the DATA term of getLogLikelihood at the values of post-burn-in trace row s
+# (the structural term -- theta, zeta given beta, Sigp -- is not part of it: the conditional WAIC, leave-one-unit-out given the subject's own parameters).
+# ------------------------------------------------------------------------------------------------------------------
+def getWaic(MCMC: _GibbsBase, pointwise=False) -> OutputWaic:
+    """WAIC of the last sample!(...; waic="subject" | "cell"), from the accumulators the engine kept on the device (erm_get_waic: the per-unit finish and the
+    totals are computed there).  pointwise=True also fetches lppd_u and p_u (erm_get_pointwise), which compareWaic needs."""
+    if getattr(MCMC, "farm", None) is not None:
+        raise ValueError("getWaic is not available for a sampler run through devices= (a chain farm keeps no WAIC accumulators)")
+    eng, unit = MCMC._engine, getattr(MCMC, "_waic_unit", None)
+    if eng is None or unit is None:
+        raise ValueError("run sample!(...; waic='subject' or 'cell') first (getWaic reads the engine's resident accumulators)")
+    w = eng.waic()
+    out = OutputWaic(elpd=w["elpd"], pWaic=w["pWaic"], WAIC=w["WAIC"], se=w["se"], nHighVar=w["nHighVar"], lppd=w["lppd"], unit=unit, nUnits=w["nUnits"], nRows=w["nRows"])
+    if pointwise:
+        out.lppd_u, out.p_u = eng.pointwise()
+    return out
+
+
+def pointwiseLogLikHost(MCMC: _GibbsBase, unit) -> np.ndarray:
+    """l_u^(s) for every post-burn-in row s (iteration >= nBurnin, every interleaved chain) and unit u, with numpy from MCMC.Data and the full Post traces:
+    an (|S|, U) array; cells in column-major order of (nSubj, nItem)."""
+    if unit not in ("subject", "cell"):
+        raise ValueError("unit must be 'subject' or 'cell'")
+    C, D, P, m = MCMC.Cond, MCMC.Data, MCMC.Post, MCMC._model
+    N, J = C.nSubj, C.nItem
+    if np.ndim(P.ra) != 3:
+        raise ValueError("getWaicHost needs the full Post traces (trace='full' and fill=True)")
+    Y = np.asarray(D.Y, dtype=np.float64)
+    logT = None if m == _lib.MODEL_MLIRT else np.asarray(D.logT, dtype=np.float64)
+    q = C.qRt
+    k1, k2 = ((1 - 2 * q) / (q * (1 - q)), 2 / (q * (1 - q))) if m == _lib.MODEL_CROSSQR else (0.0, 1.0)
+    if m == _lib.MODEL_CROSSQR and P.qr.shape[1] != J + 4 + N * J:
+        raise ValueError("getWaicHost needs the per-sweep nu trace of GibbsRtIrtCrossQr in Post.qr")
+    rows = [(it, l) for it in range(C.nBurnin, C.nIter) for l in range(C.nChain)]
+    out = np.empty((len(rows), N * J if unit == "cell" else N))
+    for s, (it, l) in enumerate(rows):
+        ra = P.ra[it, :, l]
+        th, a, b = ra[:N], ra[N:N + J], ra[N + J:N + 2 * J]
+        eta = a[None, :] * (th[:, None] - b[None, :])
+        ll = Y * eta - _log1pexp(eta)
+        if m != _lib.MODEL_MLIRT:
+            rt = P.rt[it, :, l]
+            ze, lam, sg = rt[:N], rt[N:N + J], rt[N + J:N + 2 * J]
+            mu = lam[None, :] - ze[:, None]
+            var = np.broadcast_to(sg[None, :], (N, J))
+            if m in (_lib.MODEL_CROSS, _lib.MODEL_CROSSQR):
+                qr = P.qr[it, :, l]
+                mu = mu - th[:, None] * qr[None, :J]
+                if m == _lib.MODEL_CROSSQR:
+                    nu = qr[J + 4:].reshape(N, J, order="F")
+                    mu = mu + k1 * nu
+                    var = sg[None, :] * (k2 * nu)
+            ll = ll + _norm_logpdf(logT, mu, np.sqrt(var))
+        out[s] = ll.reshape(-1, order="F") if unit == "cell" else ll.sum(axis=1)
+    return out
+
+
+def getWaicHost(MCMC: _GibbsBase, unit) -> OutputWaic:
+    """getWaic evaluated with numpy on the host (the test twin of the device path): scipy's logsumexp and np.var(ddof=1) over pointwiseLogLikHost's rows."""
+    from scipy.special import logsumexp
+    L = pointwiseLogLikHost(MCMC, unit)
+    S, U = L.shape
+    if S < 2:
+        raise ValueError("WAIC needs at least two post-burn-in rows")
+    lppd_u = logsumexp(L, axis=0) - np.log(S)
+    p_u = np.var(L, axis=0, ddof=1)
+    el = lppd_u - p_u
+    elpd = float(np.sum(el))
+    se = 2.0 * float(np.sqrt(U * np.var(el, ddof=1))) if U > 1 else 0.0
+    if unit == "cell":
+        sh = (MCMC.Cond.nSubj, MCMC.Cond.nItem)
+        lppd_u, p_u = lppd_u.reshape(sh, order="F"), p_u.reshape(sh, order="F")
+    return OutputWaic(elpd=elpd, pWaic=float(np.sum(p_u)), WAIC=-2.0 * elpd, se=se, nHighVar=int(np.sum(p_u > 0.4)), lppd=float(np.sum(lppd_u)), unit=unit, nUnits=U,
+                      nRows=S, lppd_u=lppd_u, p_u=p_u)
+
+
+def compareWaic(A, B) -> dict:
+    """Two fits of the SAME data compared unit by unit: elpd_diff = sum_u (elpd_u^A - elpd_u^B) (positive: A predicts better) and its standard error
+    se_diff = sqrt(U Var_u(elpd_u^A - elpd_u^B)).  A, B: samplers (getWaic(pointwise=True) is called) or OutputWaic objects that carry the pointwise vectors."""
+    wa = A if isinstance(A, OutputWaic) else getWaic(A, pointwise=True)
+    wb = B if isinstance(B, OutputWaic) else getWaic(B, pointwise=True)
+    if wa.lppd_u is None or wb.lppd_u is None:
+        raise ValueError("compareWaic needs the pointwise values (getWaic(..., pointwise=True))")
+    if wa.unit != wb.unit:
+        raise ValueError(f"compareWaic: the fits use different units ({wa.unit!r} and {wb.unit!r})")
+    if np.shape(wa.lppd_u) != np.shape(wb.lppd_u):
+        raise ValueError(f"compareWaic: the fits have different numbers of units ({np.size(wa.lppd_u)} and {np.size(wb.lppd_u)})")
+    d = np.ravel(wa.elpd_u) - np.ravel(wb.elpd_u)
+    U = d.size
+    return dict(elpd_diff=float(np.sum(d)), se_diff=float(np.sqrt(U * np.var(d, ddof=1))) if U > 1 else 0.0, unit=wa.unit, nUnits=U)
 
 
 def ess_rhat(x: np.ndarray):

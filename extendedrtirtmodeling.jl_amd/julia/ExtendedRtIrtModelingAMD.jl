@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, setPointwise!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -202,22 +202,25 @@ function sampleFarm!(M::GibbsAMD, intercept::Bool, onepl::Bool, cov2one::Bool, d
 end
 
 """
-    sample!(MCMC; intercept=false, itemtype="2pl", cov2one, devices=nothing)
+    sample!(MCMC; intercept=false, itemtype="2pl", cov2one, devices=nothing, waic=:off)
 
 Same contract as the reference's `sample!`: runs `Cond.nIter * Cond.nChain` sweeps of the interleaved loop, fills
 `MCMC.Post.{ra,rt,qr,logLike,mean}`, leaves the final state in `MCMC.Para`, returns `MCMC`.
 `devices = 0:7` runs the `Cond.nChain` chains as independent chains, one per listed GPU (cycled), instead: `Post` has the same shapes,
 chain `l` in slab `l`; `Post.mean` is the joint mean over iterations and chains.
+`waic = :subject` or `:cell` also accumulates the pointwise log-likelihood on the device (`erm_set_pointwise`) for `getWaicDevice`; not with `devices`.
 """
 function sample!(M::GibbsAMD; intercept = false, itemtype::Union{String} = "2pl",
-                 cov2one = !(M isa GibbsRtIrtLatentQr || M isa GibbsRtIrtLatent), devices = nothing)
+                 cov2one = !(M isa GibbsRtIrtLatentQr || M isa GibbsRtIrtLatent), devices = nothing, waic::Symbol = :off)
     if !(itemtype in ["1pl", "2pl"])
         error("Invalid input: the item type must be '1pl' or '2pl'.")
     end
+    devices === nothing || waic == :off || error("WAIC is not available for a chain farm (devices)")
     devices === nothing || return sampleFarm!(M, Bool(intercept), itemtype == "1pl", Bool(cov2one), collect(devices))
     C = M.Cond
     h = engine!(M, intercept, itemtype == "1pl", cov2one)
     check(ccall((:erm_reset_trace, LIB[]), Cint, (Ptr{Cvoid},), h))
+    setPointwise!(M, waic)
     arrs = state_arrays(M.Para)
     GC.@preserve arrs begin
         st = ErmState(map(ptr, arrs)...)
@@ -285,6 +288,41 @@ function getDicDevice(M::GibbsAMD)
     out = zeros(4)
     check(ccall((:erm_get_dic, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.handle, out))
     return (Dbar = out[1], Dhat = out[2], pD = out[3], DIC = out[4])
+end
+
+"""
+    getWaicDevice(MCMC; pointwise = false) -> (elpd, pWaic, WAIC, se, lppd, nUnits, nRows, nHighVar[, lppd_u, p_u])
+
+WAIC from the accumulators the engine keeps on the device (`erm_get_waic`; the reference offers DIC only).  Enable it before the run, while no trace row is
+recorded: `setPointwise!(MCMC, :subject)` or `:cell` (`erm_set_pointwise`), then `sample!`.  The unit's log-likelihood is the data term of `getLogLikelihood*`
+at each post-burn-in row (the conditional WAIC: the structural term is not part of it).  `pointwise = true` also fetches lppd_u and p_u
+(`erm_get_pointwise`; subjects in order, cells as an nSubj x nItem matrix).
+"""
+function getWaicDevice(M::GibbsAMD; pointwise::Bool = false)
+    M.handle == C_NULL && error("run sample! first")
+    out = zeros(8)
+    check(ccall((:erm_get_waic, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.handle, out))
+    res = (elpd = out[1], pWaic = out[2], WAIC = out[3], se = out[4], lppd = out[5], nUnits = Int(out[6]), nRows = Int(out[7]), nHighVar = Int(out[8]))
+    pointwise || return res
+    U = ccall((:erm_pointwise_units, LIB[]), Int64, (Ptr{Cvoid},), M.handle)
+    lppd_u, p_u = zeros(U), zeros(U)
+    check(ccall((:erm_get_pointwise, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), M.handle, lppd_u, p_u))
+    if U == M.Cond.nSubj * M.Cond.nItem && M.Cond.nItem > 1
+        lppd_u, p_u = reshape(lppd_u, M.Cond.nSubj, M.Cond.nItem), reshape(p_u, M.Cond.nSubj, M.Cond.nItem)
+    end
+    return merge(res, (lppd_u = lppd_u, p_u = p_u))
+end
+
+"""
+    setPointwise!(MCMC, unit)   # unit = :off | :subject | :cell
+
+`erm_set_pointwise`: allowed only while no trace row is recorded (a fresh engine or after the trace was reset).
+"""
+function setPointwise!(M::GibbsAMD, unit::Symbol)
+    M.handle == C_NULL && error("the engine does not exist yet")
+    code = unit == :off ? 0 : unit == :subject ? 1 : unit == :cell ? 2 : error("unit must be :off, :subject or :cell")
+    check(ccall((:erm_set_pointwise, LIB[]), Cint, (Ptr{Cvoid}, Cint), M.handle, code))
+    return M
 end
 
 """

@@ -161,6 +161,27 @@ int erm_get_convergence(erm_handle h, int which, int64_t* counts4);
  * the boundary), pD = Dbar - Dhat, DIC = Dbar + pD.  Needs a run with post-burn-in rows. */
 int erm_get_dic(erm_handle h, double* out4);
 
+/* WAIC (Watanabe 2010; Vehtari, Gelman and Gabry 2017), accumulated on the device sweep by sweep.  The reference offers DIC only.  A unit u is a subject or a
+ * cell (i, j); l_u^(s) is the unit's part of the model's own getLogLikelihood* at the values of trace row s: per cell y eta - log(1 + e^eta), eta = a_j (theta_i - b_j),
+ * plus -- for every model but GibbsMlIrt -- the normal log-density of logT_ij (mean lambda_j - zeta_i [- theta_i rho_j + k1 nu_ij], variance sig2t_j [k2 nu_ij]; brackets:
+ * Cross family); a subject's is the sum of its cells.  The structural term (theta, zeta given beta, Sigma_p) is NOT part of it: this is the conditional WAIC,
+ * leave-one-unit-out given the subject's own parameters.  S = the post-burn-in rows, exactly those behind Post.mean (|S| = erm_post_count):
+ *   lppd_u = log mean_S exp l_u,  p_u = Var_S(l_u) (|S| - 1 in the denominator),  elpd_u = lppd_u - p_u,
+ *   elpd = sum_u elpd_u,  p_waic = sum_u p_u,  waic = -2 elpd,  se_waic = 2 sqrt(U Var_u(elpd_u)).
+ * erm_set_pointwise enables it (four doubles of device memory per unit; GibbsRtIrtCrossQr also keeps a copy of nu_t, nSubj * nItem values, taken ahead of the pass
+ * that overwrites it) and is allowed only while no trace row is recorded (after erm_create or erm_reset_trace; ERM_ERR_STATE otherwise).  Unknown unit: ERM_ERR_ARG;
+ * a subject-sharded engine: ERM_ERR_STATE; no memory for the accumulators: ERM_ERR_NOMEM, the engine stays as it was.  From then on every sweep is followed by one
+ * streaming pass over the resident data set (on the stream and inside the captured graphs; burn-in rows return at once), and small data sets are run one launch per
+ * sweep at the persistent schedule's geometry, as under ERM_FLAG_NO_PERSIST (erm_timing.persistent = 0): the chain itself is bit for bit the chain without WAIC.
+ * In profile mode the event bracket of a timed sweep also holds the pointwise pass.  erm_reset_trace clears the accumulators.  The chain farm has no WAIC yet.
+ * erm_get_waic: out = { elpd, p_waic, waic, se_waic, lppd, n_units, n_rows, number of units with p_u > 0.4 }, finished and summed on the device (needs two
+ * post-burn-in rows).  erm_get_pointwise: lppd_u / p_u of every unit (either may be NULL): subjects in order, cells column-major [nSubj][nItem]. */
+enum { ERM_POINTWISE_OFF = 0, ERM_POINTWISE_SUBJECT = 1, ERM_POINTWISE_CELL = 2 };
+int erm_set_pointwise(erm_handle h, int unit);
+int erm_get_waic(erm_handle h, double* out_eight);
+int64_t erm_pointwise_units(erm_handle h);
+int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u);
+
 int erm_get_timing(erm_handle h, erm_timing* out);
 /* Subject sharding of ONE chain over several devices (second bullet).  The reference has no counterpart: its
  * conditionals (src/Draw.pl.jl:36-606) make subjects independent given the item / structural parameters, so each device keeps
