@@ -27,6 +27,7 @@ EXPORTS = [
     "erm_farm_run", "erm_farm_reset_trace", "erm_farm_get_trace", "erm_farm_get_mean", "erm_farm_post_count", "erm_farm_used_rccl", "erm_farm_get_timing",
     "erm_get_dic", "erm_set_seed", "erm_farm_get_dic", "erm_farm_set_seed", "erm_abi_version", "erm_debug_invwishart", "erm_get_convergence",
     "erm_set_pointwise", "erm_get_waic", "erm_pointwise_units", "erm_get_pointwise",
+    "erm_set_predictive", "erm_predictive_reps", "erm_get_predictive",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -146,6 +147,10 @@ def load():
     lib.erm_pointwise_units.argtypes = [H]
     lib.erm_pointwise_units.restype = C.c_int64
     lib.erm_get_pointwise.argtypes = [H, C.c_void_p, C.c_void_p]
+    lib.erm_set_predictive.argtypes = [H, C.c_int, C.c_int32]
+    lib.erm_predictive_reps.argtypes = [H]
+    lib.erm_predictive_reps.restype = C.c_int64
+    lib.erm_get_predictive.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erm_set_seed.argtypes = [H, C.c_uint64]
     lib.erm_farm_get_dic.argtypes = [H, C.c_void_p]
     lib.erm_farm_set_seed.argtypes = [H, C.c_uint64]
@@ -335,6 +340,22 @@ class Engine:
             sh = (self.cfg.n_subj, self.cfg.n_item)
             return lppd.reshape(sh, order="F"), p.reshape(sh, order="F")
         return lppd, p
+
+    # ---- posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
+    def set_predictive(self, on=True, thin=1):
+        """Enable the replicate pass (every thin-th post-burn-in row is replicated) or turn it off; only while no trace row is recorded."""
+        check(self._lib.erm_set_predictive(self._h, int(bool(on)), int(thin)))
+
+    @property
+    def predictive_reps(self):
+        return int(self._lib.erm_predictive_reps(self._h))
+
+    def predictive(self):
+        """erm_get_predictive: (item (3, 4, nItem), subj (2, 4, nSubj), total (2, 4)); components RA, RT[, SCORE] x {n_ge, n_gt, mean_obs, mean_rep}."""
+        N, J = self.cfg.n_subj, self.cfg.n_item
+        item, subj, total = np.empty((3, 4, J)), np.empty((2, 4, N)), np.empty((2, 4))
+        check(self._lib.erm_get_predictive(self._h, item.ctypes.data, subj.ctypes.data, total.ctypes.data))
+        return item, subj, total
 
     @property
     def rows_done(self):

@@ -115,3 +115,37 @@ class OutputWaic:
 
     def __repr__(self):
         return f"OutputWaic(unit={self.unit!r}, elpd={self.elpd}, pWaic={self.pWaic}, WAIC={self.WAIC}, se={self.se}, nHighVar={self.nHighVar})"
+
+
+class OutputPpc:
+    """Posterior predictive checks of a fit (getPpc / getPpcHost; the reference has no counterpart).  R = the number of replicated data sets; item (3, 4, nItem),
+    subj (2, 4, nSubj), total (2, 4): components RA (response deviance), RT (response-time chi^2; NaN for GibbsMlIrt)[, SCORE (item score)] x
+    {n_ge = #(rep >= obs), n_gt = #(rep > obs), mean of obs, mean of rep}.  ppp(...) = n_ge / R, ppp_mid(...) = (n_gt + (n_ge - n_gt) / 2) / R."""
+
+    COMPONENTS = {"ra": 0, "rt": 1, "score": 2}
+
+    def __init__(self, R=None, thin=None, item=None, subj=None, total=None):
+        self.R, self.thin, self.item, self.subj, self.total = R, thin, item, subj, total
+
+    def _pick(self, unit, comp):
+        a = {"item": self.item, "subject": self.subj, "total": self.total}[unit]
+        c = self.COMPONENTS[comp]
+        if c >= a.shape[0]:
+            raise ValueError("the item score is a test quantity of the items only")
+        return a[c]
+
+    def ppp(self, unit="item", comp="ra"):
+        return self._pick(unit, comp)[0] / self.R
+
+    def ppp_mid(self, unit="item", comp="ra"):
+        a = self._pick(unit, comp)
+        return (a[1] + 0.5 * (a[0] - a[1])) / self.R
+
+    def mean_obs(self, unit="item", comp="ra"):
+        return self._pick(unit, comp)[2]
+
+    def mean_rep(self, unit="item", comp="ra"):
+        return self._pick(unit, comp)[3]
+
+    def __repr__(self):
+        return f"OutputPpc(R={self.R}, thin={self.thin}, total ppp RA={self.ppp('total', 'ra')}, RT={self.ppp('total', 'rt')})"

@@ -18,6 +18,7 @@
 #include <vector>
 #include "ertirt.h"
 #include "erm_kernels.hpp"
+#include "erm_predictive_kernels.hpp"      // posterior predictive checks: the replicate pass behind every sweep
 #include "erm_geometry.hpp"
 #include "erm_schedule.hpp"
 
@@ -122,6 +123,10 @@ struct EngineBase {
     virtual int get_waic(double* out8) = 0;
     virtual int64_t pointwise_units() const = 0;
     virtual int get_pointwise(double* lppd_u, double* p_u) = 0;
+    // posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
+    virtual int set_predictive(int on, int32_t thin) = 0;
+    virtual int64_t predictive_reps() const = 0;
+    virtual int get_predictive(double* item, double* subj, double* total) = 0;
     virtual int set_seed(uint64_t) = 0;
     // DIC pieces for the chain farm: the log-likelihood at sum * inv (sum: a device vector in the summary layout) and the sum of the recorded logLike rows
     virtual int loglik_at(const double* dsum, double inv, double* ll) = 0;
@@ -211,6 +216,11 @@ template <typename real> struct Engine : EngineBase {
     // (taken ahead of pass B of every sweep, which overwrites nu_t with nu_{t+1}: N * J values of the engine's cell type)
     int pw_unit = PW_OFF;
     DevBuf dPwMs, dPwW, dNuSnap;
+    // posterior predictive checks (erm_set_predictive): every pred_thin-th post-burn-in row is a replicate row (0 = off); the accumulators of the subjects
+    // [N][PRED_SUBJ], of the items and the data set [J][PRED_ITEM] | [PRED_TOT] | replicate counter, and the workgroups' slab rows (erm_predictive_kernels.hpp)
+    int32_t pred_thin = 0;
+    DevBuf dPredSubj, dPredItem, dPredSlab;
+    bool aux_pass() const { return pw_unit != PW_OFF || pred_thin > 0; }      // a pass of its own follows every sweep
     bool persist_avail = false;                       // the persistent schedule as init() / erm_set_shard / a time-out left it: an engine with WAIC enabled plans
                                                       // per-sweep launches at the same geometry (as ERM_FLAG_NO_PERSIST does) and returns to it when WAIC is turned off
 
@@ -494,7 +504,7 @@ template <typename real> struct Engine : EngineBase {
         TinyArgs t{};
         if (timed) { if (int rc = bracket(false)) return rc; }
         hipLaunchKernelGGL((pass_kernel<MODEL, real, PHASE, false>), dim3(grid_blocks), dim3(block_threads), lds_pass[PHASE], stream, a, t);
-        if (pw) { if (int rc = launch_pointwise<MODEL>(cur)) return rc; }
+        if (pw) { if (int rc = launch_behind<MODEL>(cur)) return rc; }
         if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(PHASE, a.gslab);
         return 0;
@@ -528,6 +538,7 @@ template <typename real> struct Engine : EngineBase {
     int set_shard(int rank, int count, int64_t ntot, int64_t base, erm_exchange_fn fn, void* user, const void* rccl_id) override {
         if (has_data || rows_done > 0 || sharded()) return fail(ERM_ERR_STATE, "erm_set_shard must precede erm_set_data and be called once");
         if (pw_unit != PW_OFF) return fail(ERM_ERR_STATE, "an engine with WAIC enabled cannot become a shard (sharding: erm_set_pointwise)");
+        if (pred_thin > 0) return fail(ERM_ERR_STATE, "an engine with posterior predictive checks enabled cannot become a shard (sharding: erm_set_predictive)");
         if (count < 1 || rank < 0 || rank >= count) return fail(ERM_ERR_ARG, "bad shard rank / count");
         if (!fn && !rccl_id) return fail(ERM_ERR_ARG, "exchange callback / RCCL id is NULL");
         if (base < 0 || ntot < N || base + N > ntot) return fail(ERM_ERR_ARG, "local subjects must lie inside [0, n_subj_total)");
@@ -552,7 +563,7 @@ template <typename real> struct Engine : EngineBase {
         TinyArgs t = tiny_args(0, true);
         if (timed) { if (int rc = bracket(false)) return rc; }
         hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true>), dim3(grid_blocks), dim3(block_threads), fused_lds(), stream, a, t);
-        if (int rc = launch_pointwise<MODEL>(1 - cur)) return rc;      // the sweep published its parameter block and counters in buffer [1 - cur]
+        if (int rc = launch_behind<MODEL>(1 - cur)) return rc;      // the sweep published its parameter block and counters in buffer [1 - cur]
         if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(0, a.gslab);     // a.gslab: the group rows this launch wrote
         return 0;
@@ -595,8 +606,8 @@ template <typename real> struct Engine : EngineBase {
         if (int rc = launch_pass<MODEL, 0>(1, timed, !fam_cq(MODEL))) return rc;
         if constexpr (fam_cq(MODEL)) {
             if (int rc = launch_tiny<MODEL, 1>(0)) return rc;
-            // WAIC on GibbsRtIrtCrossQr: pass B overwrites nu_t with nu_{t+1} in the phase that uses it, so nu_t is copied first (a memcpy node inside a graph)
-            if (MODEL == CROSSQR && pw_unit != PW_OFF) HIPCHK(hipMemcpyAsync(dNuSnap.p, dNu.p, dNu.bytes, hipMemcpyDeviceToDevice, stream));
+            // WAIC / predictive checks on GibbsRtIrtCrossQr: pass B overwrites nu_t with nu_{t+1} in the phase that uses it, so nu_t is copied first (a memcpy node inside a graph)
+            if (MODEL == CROSSQR && aux_pass()) HIPCHK(hipMemcpyAsync(dNuSnap.p, dNu.p, dNu.bytes, hipMemcpyDeviceToDevice, stream));
             if (int rc = launch_pass<MODEL, 1>(1, timed, true)) return rc;
         }
         return 0;
@@ -627,9 +638,9 @@ template <typename real> struct Engine : EngineBase {
         }
         return 0;
     }
-    static int alloc_or_nomem(DevBuf& d, size_t n) {
+    static int alloc_or_nomem(DevBuf& d, size_t n, const char* what = "the WAIC accumulators") {
         void* q = nullptr;
-        if (hipMalloc(&q, n) != hipSuccess) { (void)hipGetLastError(); return fail(ERM_ERR_NOMEM, "out of device memory for the WAIC accumulators (" + std::to_string(n) + " bytes)"); }
+        if (hipMalloc(&q, n) != hipSuccess) { (void)hipGetLastError(); return fail(ERM_ERR_NOMEM, std::string("out of device memory for ") + what + " (" + std::to_string(n) + " bytes)"); }
         if (d.p) (void)hipFree(d.p);
         d.p = q; d.bytes = n;
         return 0;
@@ -653,11 +664,12 @@ template <typename real> struct Engine : EngineBase {
             if (ms.p) { std::swap(ms.p, dPwMs.p); std::swap(ms.bytes, dPwMs.bytes); std::swap(w.p, dPwW.p); std::swap(w.bytes, dPwW.bytes); }
             if (snap.p) { std::swap(snap.p, dNuSnap.p); std::swap(snap.bytes, dNuSnap.bytes); }
         } else {
-            (void)dPwMs.alloc(0); (void)dPwW.alloc(0); (void)dNuSnap.alloc(0);
+            (void)dPwMs.alloc(0); (void)dPwW.alloc(0);
+            if (pred_thin == 0) (void)dNuSnap.alloc(0);
         }
         if (unit != pw_unit) drop_graphs();          // the captured sweeps hold (or lack) the pointwise launch
         pw_unit = unit;
-        persist = unit == PW_OFF ? persist_avail : false;      // a persistent launch cannot interleave another kernel between its sweeps
+        persist = aux_pass() ? false : persist_avail;          // a persistent launch cannot interleave another kernel between its sweeps
         timing.persistent = persist ? 1 : 0;
         return pw_clear();
     }
@@ -715,6 +727,103 @@ template <typename real> struct Engine : EngineBase {
         };
         if (int rc = down(dL, lppd_u)) return rc;
         return down(dP, p_u);
+    }
+    // ---- posterior predictive checks: the replicate pass behind a sweep and the item / total step behind it (erm_predictive_kernels.hpp).  Like the WAIC pass
+    // the same two launches for every sweep (the kernels skip rows that are no replicate rows), inside the captured graphs; with both enabled, both run.
+    // The geometry is a function of (N, J) alone: the accumulators do not depend on the device, the sweep kernels' geometry or the schedule.
+    struct PredGeom { int logW, T, nb, nq; size_t lds; };
+    PredGeom pred_geom() const {
+        PredGeom g{};
+        while ((1 << g.logW) < 64 && (4 << g.logW) < J) ++g.logW;      // lanes per subject: as the WAIC subject unit
+        g.T = 256; g.nq = pred_nq(cfg.model);
+        while (g.T > 64 && pred_lds_bytes(cfg.model, J, g.T, g.logW) > (size_t)160 * 1024) g.T >>= 1;      // long tests: fewer subject slots (nItem 896: 128 threads, 115 KB)
+        g.lds = pred_lds_bytes(cfg.model, J, g.T, g.logW);
+        const int64_t R = g.T >> g.logW;
+        g.nb = (int)std::min<int64_t>((N + R - 1) / R, PRED_MAX_BLOCKS);
+        return g;
+    }
+    template <int MODEL> int launch_behind(int buf) {
+        if (int rc = launch_pointwise<MODEL>(buf)) return rc;
+        return launch_predictive<MODEL>(buf);
+    }
+    template <int MODEL> int launch_predictive(int buf) {
+        if (pred_thin == 0) return 0;
+        const PredGeom g = pred_geom();
+        PredArgs a{};
+        a.Y = dY.as<uint8_t>(); a.C = dC.p; a.nu = MODEL == CROSSQR ? dNuSnap.p : nullptr; a.theta = dTheta.p; a.zeta = dZeta.p;
+        a.par = dParB[buf].template as<double>(); a.cm = dCst.as<double>() + cst_off_m(J); a.ctl = dCtlB[buf].template as<Ctl>();
+        a.subj = dPredSubj.as<double>(); a.slab = dPredSlab.as<double>();
+        a.N = N; a.J = J; a.logW = g.logW; a.thin = (uint32_t)pred_thin;
+        const double q = cfg.q_rt;
+        a.k1 = m_nu() ? (1.0 - 2.0 * q) / (q * (1.0 - q)) : 0.0; a.k2 = m_nu() ? 2.0 / (q * (1.0 - q)) : 1.0;
+        a.seed = cfg.seed; a.chain = (uint32_t)cfg.chain_id; a.row_base = (uint32_t)row_base;
+        hipLaunchKernelGGL((predictive_kernel<MODEL, real>), dim3(g.nb), dim3(g.T), g.lds, stream, a);
+        PredItemArgs b{};
+        b.slab = dPredSlab.as<double>(); b.nb = g.nb; b.nq = g.nq; b.J = J; b.N = (double)N; b.k0 = dCst.as<double>() + cst_off_k0(J);
+        b.ctl = a.ctl; b.thin = a.thin; b.item = dPredItem.as<double>(); b.tot = dPredItem.as<double>() + (size_t)J * PRED_ITEM;
+        hipLaunchKernelGGL(predictive_items_kernel, dim3(1), dim3(PRED_IT_THREADS), 0, stream, b);
+        return 0;
+    }
+    int pred_clear() {
+        if (dPredSubj.p) { HIPCHK(hipMemsetAsync(dPredSubj.p, 0, dPredSubj.bytes, stream)); HIPCHK(hipMemsetAsync(dPredItem.p, 0, dPredItem.bytes, stream)); }
+        return 0;
+    }
+    int set_predictive(int on, int32_t thin) override {
+        if (on && thin < 1) return fail(ERM_ERR_ARG, "erm_set_predictive: thin must be at least 1");
+        if (rows_done > 0) return fail(ERM_ERR_STATE, "erm_set_predictive is allowed only while no trace row is recorded (after erm_create or erm_reset_trace)");
+        if (on && sharded()) return fail(ERM_ERR_STATE, "posterior predictive checks are not available under subject sharding (the accumulators of the shards would have to be merged across devices)");
+        HIPCHK(hipSetDevice(cfg.device));
+        HIPCHK(hipStreamSynchronize(stream));
+        const int32_t want = on ? thin : 0;
+        if (on) {
+            const PredGeom g = pred_geom();
+            if (int rc = dispatch([&](auto m) -> int {
+                    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&predictive_kernel<decltype(m)::value, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+                    return 0; })) return rc;
+            // the new buffers first: a failed allocation leaves the engine exactly as it was
+            DevBuf su, it, sl, snap;
+            if (!dPredSubj.p) {
+                if (int rc = alloc_or_nomem(su, (size_t)N * PRED_SUBJ * sizeof(double), "the predictive accumulators")) return rc;
+                if (int rc = alloc_or_nomem(it, ((size_t)J * PRED_ITEM + PRED_TOT + 1) * sizeof(double), "the predictive accumulators")) return rc;
+                if (int rc = alloc_or_nomem(sl, (size_t)g.nb * g.nq * J * sizeof(double), "the predictive slab")) return rc;
+            }
+            if (cfg.model == ERM_MODEL_CROSSQR && !dNuSnap.p) { if (int rc = alloc_or_nomem(snap, dNu.bytes, "the copy of nu")) return rc; }
+            if (su.p) { std::swap(su.p, dPredSubj.p); std::swap(su.bytes, dPredSubj.bytes); std::swap(it.p, dPredItem.p); std::swap(it.bytes, dPredItem.bytes); std::swap(sl.p, dPredSlab.p); std::swap(sl.bytes, dPredSlab.bytes); }
+            if (snap.p) { std::swap(snap.p, dNuSnap.p); std::swap(snap.bytes, dNuSnap.bytes); }
+        } else {
+            (void)dPredSubj.alloc(0); (void)dPredItem.alloc(0); (void)dPredSlab.alloc(0);
+            if (pw_unit == PW_OFF) (void)dNuSnap.alloc(0);
+        }
+        if (want != pred_thin) drop_graphs();        // the captured sweeps hold (or lack) the pass, and its thinning as a kernel argument
+        pred_thin = want;
+        persist = aux_pass() ? false : persist_avail;
+        timing.persistent = persist ? 1 : 0;
+        return pred_clear();
+    }
+    int64_t predictive_reps() const override { return pred_thin > 0 ? (post_rows + pred_thin - 1) / pred_thin : 0; }
+    int get_predictive(double* item, double* subj, double* total) override {
+        if (pred_thin == 0) return fail(ERM_ERR_STATE, "posterior predictive checks are not enabled on this engine (erm_set_predictive)");
+        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
+        const int64_t R = predictive_reps();
+        if (R < 1) return fail(ERM_ERR_STATE, "posterior predictive checks need at least one replicate row");
+        HIPCHK(hipSetDevice(cfg.device));
+        HIPCHK(hipStreamSynchronize(stream));
+        const double nan = std::nan("");
+        std::vector<double> it((size_t)J * PRED_ITEM + PRED_TOT + 1);
+        HIPCHK(hipMemcpy(it.data(), dPredItem.p, it.size() * sizeof(double), hipMemcpyDeviceToHost));
+        unsigned long long dev_reps = 0;
+        std::memcpy(&dev_reps, &it[(size_t)J * PRED_ITEM + PRED_TOT], sizeof(dev_reps));
+        if ((int64_t)dev_reps != R) return fail(ERM_ERR_STATE, "internal: the device counted " + std::to_string(dev_reps) + " replicate rows, the host " + std::to_string(R));
+        if (item) for (int c = 0; c < 3; ++c) for (int q = 0; q < 4; ++q) for (int j = 0; j < J; ++j)
+            item[((size_t)c * 4 + q) * J + j] = (c == 1 && !is_rt()) ? nan : it[(size_t)j * PRED_ITEM + c * 4 + q];
+        if (total) for (int c = 0; c < 2; ++c) for (int q = 0; q < 4; ++q) total[c * 4 + q] = (c == 1 && !is_rt()) ? nan : it[(size_t)J * PRED_ITEM + c * 4 + q];
+        if (subj) {
+            std::vector<double> su((size_t)N * PRED_SUBJ);
+            HIPCHK(hipMemcpy(su.data(), dPredSubj.p, su.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (int c = 0; c < 2; ++c) for (int q = 0; q < 4; ++q) for (int64_t i = 0; i < N; ++i)
+                subj[((size_t)c * 4 + q) * N + i] = (c == 1 && !is_rt()) ? nan : su[(size_t)i * PRED_SUBJ + c * 4 + q];
+        }
+        return 0;
     }
     void launch_run_begin() {
         hipLaunchKernelGGL(run_begin_kernel, dim3(1), dim3(256), 0, stream, dCtlB[0].template as<Ctl>(), dCtlB[1].template as<Ctl>(), host_run_dev, dGcnt.as<unsigned int>(), 2 * n_groups + 4);
@@ -961,7 +1070,8 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipMemsetAsync(dSumTheta.p, 0, dSumTheta.bytes, stream));
         HIPCHK(hipMemsetAsync(dSumZeta.p, 0, dSumZeta.bytes, stream));
         if (dSumNu.p) HIPCHK(hipMemsetAsync(dSumNu.p, 0, dSumNu.bytes, stream));
-        return pw_clear();
+        if (int rc = pw_clear()) return rc;
+        return pred_clear();
     }
 
     // -------------------------------------------------------------------------------------------- data
@@ -1580,7 +1690,7 @@ template <typename real> struct Engine : EngineBase {
         sweeps_total = 0;            // a new seed starts a new chain: its streams are addressed from sweep 1, as a freshly created engine's are
         drop_graphs();               // the captured launches carry the seed as a kernel argument
         stats_valid = false;         // the resident omega_{t+1} / nu_{t+1} were drawn from the old streams: the next run draws them again
-        return 0;
+        return pred_clear();         // the replicates of the old chain do not mix with the new one's
     }
     int summary_unpack(const double* mean, erm_state* out) const override {
         unpack_items(mean, out);
@@ -1719,6 +1829,9 @@ int erm_set_pointwise(erm_handle h, int unit) { CHK_H; return h->e->set_pointwis
 int erm_get_waic(erm_handle h, double* out_eight) { CHK_H; if (!out_eight) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_waic(out_eight); }
 int64_t erm_pointwise_units(erm_handle h) { return h ? h->e->pointwise_units() : -1; }
 int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u) { CHK_H; return h->e->get_pointwise(lppd_u, p_u); }
+int erm_set_predictive(erm_handle h, int on, int32_t thin) { CHK_H; return h->e->set_predictive(on, thin); }
+int64_t erm_predictive_reps(erm_handle h) { return h ? h->e->predictive_reps() : -1; }
+int erm_get_predictive(erm_handle h, double* item, double* subj, double* total) { CHK_H; return h->e->get_predictive(item, subj, total); }
 int erm_set_seed(erm_handle h, uint64_t seed) { CHK_H; return h->e->set_seed(seed); }
 int erm_get_timing(erm_handle h, erm_timing* out) { CHK_H; if (!out) return fail(ERM_ERR_ARG, "out is NULL"); *out = h->e->timing; return 0; }
 int erm_set_shard(erm_handle h, int rank, int count, int64_t n_subj_total, int64_t row_base, erm_exchange_fn exchange, void* user)

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import InputPara, OutputDic, OutputWaic, SimConditions
+from .base import InputPara, OutputDic, OutputPpc, OutputWaic, SimConditions
 
 _PREC = {"f32": _lib.PREC_F32, "f64": _lib.PREC_F64}
 _TRACE = {"summary": _lib.TRACE_SUMMARY, "full": _lib.TRACE_FULL}
@@ -270,7 +270,7 @@ def _sample_farm(MCMC: _GibbsBase, intercept, onepl, cov2one, devices):
     return MCMC
 
 
-def sample_b(MCMC: _GibbsBase, *, intercept=False, itemtype="2pl", cov2one=None, devices=None, fill=True, waic=None):
+def sample_b(MCMC: _GibbsBase, *, intercept=False, itemtype="2pl", cov2one=None, devices=None, fill=True, waic=None, ppc=None):
     """sample!(MCMC; intercept, itemtype, cov2one) -- src/GibbsRtIrt.pl.jl:210,278; Cross :265; Latent :271.
     Runs Cond.nIter * Cond.nChain sweeps (the reference's interleaved `for m in 1:nIter, l in 1:nChain` loop over ONE
     shared Para), fills MCMC.Post, leaves the final state in MCMC.Para and returns MCMC.
@@ -278,7 +278,14 @@ def sample_b(MCMC: _GibbsBase, *, intercept=False, itemtype="2pl", cov2one=None,
     fill = False leaves Post and Para untouched: traces, running means and the final state stay on the device, where getDic,
     checkConvergence and MCMC._engine.get_mean(which) read them (runSimulation's replications cross the boundary with summaries only).
     waic = "subject" | "cell": the engine also accumulates the pointwise log-likelihood of every subject / cell over the post-burn-in sweeps (erm_set_pointwise;
-    one more streaming pass per sweep, the chain itself is unchanged); getWaic reads it.  Not available with devices=."""
+    one more streaming pass per sweep, the chain itself is unchanged); getWaic reads it.  Not available with devices=.
+    ppc = True | thin (an int >= 1): the engine also replicates the data set at every thin-th post-burn-in sweep and accumulates the posterior predictive checks of every
+    item, subject and the whole fit (erm_set_predictive; the chain itself is unchanged); getPpc reads them.  Not available with devices=."""
+    if ppc is not None and ppc is not False and (isinstance(ppc, (bool, np.bool_)) is False and (not isinstance(ppc, (int, np.integer)) or ppc < 1)):
+        raise ValueError("ppc must be None, True or a thinning interval >= 1")
+    ppc_thin = 0 if ppc is None or ppc is False else int(ppc)      # True -> 1
+    if ppc_thin and (devices is not None or MCMC.shard is not None):
+        raise ValueError("posterior predictive checks are not available for a chain farm (devices=) or a subject-sharded sampler: the accumulators of several devices are not merged")
     if waic not in _lib.POINTWISE_UNITS:
         raise ValueError("waic must be None, 'subject' or 'cell'")
     if waic is not None and (devices is not None or MCMC.shard is not None):
@@ -299,6 +306,9 @@ def sample_b(MCMC: _GibbsBase, *, intercept=False, itemtype="2pl", cov2one=None,
     if waic is not None or eng.pointwise_units:
         eng.set_pointwise(waic)
     MCMC._waic_unit = waic
+    if ppc_thin or eng.predictive_reps or getattr(MCMC, "_ppc_thin", 0):
+        eng.set_predictive(ppc_thin > 0, max(ppc_thin, 1))
+    MCMC._ppc_thin = ppc_thin
     eng.set_state(**MCMC._state_for_engine())
     eng.run(MCMC.Cond.nIter * MCMC.Cond.nChain)
     if fill:
@@ -568,6 +578,130 @@ def compareWaic(A, B) -> dict:
     d = np.ravel(wa.elpd_u) - np.ravel(wb.elpd_u)
     U = d.size
     return dict(elpd_diff=float(np.sum(d)), se_diff=float(np.sqrt(U * np.var(d, ddof=1))) if U > 1 else 0.0, unit=wa.unit, nUnits=U)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Posterior predictive checks.  At every replicate row the data set is drawn again from the model at the values of that row; the deviance of the
+# responses, the chi^2 of the response times and the item scores of the replicate are compared with those of the data, per subject, per item and over the data set.
+# ------------------------------------------------------------------------------------------------------------------
+def getPpc(MCMC: _GibbsBase) -> OutputPpc:
+    """Posterior predictive checks of the last sample!(...; ppc=True | thin), from the accumulators the engine kept on the device (erm_get_predictive)."""
+    if getattr(MCMC, "farm", None) is not None:
+        raise ValueError("getPpc is not available for a sampler run through devices= (a chain farm keeps no predictive accumulators)")
+    eng, thin = MCMC._engine, getattr(MCMC, "_ppc_thin", 0)
+    if eng is None or not thin:
+        raise ValueError("run sample!(...; ppc=True) first (getPpc reads the engine's resident accumulators)")
+    item, subj, total = eng.predictive()
+    return OutputPpc(R=eng.predictive_reps, thin=thin, item=item, subj=subj, total=total)
+
+
+_PPC_SITE = 14          # the replicate draws' stream site (erm_predictive_kernels.hpp: SITE_PRED)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al. 2011) on broadcastable arrays of 32-bit counter and key words; returns the four output words as uint64 arrays < 2^32."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & m32 for c in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = np.uint64(int(k0) & 0xFFFFFFFF), np.uint64(int(k1) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0, c1, c2, c3
+
+
+def _ppc_uniform(w):
+    return (w.astype(np.float64) + 0.5) * 2.0 ** -32
+
+
+def _ppc_normal(wa, wb):
+    return np.sqrt(-2.0 * np.log(_ppc_uniform(wa))) * np.cos(2.0 * np.pi * _ppc_uniform(wb))
+
+
+def _ppc_stream_word3(chain, site=_PPC_SITE, k=0):
+    return (site << 24) | ((chain & 0xFF) << 16) | k
+
+
+def getPpcHost(MCMC: _GibbsBase, thin=1, sweep0=1, *, seed=None, chain=None, row_base=0) -> OutputPpc:
+    """getPpc evaluated with numpy on the host from MCMC.Data and the full Post traces (the test twin of the device path): the same replicate draws -- one
+    Philox4x32-10 block per cell at (site 14, subject, item, sweep, chain) -- and the same discrepancies.  sweep0: the global sweep index of trace row 0 (1 on a
+    fresh engine or after setSeed; it goes on counting over erm_reset_trace).  The result also carries `margin`: per unit and component the smallest non-zero
+    |D_rep - D_obs| over the replicate rows relative to the magnitudes compared (a count is decided beyond rounding when its margin is far above 1e-16)."""
+    C, D, P, m = MCMC.Cond, MCMC.Data, MCMC.Post, MCMC._model
+    N, J = C.nSubj, C.nItem
+    if thin < 1:
+        raise ValueError("thin must be at least 1")
+    if np.ndim(P.ra) != 3:
+        raise ValueError("getPpcHost needs the full Post traces (trace='full' and fill=True)")
+    seed = int(MCMC.seed if seed is None else seed)
+    chain = int(getattr(MCMC, "chain_id", 0) if chain is None else chain)
+    Y = np.asarray(D.Y, dtype=np.float64)
+    rt_model = m != _lib.MODEL_MLIRT
+    logT = np.asarray(D.logT, dtype=np.float64) if rt_model else None
+    q = C.qRt
+    k1, k2 = ((1 - 2 * q) / (q * (1 - q)), 2 / (q * (1 - q))) if m == _lib.MODEL_CROSSQR else (0.0, 1.0)
+    if m == _lib.MODEL_CROSSQR and P.qr.shape[1] != J + 4 + N * J:
+        raise ValueError("getPpcHost needs the per-sweep nu trace of GibbsRtIrtCrossQr in Post.qr")
+    ii, jj = np.arange(N, dtype=np.uint64)[:, None] + np.uint64(row_base), np.arange(J, dtype=np.uint64)[None, :]
+    item, subj, total = np.zeros((3, 4, J)), np.zeros((2, 4, N)), np.zeros((2, 4))
+    margin = dict(item=np.full((3, J), np.inf), subject=np.full((2, N), np.inf), total=np.full(2, np.inf))
+    if not rt_model:
+        item[1], subj[1], total[1] = np.nan, np.nan, np.nan
+
+    def update(acc, mar, obs, rep, diff, scale):
+        acc[0] += diff >= 0
+        acc[1] += diff > 0
+        acc[2] += obs
+        acc[3] += rep
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel = np.where(diff != 0, np.abs(diff) / scale, np.inf)
+        np.minimum(mar, rel, out=mar)
+
+    R = 0
+    post = [(it, l) for it in range(C.nBurnin, C.nIter) for l in range(C.nChain)]
+    for k, (it, l) in enumerate(post):
+        if k % thin:
+            continue
+        R += 1
+        sweep = sweep0 + it * C.nChain + l
+        ra = P.ra[it, :, l]
+        th, a, b = ra[:N], ra[N:N + J], ra[N + J:N + 2 * J]
+        eta = a[None, :] * (th[:, None] - b[None, :])
+        with np.errstate(over="ignore"):
+            p = 1.0 / (1.0 + np.exp(-eta))
+        w0, w1, w2, _ = _philox4x32_10(ii, jj, sweep, _ppc_stream_word3(chain), seed, seed >> 32)
+        yrep = (_ppc_uniform(w0) < p).astype(np.float64)
+        lobs = Y * eta - _log1pexp(eta)
+        dcell = (Y - yrep) * eta                        # l(y) - l(y_rep): D_rep - D_obs = 2 sum dcell
+        for ax, acc, mar in ((1, subj, margin["subject"]), (0, item, margin["item"]), (None, total, margin["total"])):
+            dobs, dlt = -2.0 * lobs.sum(axis=ax), dcell.sum(axis=ax)
+            update(acc[0], mar[0] if ax is not None else mar[0:1], dobs, dobs + 2.0 * dlt, dlt, np.abs(dcell).sum(axis=ax))
+        tobs, trep = Y.sum(axis=0), yrep.sum(axis=0)
+        update(item[2], margin["item"][2], tobs, trep, trep - tobs, 1.0)
+        if rt_model:
+            rt = P.rt[it, :, l]
+            ze, lam, sg = rt[:N], rt[N:N + J], rt[N + J:N + 2 * J]
+            mu = lam[None, :] - ze[:, None]
+            var = np.broadcast_to(sg[None, :], (N, J))
+            if m in (_lib.MODEL_CROSS, _lib.MODEL_CROSSQR):
+                qr = P.qr[it, :, l]
+                mu = mu - th[:, None] * qr[None, :J]
+                if m == _lib.MODEL_CROSSQR:
+                    nu = qr[J + 4:].reshape(N, J, order="F")
+                    mu = mu + k1 * nu
+                    var = sg[None, :] * (k2 * nu)
+            z = _ppc_normal(w1, w2)                     # logT_rep = mu + sqrt(var) z: its standardised square is z^2
+            cobs, crep = (logT - mu) ** 2 / var, z * z
+            for ax, acc, mar in ((1, subj, margin["subject"]), (0, item, margin["item"]), (None, total, margin["total"])):
+                o, r_ = cobs.sum(axis=ax), crep.sum(axis=ax)
+                update(acc[1], mar[1] if ax is not None else mar[1:2], o, r_, r_ - o, o + r_)
+    if R == 0:
+        raise ValueError("posterior predictive checks need at least one replicate row")
+    for acc in (item, subj, total):
+        acc[:, 2:4] /= R
+    out = OutputPpc(R=R, thin=thin, item=item, subj=subj, total=total)
+    out.margin = margin
+    return out
 
 
 def ess_rhat(x: np.ndarray):

@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, setPointwise!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -202,25 +202,31 @@ function sampleFarm!(M::GibbsAMD, intercept::Bool, onepl::Bool, cov2one::Bool, d
 end
 
 """
-    sample!(MCMC; intercept=false, itemtype="2pl", cov2one, devices=nothing, waic=:off)
+    sample!(MCMC; intercept=false, itemtype="2pl", cov2one, devices=nothing, waic=:off, ppc=0)
 
 Same contract as the reference's `sample!`: runs `Cond.nIter * Cond.nChain` sweeps of the interleaved loop, fills
 `MCMC.Post.{ra,rt,qr,logLike,mean}`, leaves the final state in `MCMC.Para`, returns `MCMC`.
 `devices = 0:7` runs the `Cond.nChain` chains as independent chains, one per listed GPU (cycled), instead: `Post` has the same shapes,
 chain `l` in slab `l`; `Post.mean` is the joint mean over iterations and chains.
 `waic = :subject` or `:cell` also accumulates the pointwise log-likelihood on the device (`erm_set_pointwise`) for `getWaicDevice`; not with `devices`.
+`ppc = true` or a thinning interval `>= 1` also replicates the data set on the device at every `ppc`-th post-burn-in sweep (`erm_set_predictive`) for `getPpcDevice`;
+not with `devices`.
 """
 function sample!(M::GibbsAMD; intercept = false, itemtype::Union{String} = "2pl",
-                 cov2one = !(M isa GibbsRtIrtLatentQr || M isa GibbsRtIrtLatent), devices = nothing, waic::Symbol = :off)
+                 cov2one = !(M isa GibbsRtIrtLatentQr || M isa GibbsRtIrtLatent), devices = nothing, waic::Symbol = :off, ppc::Union{Bool, Integer} = 0)
     if !(itemtype in ["1pl", "2pl"])
         error("Invalid input: the item type must be '1pl' or '2pl'.")
     end
     devices === nothing || waic == :off || error("WAIC is not available for a chain farm (devices)")
+    thin = ppc === true ? 1 : Int(ppc)
+    thin >= 0 || error("ppc must be false, true or a thinning interval >= 1")
+    devices === nothing || thin == 0 || error("posterior predictive checks are not available for a chain farm (devices)")
     devices === nothing || return sampleFarm!(M, Bool(intercept), itemtype == "1pl", Bool(cov2one), collect(devices))
     C = M.Cond
     h = engine!(M, intercept, itemtype == "1pl", cov2one)
     check(ccall((:erm_reset_trace, LIB[]), Cint, (Ptr{Cvoid},), h))
     setPointwise!(M, waic)
+    setPredictive!(M, thin)
     arrs = state_arrays(M.Para)
     GC.@preserve arrs begin
         st = ErmState(map(ptr, arrs)...)
@@ -323,6 +329,33 @@ function setPointwise!(M::GibbsAMD, unit::Symbol)
     code = unit == :off ? 0 : unit == :subject ? 1 : unit == :cell ? 2 : error("unit must be :off, :subject or :cell")
     check(ccall((:erm_set_pointwise, LIB[]), Cint, (Ptr{Cvoid}, Cint), M.handle, code))
     return M
+end
+
+"""
+    setPredictive!(MCMC, thin)   # thin = 0: off; thin >= 1: every thin-th post-burn-in sweep is replicated
+
+`erm_set_predictive`: allowed only while no trace row is recorded (a fresh engine or after the trace was reset).
+"""
+function setPredictive!(M::GibbsAMD, thin::Integer)
+    M.handle == C_NULL && error("the engine does not exist yet")
+    check(ccall((:erm_set_predictive, LIB[]), Cint, (Ptr{Cvoid}, Cint, Int32), M.handle, thin > 0 ? 1 : 0, max(thin, 1)))
+    return M
+end
+
+"""
+    getPpcDevice(MCMC) -> (R, item, subj, total)
+
+Posterior predictive checks from the accumulators the engine keeps on the device (`erm_get_predictive`; the reference has no counterpart).  Enable them before
+the run: `sample!(MCMC; ppc = true)` (or `setPredictive!`).  `R` = the number of replicated data sets (`erm_predictive_reps`); `item` is nItem x 4 x 3, `subj`
+nSubj x 4 x 2, `total` 4 x 2: unit x {n_ge, n_gt, mean_obs, mean_rep} x component (RA: response deviance, RT: response-time chi^2 -- NaN for GibbsMlIrt --,
+SCORE: item score).  ppp = n_ge / R; mid-p = (n_gt + (n_ge - n_gt) / 2) / R.
+"""
+function getPpcDevice(M::GibbsAMD)
+    M.handle == C_NULL && error("run sample! first")
+    R = ccall((:erm_predictive_reps, LIB[]), Int64, (Ptr{Cvoid},), M.handle)
+    item, subj, total = zeros(M.Cond.nItem, 4, 3), zeros(M.Cond.nSubj, 4, 2), zeros(4, 2)      # column-major: the C layout [component][quantity][unit]
+    check(ccall((:erm_get_predictive, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), M.handle, item, subj, total))
+    return (R = Int(R), item = item, subj = subj, total = total)
 end
 
 """

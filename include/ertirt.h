@@ -182,6 +182,36 @@ int erm_get_waic(erm_handle h, double* out_eight);
 int64_t erm_pointwise_units(erm_handle h);
 int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u);
 
+/* Posterior predictive checks (Gelman, Meng and Stern 1996; Sinharay 2006; Glas and Meijer 2003; Marianti et al. 2014), drawn and accumulated on the device.  The
+ * reference has no counterpart.  Post-burn-in row number k = 1, 2, ... (the rows behind Post.mean) is a REPLICATE row when (k - 1) mod thin = 0.  At a replicate
+ * row the whole data set is drawn again from the model at the values of that row -- the law whose log-density is WAIC's cell term: y_rep ~ Bernoulli(p),
+ * p = 1 / (1 + e^-eta), eta = a_j (theta_i - b_j); logT_rep = mu + sqrt(var) z with WAIC's mean and variance, z standard normal -- from ONE Philox4x32-10 block per
+ * cell at stream (site 14, subject, item, sweep, chain): y_rep = [u(w0) < p], z = sqrt(-2 log u(w1)) cos(2 pi u(w2)), u(w) = (w + 1/2) 2^-32.  The draws depend on
+ * (seed, chain, subject, item, sweep) only.  Three discrepancies of the replicate are compared with the same discrepancies of the data:
+ *   RA     responses, the deviance:        D = -2 sum (y eta - log(1 + e^eta));  D_rep - D_obs = 2 sum (y - y_rep) eta, an exact zero when the replicate repeats the data
+ *   RT     response times, chi^2:          D_obs = sum (logT - mu)^2 / var,  D_rep = sum z^2                      (NaN for GibbsMlIrt)
+ *   SCORE  the item score (items only):    T_obs = sum_i y_ij,  T_rep = sum_i y_rep,ij
+ * for every subject (over its items), every item (over all subjects) and the data set.  Per unit and component four doubles, updated once per replicate row in trace
+ * order: { n_ge = #(rep >= obs), n_gt = #(rep > obs), mean of obs, mean of rep }; with R = erm_predictive_reps the posterior predictive p-value is n_ge / R and its
+ * mid-p form (n_gt + (n_ge - n_gt) / 2) / R (a person with few items often replicates its responses exactly: a tie).
+ * erm_set_predictive(h, on, thin) enables (on != 0; thin >= 1, else ERM_ERR_ARG) or disables it; 64 bytes of device memory per subject and 96 per item, a few MB
+ * of workgroup partial sums, and GibbsRtIrtCrossQr's copy of nu_t as for WAIC.  Like erm_set_pointwise it is allowed only while no trace row is recorded
+ * (ERM_ERR_STATE otherwise), refused on a subject-sharded engine (ERM_ERR_STATE), and ERM_ERR_NOMEM leaves the engine as it was.  From then on every sweep is followed
+ * by one streaming pass over the resident data set and a one-workgroup item step (on the stream and inside the captured graphs; rows that are no replicate rows
+ * return at once; with WAIC enabled too, both passes run), and small data sets are run one launch per sweep at the persistent schedule's geometry
+ * (erm_timing.persistent = 0): the chain itself is bit for bit the chain without it.  All sums are order-deterministic (no atomics) at a geometry that depends on
+ * (n_subj, n_item) only: the accumulators are bit-reproducible and do not depend on lanes_per_row / block_threads / grid_blocks, the schedule or how the sweeps
+ * are split into erm_run calls.  In profile mode the event bracket of a timed sweep also holds the pass.  erm_reset_trace and erm_set_seed clear the accumulators
+ * and the replicate count.  The chain farm has no predictive checks yet.
+ * erm_get_predictive (needs R >= 1, else ERM_ERR_STATE; any pointer may be NULL):
+ *   item  [3][4][n_item]   components RA, RT, SCORE x { n_ge, n_gt, mean_obs, mean_rep } x item
+ *   subj  [2][4][n_subj]   components RA, RT
+ *   total [2][4]           components RA, RT */
+enum { ERM_PPC_RA = 0, ERM_PPC_RT = 1, ERM_PPC_SCORE = 2 };
+int erm_set_predictive(erm_handle h, int on, int32_t thin);
+int64_t erm_predictive_reps(erm_handle h);
+int erm_get_predictive(erm_handle h, double* item, double* subj, double* total);
+
 int erm_get_timing(erm_handle h, erm_timing* out);
 /* Subject sharding of ONE chain over several devices (second bullet).  The reference has no counterpart: its
  * conditionals (src/Draw.pl.jl:36-606) make subjects independent given the item / structural parameters, so each device keeps
