@@ -25,7 +25,7 @@ EXPORTS = [
     "erm_set_shard", "erm_copy", "erm_rccl_unique_id", "erm_set_shard_rccl",
     "erm_farm_create", "erm_farm_destroy", "erm_farm_chains", "erm_farm_engine", "erm_farm_set_data", "erm_farm_set_state", "erm_farm_get_state",
     "erm_farm_run", "erm_farm_reset_trace", "erm_farm_get_trace", "erm_farm_get_mean", "erm_farm_post_count", "erm_farm_used_rccl", "erm_farm_get_timing",
-    "erm_get_dic", "erm_set_seed", "erm_farm_get_dic", "erm_farm_set_seed", "erm_abi_version", "erm_debug_invwishart", "erm_get_convergence",
+    "erm_get_dic", "erm_set_seed", "erm_farm_get_dic", "erm_farm_set_seed", "erm_abi_version", "erm_debug_invwishart", "erm_get_convergence", "erm_debug_convergence",
     "erm_set_pointwise", "erm_get_waic", "erm_pointwise_units", "erm_get_pointwise",
     "erm_set_predictive", "erm_predictive_reps", "erm_get_predictive",
 ]
@@ -142,6 +142,7 @@ def load():
     lib.erm_farm_get_timing.argtypes = [H, C.POINTER(erm_farm_timing), C.c_void_p]
     lib.erm_get_dic.argtypes = [H, C.c_void_p]
     lib.erm_get_convergence.argtypes = [H, C.c_int, C.c_void_p]
+    lib.erm_debug_convergence.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erm_set_pointwise.argtypes = [H, C.c_int]
     lib.erm_get_waic.argtypes = [H, C.c_void_p]
     lib.erm_pointwise_units.argtypes = [H]
@@ -548,6 +549,16 @@ def sample_gig(p, a, b, n, *, seed=1234, site=15, sweep=1, device=0):
     out = np.empty(int(n), dtype=np.float64)
     check(load().erm_sample_gig(device, seed, site, sweep, int(n), float(p), float(a), float(b), out.ctypes.data))
     return out
+
+
+def debug_convergence(ess, rhat, *, device=0):
+    """erm_debug_convergence: erm_get_convergence's four counts of caller-supplied ess / rhat vectors, counted by the same device code."""
+    e, r = np.ascontiguousarray(ess, dtype=np.float64), np.ascontiguousarray(rhat, dtype=np.float64)
+    if e.shape != r.shape or e.ndim != 1:
+        raise ValueError("ess and rhat must be vectors of one length")
+    c = np.zeros(4, dtype=np.int64)
+    check(load().erm_debug_convergence(device, e.size, e.ctypes.data, r.ctypes.data, c.ctypes.data))
+    return tuple(int(v) for v in c)
 
 
 def debug_invwishart(nu, psi, n, *, seed=1234, sweep=1, device=0):

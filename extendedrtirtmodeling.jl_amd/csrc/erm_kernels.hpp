@@ -2039,7 +2039,13 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_kernel(TinyArgs T)
 //   draws  => M = 2 nChain sequences.  W = mean of the sequences' variances (n-1 denominator), B/n = variance of their means,
 //   var+ = (n-1)/n W + B/n, rhat = sqrt(var+ / W), rho_t = 1 - (W - mean_c acov_c(t)) / var+ with acov_c(t) = 1/n sum_i (x_i - mu_c)
 //   (x_{i+t} - mu_c); P_k = rho_{2k} + rho_{2k+1} summed while positive and made non-increasing; ess = M n / (-1 + 2 sum_k P_k).
-// A parameter that never moves (beta[1] = 0, Sigma_p[1,1] = 1 ...) has W = 0 and gets NaN, as MCMCChains reports it.
+// A parameter that never moves (beta[1] = 0, Sigma_p[1,1] = 1 ...) gets NaN, as MCMCChains reports it.  "Never moves" means that every used draw (the 2 n
+// draws of every chain; an odd length leaves the middle one out) equals the first one: decided on the draws themselves, not by W > 0, because the rounded mean of n
+// copies of a non-dyadic constant is not that constant and leaves a W of rounding noise (gibbs.ess_rhat carries the same rule).  The sampler's constant columns hold 0
+// or 1, whose sums are exact, so on a device trace the two rules agree: the difference shows on host traces only.
+// The sum over k stops BEFORE the first P_k that is not positive, P_0 included: a column whose first pair sum is not positive gets -M n (sum = 0, so the denominator
+// is -1); x_i = (-1)^i is such a column.  More generally the value is negative whenever the pair sums add up to less than 1 / 2, which sampler traces with n = 4 .. 8
+// draws per sequence do show.  The estimator is left as it is; a caller that counts "ESS defined" counts such a column too.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int DIAG_MAXSEQ = 32;
 // Subject-sharded chains: a device's reduced statistics (the nb group rows of a pass) summed into ONE row, the unit the devices
@@ -2140,9 +2146,11 @@ __global__ void diag_kernel(const T* tr, long long ncol, long long ld, int nIter
     };
     double mu[DIAG_MAXSEQ];
     double W = 0.0, mbar = 0.0;
+    const double x0 = at(0, 0);
+    bool moves = false;                                          // some used draw differs from the first one
     for (int c = 0; c < M; ++c) {
         double s1 = 0.0;
-        for (int i = 0; i < n; ++i) s1 += at(c, i);
+        for (int i = 0; i < n; ++i) { const double x = at(c, i); moves = moves || (x != x0); s1 += x; }
         mu[c] = s1 / n; mbar += mu[c];
         double s2 = 0.0;
         for (int i = 0; i < n; ++i) { const double d = at(c, i) - mu[c]; s2 += d * d; }
@@ -2153,7 +2161,7 @@ __global__ void diag_kernel(const T* tr, long long ncol, long long ld, int nIter
     for (int c = 0; c < M; ++c) Bn += (mu[c] - mbar) * (mu[c] - mbar);
     Bn /= (M - 1);
     const double varp = W * (n - 1) / n + Bn;
-    if (!(W > 0.0)) { ess[k] = __builtin_nan(""); rhat[k] = __builtin_nan(""); return; }
+    if (!moves) { ess[k] = __builtin_nan(""); rhat[k] = __builtin_nan(""); return; }
     rhat[k] = sqrt(varp / W);
     auto rho = [&](int t) -> double {
         double a = 0.0;

@@ -100,6 +100,22 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// checkConvergence's four counts (diag_count_kernel, the reference's thresholds ESS > 400 and R-hat < 1.1) of n device-resident ess / rhat values: the one place
+// that launches the kernel, for erm_get_convergence and for erm_debug_convergence
+static int count_converged(const DevBuf& dE, const DevBuf& dR, int64_t n, hipStream_t stream, int64_t* c4)
+{
+    DevBuf dC;
+    if (int rc = dC.alloc(4 * sizeof(unsigned long long))) return rc;
+    hipLaunchKernelGGL(diag_count_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, stream, dE.as<double>(), dR.as<double>(), (long long)n, 400.0, 1.1,
+                       dC.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    unsigned long long h[4];
+    HIPCHK(hipMemcpy(h, dC.p, sizeof(h), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; ++k) c4[k] = (int64_t)h[k];
+    return 0;
+}
+
 // A persistent launch needs all its workgroups resident at once.  Two persistent launches of ONE process on one device (a farm's chains sharing a
 // device, several engines) could each hold some compute units and wait for the other's for ever: they take turns.
 std::mutex g_persist_mu[64];
@@ -1550,16 +1566,7 @@ template <typename real> struct Engine : EngineBase {
         DevBuf dE, dR, dC;
         bool nu_block = false;
         if (int rc = diag_device(which, dE, dR, &nu_block)) return rc;
-        if (int rc = dC.alloc(4 * sizeof(unsigned long long))) return rc;
-        const int64_t wd = trace_width(which);
-        hipLaunchKernelGGL(diag_count_kernel, dim3((unsigned)std::min<int64_t>((wd + 255) / 256, 1024)), dim3(256), 0, stream, dE.as<double>(), dR.as<double>(), (long long)wd, 400.0, 1.1,
-                           dC.as<unsigned long long>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
-        unsigned long long h[4];
-        HIPCHK(hipMemcpy(h, dC.p, sizeof(h), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 4; ++k) c4[k] = (int64_t)h[k];
-        return 0;
+        return count_converged(dE, dR, trace_width(which), stream, c4);
     }
 
     // sums over the post-burn-in rows of the item-level trace columns (a, b, lambda, sig2t, small part of qr)
@@ -2072,6 +2079,18 @@ int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, d
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
+}
+
+int erm_debug_convergence(int device, int64_t n, const double* ess, const double* rhat, int64_t* counts4)
+{
+    if (n <= 0 || !ess || !rhat || !counts4) return fail(ERM_ERR_ARG, "bad n / ess / rhat / out");
+    HIPCHK(hipSetDevice(device));
+    DevBuf dE, dR;
+    if (int rc = dE.alloc((size_t)n * sizeof(double))) return rc;
+    if (int rc = dR.alloc((size_t)n * sizeof(double))) return rc;
+    H2D(dE.p, ess, (size_t)n * sizeof(double));
+    H2D(dR.p, rhat, (size_t)n * sizeof(double));
+    return count_converged(dE, dR, n, nullptr, counts4);
 }
 
 int erm_debug_sample(int device, int precision, int which, uint64_t seed, uint32_t site, uint32_t sweep, int64_t n,

@@ -707,7 +707,9 @@ def getPpcHost(MCMC: _GibbsBase, thin=1, sweep0=1, *, seed=None, chain=None, row
 def ess_rhat(x: np.ndarray):
     """Split-R-hat and effective sample size (Geyer's initial monotone sequence over the split chains; BDA3 sec. 11.4-11.5, the
     non-rank-normalised estimator) of draws x[(iteration, chain)] -- the host twin of the device kernel `diag_kernel`, used by its
-    tests and for traces that are not resident on the device."""
+    tests and for traces that are not resident on the device.  A column that never moves -- every used draw (the first and last
+    floor(T / 2) of every chain) equal to the first one -- gets (nan, nan); a column whose first pair sum rho_0 + rho_1 is not positive gets
+    ess = -M n (M = 2 * chains sequences of n draws): the sum of pair sums stops before it (and pair sums that add up to less than 1 / 2 give a negative ess)."""
     x = np.asarray(x, dtype=np.float64)
     if x.ndim == 1:
         x = x[:, None]
@@ -715,13 +717,13 @@ def ess_rhat(x: np.ndarray):
     n = T // 2
     seq = np.stack([x[:n, l] if h == 0 else x[T - n:, l] for l in range(C) for h in (0, 1)])      # (M, n)
     M = seq.shape[0]
+    if not np.any(seq != seq[0, 0]):          # decided on the draws: the rounded mean of n copies of 0.1 is not 0.1, and W > 0 would be rounding noise
+        return float("nan"), float("nan")
     mu = seq.mean(axis=1)
     d = seq - mu[:, None]
     W = np.mean(np.sum(d * d, axis=1) / (n - 1))
     Bn = np.sum((mu - mu.mean()) ** 2) / (M - 1)
     varp = W * (n - 1) / n + Bn
-    if not W > 0:
-        return float("nan"), float("nan")
 
     def rho(t):
         return 1.0 - (W - np.mean(np.sum(d[:, :n - t] * d[:, t:], axis=1) / n)) / varp

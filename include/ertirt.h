@@ -149,7 +149,11 @@ int64_t erm_post_count(erm_handle h);   /* number of rows that entered the means
 /* checkConvergence's inputs (src/SimTools.jl:419-443, MCMCChains' ess_rhat on Post.ra / rt / qr after burn-in), computed on the device
  * from the resident traces: ess[k], rhat[k] for every column k of trace `which` (width erm_trace_width); split-R-hat and the effective
  * sample size by Geyer's initial monotone sequence over the 2*nChain split chains (the non-rank-normalised estimator); NaN for a column
- * that never moves.  Needs ERM_TRACE_FULL and a completed run. */
+ * that never moves: one whose used draws (the first and last floor((nIter - nBurnin) / 2) post-burn-in draws of every chain) are all equal -- decided on the draws,
+ * not on a variance computed from a rounded mean.  The sum of pair sums P_k = rho_2k + rho_2k+1 stops before the first one that is not positive: a column whose
+ * first pair sum is not positive gets -M n (M = 2*nChain sequences of n draws), a defined and negative ESS (and any column whose pair sums add up to less than
+ * 1/2 gets a negative one: seen on sampler traces with n = 4 .. 8, not with n >= 32).  Needs ERM_TRACE_FULL and a completed run with at least
+ * 8 post-burn-in iterations and at most 16 chains (ERM_ERR_ARG otherwise). */
 int erm_get_diagnostics(erm_handle h, int which, double* ess, double* rhat);
 /* checkConvergence's summary itself (src/SimTools.jl:427-437) without the N-wide vectors: counts4 = { columns with a defined ESS, of those ESS > 400, columns with a
  * defined R-hat, of those R-hat < 1.1 } for trace `which`, counted on the device. */
@@ -294,6 +298,11 @@ int erm_debug_sample(int device, int precision, int which, uint64_t seed, uint32
 /* n draws of the 2 x 2 InverseWishart(nu, Psi) of drawSubjCovariance (src/Draw.pl.jl:499-515) through the device code the structural step runs (Bartlett factor of
  * the Wishart on Psi^-1, then the inverse): out[4 k .. 4 k + 3] = vec(Sigma) of draw k, which uses stream (seed, site SIGP, i = k, sweep).  psi = vec(Psi). */
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out);
+
+/* checkConvergence's four counts of n caller-supplied ess / rhat values, through the device code erm_get_convergence runs on its own vectors (the same kernel, the
+ * same thresholds ESS > 400 and R-hat < 1.1, both strict; a NaN is "not defined" and enters no count): lets a test put values ON the thresholds, where a sampler's
+ * trace never lands.  counts4 as for erm_get_convergence. */
+int erm_debug_convergence(int device, int64_t n, const double* ess, const double* rhat, int64_t* counts4);
 
 /* n draws of the generalized inverse Gaussian GIG(p, a, b) (density ~ x^(p-1) exp(-(a x + b/x)/2); the distribution type of
  * src/GenInvGaussian.jl:17-30, whose sampler :76-106 is dead code in the reference) by Devroye's (2014) sampler, fp64; element k uses
