@@ -35,19 +35,16 @@ constexpr int PRED_MAX_BLOCKS = 1024;                      // slab rows at most
 constexpr int PRED_IT_THREADS = 1024, PRED_IT_PARTS = PRED_IT_THREADS / 64;
 
 __host__ __device__ constexpr int pred_nq(int model) { return model == MLIRT ? PRED_NQ_RA : PRED_NQ_RT; }
+// lanes per subject of the passes behind a sweep (this one and the WAIC subject unit), as log2: the smallest power of two <= 64 that leaves a lane at most four items
+constexpr int pass_log_lanes(int J) { int lw = 0; while ((1 << lw) < 64 && (4 << lw) < J) ++lw; return lw; }
 // dynamic LDS of predictive_kernel with T threads: a b lambda sig2t rho | column means [6][J], then T / W private item accumulators [NQ][J]
 inline size_t pred_lds_bytes(int model, int J, int T, int logW) { return ((size_t)6 * J + (size_t)(T >> logW) * pred_nq(model) * J) * sizeof(double); }
 
 struct PredArgs {
-    const uint8_t* Y; const void* C; const void* nu;      // resident data set (row-major [N][J]); nu: CrossQr's snapshot of nu_t, else nullptr
-    const void* theta; const void* zeta;                  // [N], the engine's cell type
-    const double* par;                                    // the parameter block of the sweep just drawn
-    const double* cm;                                     // column means of logT [J]
-    const Ctl* ctl;                                       // the counters that sweep published: sweep, row, burn_rows
+    CellArgs cell;                                        // erm_waic_kernels.hpp
     double* subj;                                         // [N][PRED_SUBJ]
     double* slab;                                         // [gridDim.x][NQ][J]
-    long long N; int J; int logW; uint32_t thin;
-    double k1, k2;
+    uint32_t thin;
     uint64_t seed; uint32_t chain; uint32_t row_base;
 };
 
@@ -61,38 +58,38 @@ __device__ __forceinline__ void pred_update(double2& cnt, double2& mean, double 
 template <int MODEL, typename real>
 __global__ void __launch_bounds__(256) predictive_kernel(const PredArgs A)
 {
-    const uint32_t row = A.ctl->row, burn = A.ctl->burn_rows;
+    const uint32_t row = A.cell.ctl->row, burn = A.cell.ctl->burn_rows;
     if (row < burn) return;                               // (uniform: every thread reads the same words)
     const uint32_t kpost = row - burn;                    // k - 1
     if (kpost % A.thin != 0u) return;
     const double rk = (double)(kpost / A.thin + 1u);      // this is replicate number rk
-    const uint32_t sweep = A.ctl->sweep;
+    const uint32_t sweep = A.cell.ctl->sweep;
     constexpr int NQ = pred_nq(MODEL);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* sa = reinterpret_cast<double*>(smem);         // a b lambda sig2t rho [5][J] | column means [J]
-    const int J = A.J, tid = (int)threadIdx.x, T = (int)blockDim.x;
-    const int W = 1 << A.logW, R = T >> A.logW;           // a workgroup takes R subjects at a time, W lanes each (W divides the wave)
+    const int J = A.cell.J, tid = (int)threadIdx.x, T = (int)blockDim.x;
+    const int W = 1 << A.cell.logW, R = T >> A.cell.logW;           // a workgroup takes R subjects at a time, W lanes each (W divides the wave)
     double* acc = sa + 6 * J;                             // [R][NQ][J]
-    for (int e = tid; e < 5 * J; e += T) sa[e] = A.par[e];
-    for (int j = tid; j < J; j += T) sa[5 * J + j] = (MODEL != MLIRT) ? A.cm[j] : 0.0;
+    for (int e = tid; e < 5 * J; e += T) sa[e] = A.cell.par[e];
+    for (int j = tid; j < J; j += T) sa[5 * J + j] = (MODEL != MLIRT) ? A.cell.cm[j] : 0.0;
     for (int e = tid; e < R * NQ * J; e += T) acc[e] = 0.0;
     __syncthreads();
-    const real* C = reinterpret_cast<const real*>(A.C);
-    const real* NU = reinterpret_cast<const real*>(A.nu);
-    const real* TH = reinterpret_cast<const real*>(A.theta);
-    const real* ZE = reinterpret_cast<const real*>(A.zeta);
-    const int s = tid & (W - 1), r = tid >> A.logW;
+    const real* C = reinterpret_cast<const real*>(A.cell.C);
+    const real* NU = reinterpret_cast<const real*>(A.cell.nu);
+    const real* TH = reinterpret_cast<const real*>(A.cell.theta);
+    const real* ZE = reinterpret_cast<const real*>(A.cell.zeta);
+    const int s = tid & (W - 1), r = tid >> A.cell.logW;
     double* my = acc + (size_t)r * NQ * J;
     const uint32_t k0 = (uint32_t)A.seed, k1 = (uint32_t)(A.seed >> 32), c3 = (SITE_PRED << 24) | ((A.chain & 0xFFu) << 16);
-    for (long long i0 = (long long)blockIdx.x * R; i0 < A.N; i0 += (long long)gridDim.x * R) {
-        const bool ok = i0 + r < A.N;
-        const long long i = ok ? i0 + r : A.N - 1;        // idle lanes repeat the last subject (every lane takes part in the butterfly) and add nothing to the items
+    for (long long i0 = (long long)blockIdx.x * R; i0 < A.cell.N; i0 += (long long)gridDim.x * R) {
+        const bool ok = i0 + r < A.cell.N;
+        const long long i = ok ? i0 + r : A.cell.N - 1;        // idle lanes repeat the last subject (every lane takes part in the butterfly) and add nothing to the items
         const double th = (double)TH[i], ze = (MODEL != MLIRT) ? (double)ZE[i] : 0.0;
         const size_t e0 = (size_t)i * J;
         const uint32_t ig = (uint32_t)i + A.row_base;
         double sd = 0.0, sl = 0.0, so = 0.0, sr = 0.0;
         for (int j = s; j < J; j += W) {                  // lane s: items s, s + W, ... in order
-            const bool y = A.Y[e0 + j] != 0;
+            const bool y = A.cell.Y[e0 + j] != 0;
             const double eta = sa[j] * (th - sa[J + j]);
             const double en = exp(-fabs(eta)), l1p = log1p(en);
             const double l = (y ? eta : 0.0) - (eta > 0.0 ? eta + l1p : l1p);
@@ -110,7 +107,7 @@ __global__ void __launch_bounds__(256) predictive_kernel(const PredArgs A)
                 double mu = sa[2 * J + j] - ze, var = sa[3 * J + j];
                 if constexpr (fam_cq(MODEL)) {
                     const double nu = (MODEL == CROSSQR) ? (double)NU[e0 + j] : 1.0;
-                    mu += -th * sa[4 * J + j] + A.k1 * nu; var *= A.k2 * nu;
+                    mu += -th * sa[4 * J + j] + A.cell.k1 * nu; var *= A.cell.k2 * nu;
                 }
                 const double er = lt - mu, c = fm::cos2pi(word_to_unif<double>(w2));
                 dobs = er * er / var;

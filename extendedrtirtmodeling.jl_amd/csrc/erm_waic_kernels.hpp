@@ -1,5 +1,6 @@
 // erm_waic_kernels.hpp -- WAIC on the device: the pointwise log-likelihood of every unit, accumulated once per post-burn-in sweep.
-// Included by erm_kernels.hpp (uses its Ctl, ll_log1pexp and the model families of erm_layout.hpp).
+// Included by erm_kernels.hpp (uses its Ctl, ll_log1pexp and the model families of erm_layout.hpp).  CellArgs, the head of this pass's kernel arguments, is shared
+// with the replicate pass (erm_predictive_kernels.hpp); the cell arithmetic of the two is not (ll_log1pexp here, exp(-|eta|) / log1p there, each pinned to its twin).
 //
 // pointwise_kernel<MODEL, real, UNIT> is ONE streaming pass over the resident data set, launched behind every sweep's own kernels (on the stream and inside
 // every captured graph): at that point theta_t, zeta_t, the item parameters of sweep t and the counters of trace row t are all resident.  It reads the
@@ -16,15 +17,20 @@
 
 namespace erm {
 
-struct PwArgs {
+// A resident cell as every pass behind a sweep reads it (this one and erm_predictive_kernels.hpp): filled in one place, Engine::cell_args
+struct CellArgs {
     const uint8_t* Y; const void* C; const void* nu;      // resident data set (row-major [N][J]); nu: CrossQr's snapshot of nu_t, else nullptr
     const void* theta; const void* zeta;                  // [N], the engine's cell type
     const double* par;                                    // the parameter block of the sweep just drawn
     const double* cm;                                     // column means of logT [J]
-    const Ctl* ctl;                                       // the counters that sweep published: row, burn_rows
-    double2* acc_ms; double2* acc_w;                      // [units]
-    long long N; int J; int logW;                         // subject unit: W = 2^logW lanes share a subject
+    const Ctl* ctl;                                       // the counters that sweep published: sweep, row, burn_rows
+    long long N; int J; int logW;                         // W = 2^logW lanes share a subject (pass_log_lanes, erm_predictive_kernels.hpp)
     double k1, k2;
+};
+
+struct PwArgs {
+    CellArgs cell;
+    double2* acc_ms; double2* acc_w;                      // [units]
 };
 
 template <int MODEL>
@@ -46,37 +52,37 @@ __device__ __forceinline__ double pw_cell(bool y, double th, double ze, double c
 template <int MODEL, typename real, int UNIT>
 __global__ void __launch_bounds__(256) pointwise_kernel(const PwArgs A)
 {
-    const uint32_t row = A.ctl->row, burn = A.ctl->burn_rows;
+    const uint32_t row = A.cell.ctl->row, burn = A.cell.ctl->burn_rows;
     if (row < burn) return;                               // burn-in rows do not enter S (uniform: every thread reads the same word)
     const long long k = (long long)(row - burn) + 1;      // this is the k-th post-burn-in row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* sa = reinterpret_cast<double*>(smem);         // a b lambda sig2t rho [5][J] | column means [J] | -1/2 (log 2 pi + log var_j) [J]
-    const int J = A.J, tid = (int)threadIdx.x;
-    for (int e = tid; e < 5 * J; e += 256) sa[e] = A.par[e];
+    const int J = A.cell.J, tid = (int)threadIdx.x;
+    for (int e = tid; e < 5 * J; e += 256) sa[e] = A.cell.par[e];
     for (int j = tid; j < J; j += 256) {
-        sa[5 * J + j] = (MODEL != MLIRT) ? A.cm[j] : 0.0;
-        double var = A.par[3 * J + j];
-        if (fam_cq(MODEL)) var *= A.k2;                   // GibbsRtIrtCross: k2 = 1, nu = 1
+        sa[5 * J + j] = (MODEL != MLIRT) ? A.cell.cm[j] : 0.0;
+        double var = A.cell.par[3 * J + j];
+        if (fam_cq(MODEL)) var *= A.cell.k2;                   // GibbsRtIrtCross: k2 = 1, nu = 1
         sa[6 * J + j] = (MODEL != MLIRT) ? -0.5 * LOG_2PI - 0.5 * log(var) : 0.0;
     }
     __syncthreads();
-    const real* C = reinterpret_cast<const real*>(A.C);
-    const real* NU = reinterpret_cast<const real*>(A.nu);
-    const real* TH = reinterpret_cast<const real*>(A.theta);
-    const real* ZE = reinterpret_cast<const real*>(A.zeta);
+    const real* C = reinterpret_cast<const real*>(A.cell.C);
+    const real* NU = reinterpret_cast<const real*>(A.cell.nu);
+    const real* TH = reinterpret_cast<const real*>(A.cell.theta);
+    const real* ZE = reinterpret_cast<const real*>(A.cell.zeta);
     if constexpr (UNIT == PW_SUBJECT) {
-        const int W = 1 << A.logW, R = 256 >> A.logW;     // a workgroup takes R subjects at a time, W lanes each (W divides the wave)
-        const int s = tid & (W - 1), r = tid >> A.logW;
-        for (long long i0 = (long long)blockIdx.x * R; i0 < A.N; i0 += (long long)gridDim.x * R) {
-            const bool ok = i0 + r < A.N;
-            const long long i = ok ? i0 + r : A.N - 1;    // idle lanes repeat the last subject: every lane takes part in the butterfly
+        const int W = 1 << A.cell.logW, R = 256 >> A.cell.logW;     // a workgroup takes R subjects at a time, W lanes each (W divides the wave)
+        const int s = tid & (W - 1), r = tid >> A.cell.logW;
+        for (long long i0 = (long long)blockIdx.x * R; i0 < A.cell.N; i0 += (long long)gridDim.x * R) {
+            const bool ok = i0 + r < A.cell.N;
+            const long long i = ok ? i0 + r : A.cell.N - 1;    // idle lanes repeat the last subject: every lane takes part in the butterfly
             const double th = (double)TH[i], ze = (MODEL != MLIRT) ? (double)ZE[i] : 0.0;
             const size_t e0 = (size_t)i * J;
             double t = 0.0;
             for (int j = s; j < J; j += W) {              // lane s: items s, s + W, ... in order
                 const double c = (MODEL != MLIRT) ? (double)C[e0 + j] : 0.0;
                 const double nu = (MODEL == CROSSQR) ? (double)NU[e0 + j] : 1.0;
-                t += pw_cell<MODEL>(A.Y[e0 + j] != 0, th, ze, c, nu, j, sa, J, A.k1, A.k2);
+                t += pw_cell<MODEL>(A.cell.Y[e0 + j] != 0, th, ze, c, nu, j, sa, J, A.cell.k1, A.cell.k2);
             }
             for (int m = 1; m < W; m <<= 1) t += __shfl_xor(t, m, 64);     // fixed-order butterfly over the subject's lanes
             if (ok && s == 0) {
@@ -87,14 +93,14 @@ __global__ void __launch_bounds__(256) pointwise_kernel(const PwArgs A)
             }
         }
     } else {
-        const long long NJ = A.N * (long long)J;
+        const long long NJ = A.cell.N * (long long)J;
         for (long long e = (long long)blockIdx.x * 256 + tid; e < NJ; e += (long long)gridDim.x * 256) {
             const long long i = e / J;
             const int j = (int)(e - i * J);
             const double th = (double)TH[i], ze = (MODEL != MLIRT) ? (double)ZE[i] : 0.0;
             const double c = (MODEL != MLIRT) ? (double)C[e] : 0.0;
             const double nu = (MODEL == CROSSQR) ? (double)NU[e] : 1.0;
-            const double l = pw_cell<MODEL>(A.Y[e] != 0, th, ze, c, nu, j, sa, J, A.k1, A.k2);
+            const double l = pw_cell<MODEL>(A.cell.Y[e] != 0, th, ze, c, nu, j, sa, J, A.cell.k1, A.cell.k2);
             const double2 ms = A.acc_ms[e], w = A.acc_w[e];
             PwAcc a{ms.x, ms.y, w.x, w.y};
             pw_update(a, l, k);

@@ -84,6 +84,9 @@ Rccl g_rccl;
 #define H2D(dst, src, n) do { HIPCHK(hipMemcpy((dst), (src), (n), hipMemcpyHostToDevice)); HIPCHK(hipStreamSynchronize(nullptr)); } while (0)
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }      // (o's destructor frees what this held)
     ~DevBuf() { if (p) (void)hipFree(p); }
     int alloc(size_t n) {
         if (p) { (void)hipFree(p); p = nullptr; }
@@ -95,6 +98,15 @@ struct DevBuf {
         // a farm chain whose data constants were off about once in 500 runs, with three host threads in erm_set_data at once.
         HIPCHK(hipMemset(p, 0, n));
         HIPCHK(hipStreamSynchronize(nullptr));
+        return 0;
+    }
+    // n bytes WITHOUT the zero fill, for a buffer that is staged and then moved into place: out of memory is ERM_ERR_NOMEM (the HIP error consumed), and what
+    // this held is released only once the new memory exists
+    int try_alloc(size_t n, const char* what) {
+        void* q = nullptr;
+        if (n > 0 && hipMalloc(&q, n) != hipSuccess) { (void)hipGetLastError(); return fail(ERM_ERR_NOMEM, std::string("out of device memory for ") + what + " (" + std::to_string(n) + " bytes)"); }
+        if (p) (void)hipFree(p);
+        p = q; bytes = n;
         return 0;
     }
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -200,10 +212,7 @@ template <typename real> struct Engine : EngineBase {
     int64_t N = 0; int J = 0, F = 0, Fk = 0;   // Fk = covariate columns the kernels see (0 for CrossQr)
     int64_t rows_cap = 0;
     bool has_data = false;
-    int W = 8, logW = 3, IPL = 1, block_threads = 1024, grid_blocks = 256;
-    int64_t rows_per_block = 0; int rows_per_wave = 0;
-    size_t lds_pass[2] = {0, 0};
-    int ns[2] = {0, 0};
+    Geom G;                                          // launch geometry and LDS layout: decided by plan_geometry (erm_geometry.hpp) and nowhere else, read in place
     uint32_t sweeps_total = 0;
 
     DevBuf dY, dC, dOmega, dNu, dX, dTheta, dZeta, dCst, dSlab0, dSlab1, dGslab1, dGcnt;
@@ -216,7 +225,6 @@ template <typename real> struct Engine : EngineBase {
     int persist_fault_countdown = 0;                 // ERM_FLAG_TEST_PERSIST_TIMEOUT: the engine's SECOND persistent erm_run loses a statistics row (the first leaves rows and sums for the restore to keep)
     uint32_t xtag = 0;                               // last packet tag handed out (tags only grow; the buffer is cleared before they wrap)
     int cur = 0;
-    int n_groups = 1;
     // subject sharding (erm_set_shard): this device holds subjects [row_base, row_base + N) of n_total
     int shard_rank = 0, shard_count = 1;
     int64_t n_total = 0, row_base = 0;
@@ -224,9 +232,10 @@ template <typename real> struct Engine : EngineBase {
     ncclComm_t comm = nullptr;                                       // ... or RCCL enqueued on the engine's stream
     DevBuf dShardSend, dShardRecv[2];
     bool sharded() const { return exch != nullptr || comm != nullptr; }
-    bool persist = false;                             // small data sets: ONE launch per erm_run (pass_kernel<..., PERSIST>: the statistics rows cross between its sweeps as tagged packets)
-    bool fuse_ok = true;                              // false when the fused kernel's LDS layout cannot fit (very long tests): two kernels per sweep then
-    bool fused() const { return !m_cq() && fuse_ok; }  // single-pass models run the tiny step inside the row-pass kernel
+    // small data sets: ONE launch per erm_run (pass_kernel<..., PERSIST>: the statistics rows cross between its sweeps as tagged packets).  Starts as G.persist and is
+    // the one geometry fact kept outside G: it changes after planning (the occupancy check, erm_set_shard, a pass behind the sweep, a time-out)
+    bool persist = false;
+    bool fused() const { return !m_cq() && G.fused; }  // single-pass models run the tiny step inside the row-pass kernel (G.fused is false when its LDS layout cannot fit: very long tests)
     DevBuf dSumTheta, dSumZeta, dSumNu, dTrTheta, dTrZeta, dTrNu, dTrItem, dTrLl;
     // WAIC (erm_set_pointwise): the unit, the accumulators {m, s}[units] and {mean, m2}[units] (erm_pointwise.hpp), GibbsRtIrtCrossQr's copy of nu_t
     // (taken ahead of pass B of every sweep, which overwrites nu_t with nu_{t+1}: N * J values of the engine's cell type)
@@ -237,8 +246,10 @@ template <typename real> struct Engine : EngineBase {
     int32_t pred_thin = 0;
     DevBuf dPredSubj, dPredItem, dPredSlab;
     bool aux_pass() const { return pw_unit != PW_OFF || pred_thin > 0; }      // a pass of its own follows every sweep
-    bool persist_avail = false;                       // the persistent schedule as init() / erm_set_shard / a time-out left it: an engine with WAIC enabled plans
-                                                      // per-sweep launches at the same geometry (as ERM_FLAG_NO_PERSIST does) and returns to it when WAIC is turned off
+    bool persist_avail = false;                       // the persistent schedule as init() / erm_set_shard / a time-out left it: an engine with a pass behind the sweep plans
+                                                      // per-sweep launches at the same geometry (as ERM_FLAG_NO_PERSIST does) and returns to it when the last pass is turned off
+    // the one place that decides `persist`: a persistent launch cannot interleave another kernel between its sweeps
+    void set_persist_avail(bool avail) { persist_avail = avail; persist = avail && !aux_pass(); timing.persistent = persist ? 1 : 0; }
 
     ~Engine() override {
         drop_graphs();
@@ -274,7 +285,6 @@ template <typename real> struct Engine : EngineBase {
         const int q = p() + 1;
         return q * (q + 1) / 2 + q + 1;
     }
-    Geom G;                                          // launch geometry and LDS layout: decided by plan_geometry (erm_geometry.hpp) and nowhere else
     DevBuf dPgTab;                                   // the Polya-Gamma proposal table [PG_NBIN][4] (erm_rng.hpp, pg_bin)
 
     int init() override {
@@ -319,10 +329,7 @@ template <typename real> struct Engine : EngineBase {
             gi.no_persist = true;                       // the stage-timing early exits would strand the other workgroups polling for a row that never comes
 #endif
             if (plan_geometry(gi, G, msg) != 0) return fail(ERM_ERR_ARG, msg);
-            persist = G.persist;
-            W = G.W; logW = G.logW; IPL = G.IPL; block_threads = G.block_threads; grid_blocks = G.grid_blocks; n_groups = G.n_groups;
-            rows_per_block = G.rows_per_block; rows_per_wave = G.rows_per_wave; fuse_ok = G.fused;
-            for (int ph = 0; ph < 2; ++ph) { lds_pass[ph] = G.lds_pass[ph]; ns[ph] = G.ns[ph]; }
+            set_persist_avail(G.persist);
         }
 
         // ---- device memory
@@ -339,16 +346,16 @@ template <typename real> struct Engine : EngineBase {
         rc |= dZeta.alloc((size_t)N * sizeof(real));
         for (int k = 0; k < 2; ++k) rc |= dParB[k].alloc((size_t)par_size(J) * sizeof(double));
         rc |= dCst.alloc((size_t)cst_size(J) * sizeof(double));
-        rc |= dSlab0.alloc((size_t)grid_blocks * ns[0] * sizeof(double));
+        rc |= dSlab0.alloc((size_t)G.grid_blocks * G.ns[0] * sizeof(double));
         // (at least GROUP rows, zero-filled: the fused head requests its first GROUP group rows unconditionally and masks those beyond n_groups)
-        for (int k = 0; k < 2; ++k) rc |= dGslab0B[k].alloc((size_t)std::max(n_groups, GROUP) * ns[0] * sizeof(double));
-        rc |= dGcnt.alloc(((size_t)2 * n_groups + 4) * sizeof(unsigned int));       // group tickets | a persistent launch's time-out flag, wait bound (ticks), test hook, pad
+        for (int k = 0; k < 2; ++k) rc |= dGslab0B[k].alloc((size_t)std::max(G.n_groups, GROUP) * G.ns[0] * sizeof(double));
+        rc |= dGcnt.alloc(((size_t)2 * G.n_groups + 4) * sizeof(unsigned int));       // group tickets | a persistent launch's time-out flag, wait bound (ticks), test hook, pad
         if (persist) {      // packet rows of the persistent launch's statistics exchange: [parity][workgroup][2 * ns] 64-bit packets, tags start at 1
-            rc |= dXbuf.alloc((size_t)2 * grid_blocks * 2 * ns[0] * sizeof(unsigned long long));
+            rc |= dXbuf.alloc((size_t)2 * G.grid_blocks * 2 * G.ns[0] * sizeof(unsigned long long));
             if (!rc) HIPCHK(hipMemset(dXbuf.p, 0, dXbuf.bytes));
         }
         if (persist) rc |= dSnap.alloc(snap_bytes());
-        if (m_cq()) { rc |= dSlab1.alloc((size_t)grid_blocks * ns[1] * sizeof(double)); rc |= dGslab1.alloc((size_t)std::max(n_groups, GROUP) * ns[1] * sizeof(double)); }      // >= GROUP rows: see dGslab0B
+        if (m_cq()) { rc |= dSlab1.alloc((size_t)G.grid_blocks * G.ns[1] * sizeof(double)); rc |= dGslab1.alloc((size_t)std::max(G.n_groups, GROUP) * G.ns[1] * sizeof(double)); }      // >= GROUP rows: see dGslab0B
         for (int k = 0; k < 2; ++k) rc |= dCtlB[k].alloc(sizeof(Ctl));
         rc |= dSumTheta.alloc((size_t)N * sizeof(double));
         rc |= dSumZeta.alloc((size_t)N * sizeof(double));
@@ -394,11 +401,9 @@ template <typename real> struct Engine : EngineBase {
             H2D(dPgTab.p, tab.data(), tab.size() * sizeof(double));
         }
         persist_fault_countdown = (cfg.flags & ERM_FLAG_TEST_PERSIST_TIMEOUT) ? 2 : 0;
-        timing.lanes_per_row = W; timing.block_threads = block_threads; timing.grid_blocks = grid_blocks;
-        timing.lds_bytes = (int32_t)std::max(lds_pass[0], lds_pass[1]); timing.cu_count = cu_count; timing.persistent = persist ? 1 : 0;
-        if (int rc = configure_kernels()) return rc;
-        persist_avail = persist;
-        return 0;
+        timing.lanes_per_row = G.W; timing.block_threads = G.block_threads; timing.grid_blocks = G.grid_blocks;
+        timing.lds_bytes = (int32_t)std::max(G.lds_pass[0], G.lds_pass[1]); timing.cu_count = cu_count;
+        return configure_kernels();
     }
 
     // -------------------------------------------------------------------------------------------- kernels
@@ -407,8 +412,6 @@ template <typename real> struct Engine : EngineBase {
         return 0;
     }
     // dynamic LDS limits of every kernel this engine launches; the planner's figure for the kernels' STATIC LDS is checked against the compiler's
-    size_t fused_lds() const { return G.lds_fused; }
-    size_t tiny_lds() const { return G.lds_tiny; }
     template <int MODEL, int PHASE, bool FUSED> int check_static_lds() {
         hipFuncAttributes fa;
         HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&pass_kernel<MODEL, real, PHASE, FUSED>)));
@@ -417,28 +420,28 @@ template <typename real> struct Engine : EngineBase {
         return 0;
     }
     int configure_kernels() {
-        const int tl = (int)tiny_lds();
+        const int tl = (int)G.lds_tiny;
         return dispatch([&](auto m) -> int {
             constexpr int M = decltype(m)::value;
             if (int rc = check_static_lds<M, 0, false>()) return rc;
-            if (int rc = set_lds_attr<M, 0, false>(lds_pass[0])) return rc;
+            if (int rc = set_lds_attr<M, 0, false>(G.lds_pass[0])) return rc;
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tiny_kernel<M, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, tl));
             if constexpr (!fam_cq(M)) {
-                if (fused()) { if (int rc = check_static_lds<M, 0, true>()) return rc; if (int rc = set_lds_attr<M, 0, true>(fused_lds())) return rc; }
+                if (fused()) { if (int rc = check_static_lds<M, 0, true>()) return rc; if (int rc = set_lds_attr<M, 0, true>(G.lds_fused)) return rc; }
                 if (persist) {
                     hipFuncAttributes fa;
                     HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&pass_kernel<M, real, 0, true, true>)));
                     if (fa.sharedSizeBytes > G.lds_static[0]) return fail(ERM_ERR_STATE, "internal: the persistent kernel's static LDS exceeds the planner's figure");
-                    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pass_kernel<M, real, 0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds()));
+                    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pass_kernel<M, real, 0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds_fused));
                     // every workgroup of a persistent launch must be resident at once: ask the runtime how many fit a compute unit with this block size and LDS
                     int per_cu = 0;
-                    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&pass_kernel<M, real, 0, true, true>), block_threads, fused_lds()));
-                    if ((long long)per_cu * cu_count < grid_blocks) { persist = false; timing.persistent = 0; }
+                    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&pass_kernel<M, real, 0, true, true>), G.block_threads, G.lds_fused));
+                    if ((long long)per_cu * cu_count < G.grid_blocks) set_persist_avail(false);
                 }
             }
             if constexpr (fam_cq(M)) {
                 if (int rc = check_static_lds<M, 1, false>()) return rc;
-                if (int rc = set_lds_attr<M, 1, false>(lds_pass[1])) return rc;
+                if (int rc = set_lds_attr<M, 1, false>(G.lds_pass[1])) return rc;
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tiny_kernel<M, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, tl));
             }
             return 0;
@@ -455,6 +458,14 @@ template <typename real> struct Engine : EngineBase {
         return 0;
 #endif
     }
+    // the quantile weights' constants (src/Draw.pl.jl:163-164) for the sweep, WAIC, the replicates and DIC alike; without weights nu == 1, k1 = 0, k2 = 1
+    struct QuantileConsts { double k1, k2; };
+    QuantileConsts quantile_consts() const {
+        if (!m_nu()) return {0.0, 1.0};
+        const double q = cfg.q_rt;
+        return {(1.0 - 2.0 * q) / (q * (1.0 - q)),
+                2.0 / (q * (1.0 - q))};
+    }
     PassArgs<real> pass_args(int phase, int mode, bool fz = false) const {
         PassArgs<real> a{};
         a.Y = dY.as<uint8_t>(); a.C = dC.as<real>(); a.omega = dOmega.as<real>(); a.nu = dNu.as<real>(); a.X = dX.as<real>();
@@ -462,22 +473,21 @@ template <typename real> struct Engine : EngineBase {
         a.par = dParB[cur].template as<double>(); a.cst = dCst.as<double>(); a.pgtab = dPgTab.as<double>();
         a.slab = phase == 0 ? dSlab0.as<double>() : dSlab1.as<double>();
         a.gslab = phase == 0 ? dGslab0B[fz ? 1 - cur : cur].template as<double>() : dGslab1.as<double>();
-        a.gcnt = dGcnt.as<unsigned int>() + (phase == 0 ? 0 : n_groups);
+        a.gcnt = dGcnt.as<unsigned int>() + (phase == 0 ? 0 : G.n_groups);
         a.ctl = dCtlB[cur].template as<Ctl>();
         a.sum_theta = dSumTheta.as<double>(); a.sum_zeta = dSumZeta.as<double>(); a.sum_nu = dSumNu.as<double>();
         a.tr_theta = dTrTheta.as<real>(); a.tr_zeta = dTrZeta.as<real>(); a.tr_nu = dTrNu.as<real>();
-        a.N = N; a.rows_per_block = rows_per_block; a.rows_per_wave = rows_per_wave; a.J = J; a.nFeat = Fk; a.W = W; a.logW = logW; a.IPL = IPL; a.mode = mode; a.ngx = phase == 0 ? ngx() : 0;
+        a.N = N; a.rows_per_block = G.rows_per_block; a.rows_per_wave = G.rows_per_wave; a.J = J; a.nFeat = Fk; a.W = G.W; a.logW = G.logW; a.IPL = G.IPL; a.mode = mode; a.ngx = phase == 0 ? ngx() : 0;
         a.chain = (uint32_t)cfg.chain_id; a.seed = cfg.seed;
-        const double q = cfg.q_rt;
-        a.k1 = (1.0 - 2.0 * q) / (q * (1.0 - q)); a.k2 = 2.0 / (q * (1.0 - q));   // src/Draw.pl.jl:163-164
-        if (!m_nu()) { a.k1 = 0.0; a.k2 = 1.0; }                                   // no quantile weights: nu == 1, k1 = 0, k2 = 1
+        const QuantileConsts k = quantile_consts();
+        a.k1 = k.k1; a.k2 = k.k2;
         a.dbg_stop = diag_stop("ERM_PASS_STOP"); a.dbg_sweep = (uint32_t)diag_stop("ERM_STOP_SWEEP");
         a.dbg_ts = dDbgTs.as<unsigned long long>();
         a.row_base = (uint32_t)row_base;
         a.acc_off = fz ? G.acc_off_fused : G.acc_off[phase];     // the accumulators close the launch's dynamic LDS
         for (int k = 0; k < 2; ++k) { a.parB[k] = dParB[k].template as<double>(); a.ctlB[k] = dCtlB[k].template as<Ctl>(); a.gslabB[k] = dGslab0B[k].template as<double>(); }
         a.nsweeps = 1u; a.cur0 = (uint32_t)cur;
-        a.xbuf = dXbuf.as<unsigned long long>(); a.tag0 = 0u; a.tmo = dGcnt.as<unsigned int>() + 2 * n_groups;
+        a.xbuf = dXbuf.as<unsigned long long>(); a.tag0 = 0u; a.tmo = dGcnt.as<unsigned int>() + 2 * G.n_groups;
         return a;
     }
     TinyArgs tiny_args(int mode, bool fz = false) const {
@@ -487,12 +497,11 @@ template <typename real> struct Engine : EngineBase {
         t.cst = dCst.as<double>(); t.slab0 = dGslab0B[cur].template as<double>(); t.slab1 = dGslab1.as<double>();
         t.ctl = dCtlB[cur].template as<Ctl>(); t.ctl_out = dCtlB[o].template as<Ctl>(); t.ctl_err = dCtlB[0].template as<Ctl>();
         t.tr_item = dTrItem.as<double>(); t.tr_ll = dTrLl.as<double>();
-        t.N = N; t.J = J; t.nFeat = Fk; t.nb0 = n_groups; t.nb1 = n_groups; t.mode = mode;
+        t.N = N; t.J = J; t.nFeat = Fk; t.nb0 = G.n_groups; t.nb1 = G.n_groups; t.mode = mode;
         t.intercept = cfg.intercept; t.onepl = cfg.one_pl; t.cov2one = cfg.cov2one; t.sigp_mode = cfg.sigp_mode;
         t.chain = (uint32_t)cfg.chain_id; t.seed = cfg.seed;
-        const double q = cfg.q_rt;
-        t.k1 = (1.0 - 2.0 * q) / (q * (1.0 - q)); t.k2 = 2.0 / (q * (1.0 - q));
-        if (!m_nu()) { t.k1 = 0.0; t.k2 = 1.0; }
+        const QuantileConsts k = quantile_consts();
+        t.k1 = k.k1; t.k2 = k.k2;
         t.nq = nq(); t.ngx = ngx();
         if (sharded()) {     // the statistics rows of all devices, gathered after every row pass; N = the whole data set
             t.slab0 = dShardRecv[0].as<double>(); t.slab1 = dShardRecv[1].as<double>(); t.nb0 = shard_count; t.nb1 = shard_count; t.N = n_total;
@@ -519,7 +528,7 @@ template <typename real> struct Engine : EngineBase {
         PassArgs<real> a = pass_args(PHASE, mode);
         TinyArgs t{};
         if (timed) { if (int rc = bracket(false)) return rc; }
-        hipLaunchKernelGGL((pass_kernel<MODEL, real, PHASE, false>), dim3(grid_blocks), dim3(block_threads), lds_pass[PHASE], stream, a, t);
+        hipLaunchKernelGGL((pass_kernel<MODEL, real, PHASE, false>), dim3(G.grid_blocks), dim3(G.block_threads), G.lds_pass[PHASE], stream, a, t);
         if (pw) { if (int rc = launch_behind<MODEL>(cur)) return rc; }
         if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(PHASE, a.gslab);
@@ -527,9 +536,9 @@ template <typename real> struct Engine : EngineBase {
     }
     // Subject-sharded chains: this device's statistics of the pass just enqueued -> one row -> all-gather over the devices
     int shard_exchange(int phase, const double* gslab) {
-        hipLaunchKernelGGL(shard_pack_kernel, dim3(1), dim3(256), 0, stream, gslab, n_groups, ns[phase], dShardSend.as<double>());
+        hipLaunchKernelGGL(shard_pack_kernel, dim3(1), dim3(256), 0, stream, gslab, G.n_groups, G.ns[phase], dShardSend.as<double>());
         HIPCHK(hipGetLastError());
-        return gather_row(phase, (size_t)ns[phase]);
+        return gather_row(phase, (size_t)G.ns[phase]);
     }
     // all-gather of n doubles of dShardSend into dShardRecv[k]: in stream order over RCCL, or through the caller's callback
     int gather_row(int k, size_t n) {
@@ -560,7 +569,7 @@ template <typename real> struct Engine : EngineBase {
         if (base < 0 || ntot < N || base + N > ntot) return fail(ERM_ERR_ARG, "local subjects must lie inside [0, n_subj_total)");
         if (ntot >= (1LL << 32)) return fail(ERM_ERR_ARG, "n_subj_total must fit 32 bits");
         HIPCHK(hipSetDevice(cfg.device));
-        const size_t width = (size_t)std::max(std::max(ns[0], ns[1]), 3 * J + PMAX * PMAX + 8);
+        const size_t width = (size_t)std::max(std::max(G.ns[0], G.ns[1]), 3 * J + PMAX * PMAX + 8);
         if (int rc = dShardSend.alloc(width * sizeof(double))) return rc;
         for (int k = 0; k < (m_cq() ? 2 : 1); ++k) { if (int rc = dShardRecv[k].alloc(width * (size_t)std::max(count, GROUP) * sizeof(double))) return rc; }   // >= GROUP rows: see dGslab0B
         if (rccl_id) {
@@ -570,7 +579,7 @@ template <typename real> struct Engine : EngineBase {
             RCCLCHK(g_rccl.CommInitRank(&comm, count, id, rank));
         }
         shard_rank = rank; shard_count = count; n_total = ntot; row_base = base; exch = fn; exch_user = user;
-        persist = false; persist_avail = false; timing.persistent = 0;          // a sharded sweep exchanges its statistics rows on the host side of every launch
+        set_persist_avail(false);          // a sharded sweep exchanges its statistics rows on the host side of every launch
         return 0;
     }
     // one whole sweep of a single-pass model: tiny step + row pass in one launch; reads buffers [cur], writes [1 - cur]
@@ -578,7 +587,7 @@ template <typename real> struct Engine : EngineBase {
         PassArgs<real> a = pass_args(0, 1, true);
         TinyArgs t = tiny_args(0, true);
         if (timed) { if (int rc = bracket(false)) return rc; }
-        hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true>), dim3(grid_blocks), dim3(block_threads), fused_lds(), stream, a, t);
+        hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true>), dim3(G.grid_blocks), dim3(G.block_threads), G.lds_fused, stream, a, t);
         if (int rc = launch_behind<MODEL>(1 - cur)) return rc;      // the sweep published its parameter block and counters in buffer [1 - cur]
         if (timed) { if (int rc = bracket(true, 1)) return rc; }
         if (sharded()) return shard_exchange(0, a.gslab);     // a.gslab: the group rows this launch wrote
@@ -592,12 +601,12 @@ template <typename real> struct Engine : EngineBase {
         if (xtag > 0x7fffffffu - (uint32_t)nsweeps) { HIPCHK(hipMemsetAsync(dXbuf.p, 0, dXbuf.bytes, stream)); xtag = 0; }
         a.tag0 = xtag; xtag += (uint32_t)nsweeps;
         if (timed) { if (int rc = bracket(false)) return rc; }
-        hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true, true>), dim3(grid_blocks), dim3(block_threads), fused_lds(), stream, a, t);
+        hipLaunchKernelGGL((pass_kernel<MODEL, real, 0, true, true>), dim3(G.grid_blocks), dim3(G.block_threads), G.lds_fused, stream, a, t);
         return bracket(true, nsweeps);
     }
     template <int MODEL, int STEP> int launch_tiny(int mode) {
         TinyArgs t = tiny_args(mode);
-        hipLaunchKernelGGL((tiny_kernel<MODEL, STEP>), dim3(1), dim3(TINY_THREADS), tiny_lds(), stream, t);
+        hipLaunchKernelGGL((tiny_kernel<MODEL, STEP>), dim3(1), dim3(TINY_THREADS), G.lds_tiny, stream, t);
         return 0;
     }
 
@@ -631,21 +640,24 @@ template <typename real> struct Engine : EngineBase {
     // ---- WAIC: the pointwise pass behind a sweep (erm_waic_kernels.hpp).  buf: the half of the double buffers the sweep published its parameter block and
     // counters in.  The same launch for every sweep (the kernel itself skips burn-in rows), so it sits inside the captured graphs like the sweep's own kernels.
     int64_t pw_units(int unit) const { return unit == PW_SUBJECT ? N : unit == PW_CELL ? N * (int64_t)J : 0; }
+    // the resident cell as every pass behind a sweep reads it (CellArgs, erm_waic_kernels.hpp)
+    CellArgs cell_args(int buf) const {
+        CellArgs c{};
+        c.Y = dY.as<uint8_t>(); c.C = dC.p; c.nu = cfg.model == ERM_MODEL_CROSSQR ? dNuSnap.p : nullptr; c.theta = dTheta.p; c.zeta = dZeta.p;
+        c.par = dParB[buf].template as<double>(); c.cm = dCst.as<double>() + cst_off_m(J); c.ctl = dCtlB[buf].template as<Ctl>();
+        c.N = N; c.J = J; c.logW = pass_log_lanes(J);
+        const QuantileConsts k = quantile_consts();
+        c.k1 = k.k1; c.k2 = k.k2;
+        return c;
+    }
     template <int MODEL> int launch_pointwise(int buf) {
         if (pw_unit == PW_OFF) return 0;
         PwArgs a{};
-        a.Y = dY.as<uint8_t>(); a.C = dC.p; a.nu = MODEL == CROSSQR ? dNuSnap.p : nullptr; a.theta = dTheta.p; a.zeta = dZeta.p;
-        a.par = dParB[buf].template as<double>(); a.cm = dCst.as<double>() + cst_off_m(J); a.ctl = dCtlB[buf].template as<Ctl>();
+        a.cell = cell_args(buf);
         a.acc_ms = dPwMs.as<double2>(); a.acc_w = dPwW.as<double2>();
-        a.N = N; a.J = J;
-        int lw = 0;
-        while ((1 << lw) < 64 && (4 << lw) < J) ++lw;      // lanes per subject: the smallest power of two that leaves a lane at most four items (64 at most)
-        a.logW = lw;
-        const double q = cfg.q_rt;
-        a.k1 = m_nu() ? (1.0 - 2.0 * q) / (q * (1.0 - q)) : 0.0; a.k2 = m_nu() ? 2.0 / (q * (1.0 - q)) : 1.0;
         const size_t lds = (size_t)7 * J * sizeof(double);
         if (pw_unit == PW_SUBJECT) {
-            const int64_t R = 256 >> lw;
+            const int64_t R = 256 >> a.cell.logW;
             const int nb = (int)std::min<int64_t>((N + R - 1) / R, (int64_t)cu_count * 8);
             hipLaunchKernelGGL((pointwise_kernel<MODEL, real, PW_SUBJECT>), dim3(nb), dim3(256), lds, stream, a);
         } else {
@@ -654,11 +666,29 @@ template <typename real> struct Engine : EngineBase {
         }
         return 0;
     }
-    static int alloc_or_nomem(DevBuf& d, size_t n, const char* what = "the WAIC accumulators") {
-        void* q = nullptr;
-        if (hipMalloc(&q, n) != hipSuccess) { (void)hipGetLastError(); return fail(ERM_ERR_NOMEM, std::string("out of device memory for ") + what + " (" + std::to_string(n) + " bytes)"); }
-        if (d.p) (void)hipFree(d.p);
-        d.p = q; d.bytes = n;
+    // The one way a pass behind the sweep is switched (erm_set_pointwise, erm_set_predictive).  sw: the pass's switch (pw_unit / pred_thin, 0 = off), want: its new
+    // value; bufs: the buffers the pass owns and the sizes it wants of them now (0 = released).  The refusals, in this order; the device drained; `configure` (the
+    // pass's own preparation, may fail); the buffers whose size changes staged and only then moved into place, so that a failed allocation leaves the engine
+    // exactly as it was; the captured graphs dropped if the switch moved; the schedule decided again.  The caller clears its accumulators afterwards.
+    struct PassBuf { DevBuf* buf; size_t bytes; const char* what; };
+    int switch_pass(const char* api, const char* subject, int& sw, int want, std::vector<PassBuf> bufs, const char* snap_what, const std::function<int()>& configure = nullptr) {
+        if (rows_done > 0) return fail(ERM_ERR_STATE, std::string(api) + " is allowed only while no trace row is recorded (after erm_create or erm_reset_trace)");
+        if (want && sharded()) return fail(ERM_ERR_STATE, std::string(subject) + " not available under subject sharding (the accumulators of the shards would have to be merged across devices)");
+        HIPCHK(hipSetDevice(cfg.device));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (configure) { if (int rc = configure()) return rc; }
+        const int prev = sw;
+        sw = want;      // what follows is a function of the resulting state (put back if an allocation fails)
+        // GibbsRtIrtCrossQr's copy of nu_t: kept iff any pass is on
+        bufs.push_back({&dNuSnap, cfg.model == ERM_MODEL_CROSSQR && aux_pass() ? dNu.bytes : 0, snap_what});
+        std::vector<DevBuf> staged(bufs.size());
+        for (size_t k = 0; k < bufs.size(); ++k) {
+            if (bufs[k].bytes == bufs[k].buf->bytes) continue;
+            if (int rc = staged[k].try_alloc(bufs[k].bytes, bufs[k].what)) { sw = prev; return rc; }
+        }
+        for (size_t k = 0; k < bufs.size(); ++k) { if (bufs[k].bytes != bufs[k].buf->bytes) *bufs[k].buf = std::move(staged[k]); }
+        if (want != prev) drop_graphs();      // the captured sweeps hold (or lack) the pass's launches, and its switch as a kernel argument
+        set_persist_avail(persist_avail);
         return 0;
     }
     int pw_clear() {
@@ -667,26 +697,9 @@ template <typename real> struct Engine : EngineBase {
     }
     int set_pointwise(int unit) override {
         if (unit != PW_OFF && unit != PW_SUBJECT && unit != PW_CELL) return fail(ERM_ERR_ARG, "unknown pointwise unit (ERM_POINTWISE_OFF / _SUBJECT / _CELL)");
-        if (rows_done > 0) return fail(ERM_ERR_STATE, "erm_set_pointwise is allowed only while no trace row is recorded (after erm_create or erm_reset_trace)");
-        if (unit != PW_OFF && sharded()) return fail(ERM_ERR_STATE, "WAIC is not available under subject sharding (the accumulators of the shards would have to be merged across devices)");
-        HIPCHK(hipSetDevice(cfg.device));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (unit != PW_OFF) {
-            // the new buffers first: a failed allocation leaves the engine exactly as it was
-            const size_t nb = (size_t)pw_units(unit) * sizeof(double2);
-            DevBuf ms, w, snap;
-            if (nb != dPwMs.bytes) { if (int rc = alloc_or_nomem(ms, nb)) return rc; if (int rc = alloc_or_nomem(w, nb)) return rc; }
-            if (cfg.model == ERM_MODEL_CROSSQR && !dNuSnap.p) { if (int rc = alloc_or_nomem(snap, dNu.bytes)) return rc; }
-            if (ms.p) { std::swap(ms.p, dPwMs.p); std::swap(ms.bytes, dPwMs.bytes); std::swap(w.p, dPwW.p); std::swap(w.bytes, dPwW.bytes); }
-            if (snap.p) { std::swap(snap.p, dNuSnap.p); std::swap(snap.bytes, dNuSnap.bytes); }
-        } else {
-            (void)dPwMs.alloc(0); (void)dPwW.alloc(0);
-            if (pred_thin == 0) (void)dNuSnap.alloc(0);
-        }
-        if (unit != pw_unit) drop_graphs();          // the captured sweeps hold (or lack) the pointwise launch
-        pw_unit = unit;
-        persist = aux_pass() ? false : persist_avail;          // a persistent launch cannot interleave another kernel between its sweeps
-        timing.persistent = persist ? 1 : 0;
+        const size_t nb = (size_t)pw_units(unit) * sizeof(double2);
+        const char* what = "the WAIC accumulators";
+        if (int rc = switch_pass("erm_set_pointwise", "WAIC is", pw_unit, unit, {{&dPwMs, nb, what}, {&dPwW, nb, what}}, what)) return rc;
         return pw_clear();
     }
     int64_t pointwise_units() const override { return pw_units(pw_unit); }
@@ -750,8 +763,7 @@ template <typename real> struct Engine : EngineBase {
     struct PredGeom { int logW, T, nb, nq; size_t lds; };
     PredGeom pred_geom() const {
         PredGeom g{};
-        while ((1 << g.logW) < 64 && (4 << g.logW) < J) ++g.logW;      // lanes per subject: as the WAIC subject unit
-        g.T = 256; g.nq = pred_nq(cfg.model);
+        g.logW = pass_log_lanes(J); g.T = 256; g.nq = pred_nq(cfg.model);
         while (g.T > 64 && pred_lds_bytes(cfg.model, J, g.T, g.logW) > (size_t)160 * 1024) g.T >>= 1;      // long tests: fewer subject slots (nItem 896: 128 threads, 115 KB)
         g.lds = pred_lds_bytes(cfg.model, J, g.T, g.logW);
         const int64_t R = g.T >> g.logW;
@@ -766,17 +778,13 @@ template <typename real> struct Engine : EngineBase {
         if (pred_thin == 0) return 0;
         const PredGeom g = pred_geom();
         PredArgs a{};
-        a.Y = dY.as<uint8_t>(); a.C = dC.p; a.nu = MODEL == CROSSQR ? dNuSnap.p : nullptr; a.theta = dTheta.p; a.zeta = dZeta.p;
-        a.par = dParB[buf].template as<double>(); a.cm = dCst.as<double>() + cst_off_m(J); a.ctl = dCtlB[buf].template as<Ctl>();
-        a.subj = dPredSubj.as<double>(); a.slab = dPredSlab.as<double>();
-        a.N = N; a.J = J; a.logW = g.logW; a.thin = (uint32_t)pred_thin;
-        const double q = cfg.q_rt;
-        a.k1 = m_nu() ? (1.0 - 2.0 * q) / (q * (1.0 - q)) : 0.0; a.k2 = m_nu() ? 2.0 / (q * (1.0 - q)) : 1.0;
+        a.cell = cell_args(buf);
+        a.subj = dPredSubj.as<double>(); a.slab = dPredSlab.as<double>(); a.thin = (uint32_t)pred_thin;
         a.seed = cfg.seed; a.chain = (uint32_t)cfg.chain_id; a.row_base = (uint32_t)row_base;
         hipLaunchKernelGGL((predictive_kernel<MODEL, real>), dim3(g.nb), dim3(g.T), g.lds, stream, a);
         PredItemArgs b{};
         b.slab = dPredSlab.as<double>(); b.nb = g.nb; b.nq = g.nq; b.J = J; b.N = (double)N; b.k0 = dCst.as<double>() + cst_off_k0(J);
-        b.ctl = a.ctl; b.thin = a.thin; b.item = dPredItem.as<double>(); b.tot = dPredItem.as<double>() + (size_t)J * PRED_ITEM;
+        b.ctl = a.cell.ctl; b.thin = a.thin; b.item = dPredItem.as<double>(); b.tot = dPredItem.as<double>() + (size_t)J * PRED_ITEM;
         hipLaunchKernelGGL(predictive_items_kernel, dim3(1), dim3(PRED_IT_THREADS), 0, stream, b);
         return 0;
     }
@@ -786,34 +794,18 @@ template <typename real> struct Engine : EngineBase {
     }
     int set_predictive(int on, int32_t thin) override {
         if (on && thin < 1) return fail(ERM_ERR_ARG, "erm_set_predictive: thin must be at least 1");
-        if (rows_done > 0) return fail(ERM_ERR_STATE, "erm_set_predictive is allowed only while no trace row is recorded (after erm_create or erm_reset_trace)");
-        if (on && sharded()) return fail(ERM_ERR_STATE, "posterior predictive checks are not available under subject sharding (the accumulators of the shards would have to be merged across devices)");
-        HIPCHK(hipSetDevice(cfg.device));
-        HIPCHK(hipStreamSynchronize(stream));
-        const int32_t want = on ? thin : 0;
-        if (on) {
-            const PredGeom g = pred_geom();
-            if (int rc = dispatch([&](auto m) -> int {
-                    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&predictive_kernel<decltype(m)::value, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
-                    return 0; })) return rc;
-            // the new buffers first: a failed allocation leaves the engine exactly as it was
-            DevBuf su, it, sl, snap;
-            if (!dPredSubj.p) {
-                if (int rc = alloc_or_nomem(su, (size_t)N * PRED_SUBJ * sizeof(double), "the predictive accumulators")) return rc;
-                if (int rc = alloc_or_nomem(it, ((size_t)J * PRED_ITEM + PRED_TOT + 1) * sizeof(double), "the predictive accumulators")) return rc;
-                if (int rc = alloc_or_nomem(sl, (size_t)g.nb * g.nq * J * sizeof(double), "the predictive slab")) return rc;
-            }
-            if (cfg.model == ERM_MODEL_CROSSQR && !dNuSnap.p) { if (int rc = alloc_or_nomem(snap, dNu.bytes, "the copy of nu")) return rc; }
-            if (su.p) { std::swap(su.p, dPredSubj.p); std::swap(su.bytes, dPredSubj.bytes); std::swap(it.p, dPredItem.p); std::swap(it.bytes, dPredItem.bytes); std::swap(sl.p, dPredSlab.p); std::swap(sl.bytes, dPredSlab.bytes); }
-            if (snap.p) { std::swap(snap.p, dNuSnap.p); std::swap(snap.bytes, dNuSnap.bytes); }
-        } else {
-            (void)dPredSubj.alloc(0); (void)dPredItem.alloc(0); (void)dPredSlab.alloc(0);
-            if (pw_unit == PW_OFF) (void)dNuSnap.alloc(0);
-        }
-        if (want != pred_thin) drop_graphs();        // the captured sweeps hold (or lack) the pass, and its thinning as a kernel argument
-        pred_thin = want;
-        persist = aux_pass() ? false : persist_avail;
-        timing.persistent = persist ? 1 : 0;
+        const PredGeom g = pred_geom();
+        const size_t dbl = on ? sizeof(double) : 0;      // off: every buffer released
+        const char* acc = "the predictive accumulators";
+        auto lds_limit = [&]() -> int {
+            if (!on) return 0;
+            return dispatch([&](auto m) -> int {
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&predictive_kernel<decltype(m)::value, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+                return 0; });
+        };
+        if (int rc = switch_pass("erm_set_predictive", "posterior predictive checks are", pred_thin, on ? thin : 0,
+                                 {{&dPredSubj, (size_t)N * PRED_SUBJ * dbl, acc}, {&dPredItem, ((size_t)J * PRED_ITEM + PRED_TOT + 1) * dbl, acc},
+                                  {&dPredSlab, (size_t)g.nb * g.nq * J * dbl, "the predictive slab"}}, "the copy of nu", lds_limit)) return rc;
         return pred_clear();
     }
     int64_t predictive_reps() const override { return pred_thin > 0 ? (post_rows + pred_thin - 1) / pred_thin : 0; }
@@ -842,10 +834,10 @@ template <typename real> struct Engine : EngineBase {
         return 0;
     }
     void launch_run_begin() {
-        hipLaunchKernelGGL(run_begin_kernel, dim3(1), dim3(256), 0, stream, dCtlB[0].template as<Ctl>(), dCtlB[1].template as<Ctl>(), host_run_dev, dGcnt.as<unsigned int>(), 2 * n_groups + 4);
+        hipLaunchKernelGGL(run_begin_kernel, dim3(1), dim3(256), 0, stream, dCtlB[0].template as<Ctl>(), dCtlB[1].template as<Ctl>(), host_run_dev, dGcnt.as<unsigned int>(), 2 * G.n_groups + 4);
     }
     void launch_run_end() {
-        hipLaunchKernelGGL(run_end_kernel, dim3(1), dim3(64), 0, stream, dCtlB[0].template as<Ctl>(), dCtlB[1].template as<Ctl>(), dGcnt.as<unsigned int>() + 2 * n_groups,
+        hipLaunchKernelGGL(run_end_kernel, dim3(1), dim3(64), 0, stream, dCtlB[0].template as<Ctl>(), dCtlB[1].template as<Ctl>(), dGcnt.as<unsigned int>() + 2 * G.n_groups,
                            host_ctl_dev + 1, reinterpret_cast<unsigned int*>(host_ctl_dev + 3));
     }
     Plan plan;                                       // the call being enqueued
@@ -908,10 +900,10 @@ template <typename real> struct Engine : EngineBase {
         f(dSumTheta); if (is_rt()) f(dSumZeta); if (dSumNu.p) f(dSumNu);
     }
     size_t snap_bytes() const {
-        // (called before the buffers exist: sizes from the configuration)
+        // (called before the buffers exist: sizes from the configuration and the planned geometry)
         const size_t NJ = (size_t)N * J, r = sizeof(real);
         size_t b = (size_t)N * r + (is_rt() ? (size_t)N * r : 0) + NJ * r + (cfg.model == ERM_MODEL_LATENTQR ? (size_t)N * r : 0);
-        b += (size_t)par_size(J) * 8 + (size_t)std::max(n_groups, GROUP) * ns[0] * 8;
+        b += (size_t)par_size(J) * 8 + (size_t)std::max(G.n_groups, GROUP) * G.ns[0] * 8;
         b += (size_t)N * 8 + (is_rt() ? (size_t)N * 8 : 0) + (cfg.model == ERM_MODEL_LATENTQR ? (size_t)N * 8 : 0);
         return b + 10 * 256;                         // every segment starts on a 256-byte boundary
     }
@@ -950,7 +942,7 @@ template <typename real> struct Engine : EngineBase {
             // the persistent launch never had all its workgroups resident (another process holds compute units): every workgroup has left the launch;
             // put back what the call found, leave the persistent schedule for good and run the call again, one launch per sweep at the same geometry
             // (bit for bit the chain the persistent launch would have produced)
-            persist = false; persist_avail = false; timing.persistent = 0; ++timing.persist_fallbacks;
+            set_persist_avail(false); ++timing.persist_fallbacks;
             rc = snap_copy(true);
             if (rc == 0) { cur = 0; stats_valid = snap_stats_valid; rc = run_checked(nsweeps); }
             if (rc == ERM_PERSIST_TIMEOUT) rc = fail(ERM_ERR_STATE, "internal: persistent time-out reported by a per-sweep run");
@@ -1651,8 +1643,8 @@ template <typename real> struct Engine : EngineBase {
         D.sum = dsum; D.inv = inv; D.N = N; D.J = J; D.F = Fk; D.model = cfg.model;
         const int64_t wi = item_trace_width();
         D.off_theta = wi; D.off_zeta = is_rt() ? wi + N : -1; D.off_nu = nu_len() > 0 ? wi + N + (is_rt() ? N : 0) : -1;
-        const double q = cfg.q_rt;
-        D.k1 = m_nu() ? (1.0 - 2.0 * q) / (q * (1.0 - q)) : 0.0; D.k2 = m_nu() ? 2.0 / (q * (1.0 - q)) : 1.0;
+        const QuantileConsts k = quantile_consts();
+        D.k1 = k.k1; D.k2 = k.k2;
         D.rows_per_block = (N + nb - 1) / nb; D.part = dPart.as<double>();
         const size_t lds = ((size_t)5 * J + 4 + 2 * PMAX) * sizeof(double);
         hipLaunchKernelGGL((loglik_kernel<real>), dim3(nb), dim3(256), lds, stream, D);

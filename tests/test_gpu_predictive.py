@@ -246,6 +246,71 @@ def test_every_refusal_returns_its_code_and_leaves_the_engine_usable():
     M.close()
 
 
+# ------------------------------------------------------------------------------------------------------------ two switches, one path
+@pytest.mark.parametrize("model,precision", [("crossqr", "f64"), ("cross", "f32")])
+def test_one_pass_turned_off_leaves_the_other_as_if_alone(model, precision):
+    """600 x 9 (two workgroups and the tail subject; the Cross family never runs persistent).  Both passes enabled, then one of them turned off again, in both orders:
+    the pass that stays -- and for GibbsRtIrtCrossQr the copy of nu_t it reads -- leaves the accumulators of an engine that only ever had that pass, and the chain
+    does not move."""
+    Y, logT, X, init, tp = pu.make_problem(model, 600, 9, 3, seed=41)
+    kw = dict(n_iter=6, n_burnin=2, precision=precision)
+    a = _engine(model, Y, logT, X, init, waic="subject", ppc=1, **kw)
+    a.set_pointwise(None)
+    b = _engine(model, Y, logT, X, init, ppc=1, **kw)
+    c = _engine(model, Y, logT, X, init, waic="subject", ppc=1, **kw)
+    c.set_predictive(False)
+    d = _engine(model, Y, logT, X, init, waic="subject", **kw)
+    for eng in (a, b, c, d):
+        eng.run(6)
+    assert _bytes(a) == _bytes(b)
+    assert c.waic() == d.waic() and [x.tobytes() for x in c.pointwise()] == [x.tobytes() for x in d.pointwise()]
+    ref = _everything(a, model)
+    assert all(_everything(eng, model) == ref for eng in (b, c, d))
+    host, _ = _twin(a, model, n_iter=6, n_chain=1, n_burnin=2, thin=1)
+    ppu.assert_equals_twin(_device(a, 1), host, what=f"{model} {precision} after WAIC was turned off")
+    for eng in (a, b, c, d):
+        eng.close()
+
+
+def test_persistent_schedule_returns_only_when_the_last_pass_goes():
+    """1 000 x 15 is eligible for the persistent schedule (erm_timing.persistent is 1 unless the occupancy check declined: compared with a fresh engine's)."""
+    Y, logT, X, init, tp = pu.make_problem("rtirt", 1000, 15, 3, seed=13)
+    ref = _engine("rtirt", Y, logT, X, init, n_iter=12, n_burnin=5)
+    eng = _engine("rtirt", Y, logT, X, init, n_iter=12, n_burnin=5)
+    p0 = eng.timing()["persistent"]
+    assert p0 == ref.timing()["persistent"]
+    eng.set_pointwise("subject")
+    assert eng.timing()["persistent"] == 0
+    eng.set_predictive(True, 1)
+    assert eng.timing()["persistent"] == 0
+    eng.set_pointwise(None)
+    assert eng.timing()["persistent"] == 0
+    eng.set_predictive(False)
+    assert eng.timing()["persistent"] == p0
+    for e in (eng, ref):
+        e.run(5)
+        e.run(7)
+    assert _everything(eng, "rtirt") == _everything(ref, "rtirt")
+    eng.close()
+    ref.close()
+
+
+def test_a_refused_switch_changes_nothing():
+    """erm_set_pointwise on an engine with two rows recorded is refused; the replicate pass that was running goes on as on an engine that never received the call."""
+    lib = pu.ge.load_package()._lib.load()
+    Y, logT, X, init, tp = pu.make_problem("rtirt", 500, 9, 3, seed=31)
+    out = []
+    for refused in (True, False):
+        eng = _engine("rtirt", Y, logT, X, init, n_iter=6, n_burnin=2, ppc=1)
+        eng.run(2)
+        if refused:
+            assert lib.erm_set_pointwise(eng._h, 1) == -3 and "no trace row" in lib.erm_last_error().decode()
+        eng.run(4)
+        out.append((_bytes(eng), _everything(eng, "rtirt")))
+        eng.close()
+    assert out[0] == out[1]
+
+
 # ------------------------------------------------------------------------------------------------------------ full size
 def test_full_size_rtirt_summary_trace():
     """GibbsRtIrt 100 000 x 50, fp64, default geometry, summary-trace mode (no per-sweep theta / zeta is kept anywhere): 160 sweeps, the last 60 replicated.
