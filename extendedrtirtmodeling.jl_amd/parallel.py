@@ -129,14 +129,22 @@ class ThreadExchange:
         self.barrier.abort()
 
 
-def run_sharded_threads(make_engine, count: int, n_subj: int, Y, logT, X, state, nsweeps: int):
+def run_sharded_threads(make_engine, count: int, n_subj: int, Y, logT, X, state, nsweeps: int, *, rows=None, script=None):
     """Drive `count` shards of one chain from `count` host threads of this process.  make_engine(n_local) -> _lib.Engine (not yet
-    sharded, no data); Y / logT / X / state['theta'|'zeta'|'nu'] are split by rows.  Returns the engines (data resident, nsweeps run)."""
+    sharded, no data); Y / logT / X / state['theta'|'zeta'|'nu'] are split by rows.  Returns the engines (data resident, nsweeps run).
+    `rows`: explicit [(row_base, n_local)] ranges, one per shard, tiling [0, n_subj) in order (default: shard_rows).  `script(rank, engine)`
+    runs in each shard's thread in place of the single engine.run(nsweeps); every shard must issue the same collective calls in the same order."""
     import threading
     from . import _lib
     lib = _lib.load()
     ex = ThreadExchange(lib, count)
-    rows = shard_rows(n_subj, count)
+    if rows is None:
+        rows = shard_rows(n_subj, count)
+    else:
+        rows = [(int(lo), int(n)) for lo, n in rows]
+        ends = [lo + n for lo, n in rows]
+        if len(rows) != count or any(n < 1 for _, n in rows) or [lo for lo, _ in rows] != [0] + ends[:-1] or ends[-1] != n_subj:
+            raise ValueError("rows must be `count` non-empty ranges that tile [0, n_subj) in order")
     engines, errors = [None] * count, [None] * count
 
     def cut(a, lo, n):
@@ -156,7 +164,10 @@ def run_sharded_threads(make_engine, count: int, n_subj: int, Y, logT, X, state,
             if st.get("nu") is not None:
                 st["nu"] = np.asfortranarray(cut(np.asarray(st["nu"]).reshape(n_subj, -1, order="F"), lo, n)).reshape(-1, order="F")
             eng.set_state(**st)
-            eng.run(nsweeps)
+            if script is None:
+                eng.run(nsweeps)
+            else:
+                script(r, eng)
         except BaseException as e:
             errors[r] = getattr(engines[r], "exchange_error", None) or e
             ex.abort()

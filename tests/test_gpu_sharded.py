@@ -7,51 +7,9 @@ import pytest
 import __graft_entry__ as ge
 import parity_util as pu
 from parity_util import MODELS
+from shard_util import sharded as _sharded
 
 pytestmark = pytest.mark.gpu
-
-
-def _sharded(model, N, J, nsweeps, count, *, F=3, precision="f64", seed=7, qRt=0.85, **opts):
-    pkg = ge.load_package()
-    L = pkg._lib
-    Y, logT, X, init, tp = pu.make_problem(model, N, J, F, seed=seed, qRt=qRt)
-    cov2one = model not in ("latentqr", "latent")
-    Fx = 0 if X is None else X.shape[1]
-
-    def make_engine(n_local):
-        return L.Engine(model=MODELS[model], n_item=J, n_subj=n_local, n_feat=Fx, n_iter=nsweeps, n_chain=1, n_burnin=nsweeps // 2,
-                        cov2one=int(cov2one), q_rt=qRt, seed=1234, precision={"f32": 0, "f64": 1}[precision], trace_mode=1, **opts)
-
-    st = {("lambda_" if k == "lam" else k): v for k, v in init.items()}
-    engines = pkg.parallel.run_sharded_threads(make_engine, count, N, Y, logT, X, st, nsweeps)
-    op = pu.OracleProblem(model, Y, logT, X, init, qRt=qRt, cov2one=cov2one, seed=1234)
-    orc = op.run(nsweeps, with_nu=(model in ("latentqr", "crossqr")))
-    rows = pkg.parallel.shard_rows(N, count)
-    ra = [e.trace(L.TRACE_RA)[:, :, 0] for e in engines]
-    out = {"orc": orc, "model": model, "engines": engines}
-    for r in range(1, count):            # item blocks are identical on every shard, bit for bit
-        np.testing.assert_array_equal(ra[r][:, rows[r][1]:], ra[0][:, rows[0][1]:])
-    out["dev_ra"] = np.concatenate([ra[r][:, :rows[r][1]] for r in range(count)] + [ra[0][:, rows[0][1]:]], axis=1)
-    if model != "mlirt":
-        rt = [e.trace(L.TRACE_RT)[:, :, 0] for e in engines]
-        for r in range(1, count):
-            np.testing.assert_array_equal(rt[r][:, rows[r][1]:], rt[0][:, rows[0][1]:])
-        out["dev_rt"] = np.concatenate([rt[r][:, :rows[r][1]] for r in range(count)] + [rt[0][:, rows[0][1]:]], axis=1)
-    qr = [e.trace(L.TRACE_QR)[:, :, 0] for e in engines]
-    if model == "latentqr":
-        k = Fx + 2 + 4
-        out["dev_qr"] = np.concatenate([qr[0][:, :k]] + [qr[r][:, k:] for r in range(count)], axis=1)
-    elif model == "crossqr":
-        k = J + 4
-        nus = [qr[r][:, k:].reshape(nsweeps, rows[r][1], J, order="F") for r in range(count)]       # vec(nu) is column-major [n_local x J]
-        out["dev_qr"] = np.concatenate([qr[0][:, :k], np.concatenate(nus, axis=1).reshape(nsweeps, N * J, order="F")], axis=1)
-    else:
-        out["dev_qr"] = qr[0]
-    ll = [e.trace(L.TRACE_LOGLIKE)[:, 0, 0] for e in engines]
-    for r in range(1, count):
-        np.testing.assert_array_equal(ll[r], ll[0])
-    out["dev_ll"] = ll[0]
-    return out
 
 
 @pytest.mark.parametrize("model", list(MODELS))
