@@ -6,6 +6,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
+from types import MappingProxyType
 
 import numpy as np
 
@@ -17,6 +19,40 @@ MODEL_NULL, MODEL_CROSS, MODEL_LATENT = 4, 5, 6          # the non-quantile vari
 PREC_F32, PREC_F64 = 0, 1
 TRACE_SUMMARY, TRACE_FULL = 0, 1
 TRACE_RA, TRACE_RT, TRACE_QR, TRACE_LOGLIKE = 0, 1, 2, 3
+
+# What distinguishes the models on the host -- the same table as csrc/erm_model.hpp (model_traits), entry for entry (tests/test_model_traits.py):
+#   rt: response times (logT, zeta, lambda, sig2t, Sigp, Post.rt);  rho: the cross-relation;  nu: "none" | "subject" (N) | "cell" (N x J);
+#   sees_x: the kernels read Data.X;  beta: "none" | "vec" (nFeat+1) | "pair" ((nFeat+1) x 2) | "latent" (nFeat+2) | "zero_pair" (Null: a pair that is
+#   always zero);  gen: the erm_simulate_data generator (0 MlIrt, 1 RtIrt, 2 Null, 3 Cross, 4 Latent)
+ModelTraits = namedtuple("ModelTraits", "rt rho nu sees_x beta gen")
+MODEL_TRAITS = MappingProxyType({
+    MODEL_MLIRT: ModelTraits(False, False, "none", True, "vec", 0),
+    MODEL_RTIRT: ModelTraits(True, False, "none", True, "pair", 1),
+    MODEL_CROSSQR: ModelTraits(True, True, "cell", False, "none", 3),
+    MODEL_LATENTQR: ModelTraits(True, False, "subject", True, "latent", 4),
+    MODEL_NULL: ModelTraits(True, False, "none", False, "zero_pair", 2),
+    MODEL_CROSS: ModelTraits(True, True, "none", False, "none", 3),
+    MODEL_LATENT: ModelTraits(True, False, "none", True, "latent", 4),
+})
+
+
+def beta_shape(model, F):
+    """Para.beta's shape: () when the model has none (or, for Null, never draws one)."""
+    return {"none": (), "vec": (F + 1,), "pair": (F + 1, 2), "latent": (F + 2,), "zero_pair": (F + 1, 2)}[MODEL_TRAITS[model].beta]
+
+
+def nbeta(model, F):
+    """Entries of erm_state.beta (Null's are reported as zeros): beta_len of csrc/erm_model.hpp."""
+    return {"none": 0, "vec": F + 1, "pair": 2 * (F + 1), "latent": F + 2, "zero_pair": 2 * (F + 1)}[MODEL_TRAITS[model].beta]
+
+
+def nu_len(model, N, J):
+    return {"none": 0, "subject": N, "cell": N * J}[MODEL_TRAITS[model].nu]
+
+
+def kernel_feat(model, F):
+    """Covariate columns the kernels see: the Cross family and Null never touch Data.X."""
+    return F if MODEL_TRAITS[model].sees_x else 0
 
 EXPORTS = [
     "erm_create", "erm_destroy", "erm_set_data", "erm_set_state", "erm_get_state", "erm_run", "erm_rows_done",
@@ -261,9 +297,9 @@ class Engine:
         """The resident data set as (Y uint8 NxJ, logT float64 NxJ or None, X float64 NxF or None), column-major."""
         c = self.cfg
         N, J = c.n_subj, c.n_item
-        F = 0 if c.model in (MODEL_CROSSQR, MODEL_CROSS, MODEL_NULL) else c.n_feat
+        F = kernel_feat(c.model, c.n_feat)
         Y = np.empty((N, J), dtype=np.uint8, order="F")
-        logT = None if c.model == MODEL_MLIRT else np.empty((N, J), dtype=np.float64, order="F")
+        logT = np.empty((N, J), dtype=np.float64, order="F") if MODEL_TRAITS[c.model].rt else None
         X = np.empty((N, F), dtype=np.float64, order="F") if F > 0 else None
         check(self._lib.erm_get_data(self._h, Y.ctypes.data, None if logT is None else logT.ctypes.data, None if X is None else X.ctypes.data))
         return Y, logT, X
@@ -276,10 +312,7 @@ class Engine:
     def _state_buffers(self, which=None):
         c = self.cfg
         N, J, F = c.n_subj, c.n_item, c.n_feat
-        nb = {MODEL_MLIRT: F + 1, MODEL_RTIRT: 2 * (F + 1), MODEL_LATENTQR: F + 2, MODEL_CROSSQR: 0,
-              MODEL_NULL: 2 * (F + 1), MODEL_CROSS: 0, MODEL_LATENT: F + 2}[c.model]
-        nnu = {MODEL_LATENTQR: N, MODEL_CROSSQR: N * J}.get(c.model, 0)
-        sizes = dict(theta=N, a=J, b=J, zeta=N, lambda_=J, sig2t=J, beta=nb, sigp=4, rho=J, nu=nnu)
+        sizes = dict(theta=N, a=J, b=J, zeta=N, lambda_=J, sig2t=J, beta=nbeta(c.model, F), sigp=4, rho=J, nu=nu_len(c.model, N, J))
         return {k: (np.zeros(n, dtype=np.float64) if n and (which is None or k in which) else None) for k, n in sizes.items()}
 
     def get_state(self, which=None):

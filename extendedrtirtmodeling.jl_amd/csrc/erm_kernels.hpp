@@ -2375,6 +2375,7 @@ __global__ void __launch_bounds__(256) loglik_kernel(LogLikArgs D)
     __shared__ double red[256];
     for (int e = tid; e < 4 * J; e += 256) sa[e] = D.sum[e] * D.inv;
     const double* q = D.sum + 4 * J;                      // the small part of qr (tiny_publish's order)
+    // (the offsets below restate qr_sigp_off / beta_len of erm_model.hpp, the host's table: a change there is a change here)
     for (int j = tid; j < J; j += 256) sr[j] = fam_cq(M) ? q[j] * D.inv : 0.0;
     if (tid < 4) sS[tid] = (M == MLIRT) ? (tid == 0 || tid == 3 ? 1.0 : 0.0) : q[(fam_cq(M) ? J : (fam_rt(M) ? 2 * p : p + 1)) + tid] * D.inv;
     if (tid < 2 * PMAX) {

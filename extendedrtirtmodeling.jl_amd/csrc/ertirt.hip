@@ -20,6 +20,7 @@
 #include "erm_kernels.hpp"
 #include "erm_predictive_kernels.hpp"      // posterior predictive checks: the replicate pass behind every sweep
 #include "erm_geometry.hpp"
+#include "erm_model.hpp"
 #include "erm_schedule.hpp"
 
 using namespace erm;
@@ -172,36 +173,13 @@ struct EngineBase {
     int64_t rows_done = 0;
     int64_t post_rows = 0;
     erm_timing timing{};
-    int64_t trace_width(int which) const {
-        const int64_t N = cfg.n_subj, J = cfg.n_item, F = cfg.n_feat;
-        switch (which) {
-        case ERM_TRACE_RA: return N + 2 * J;                                              // src/GibbsRtIrt.pl.jl:44,65
-        case ERM_TRACE_RT: return cfg.model == ERM_MODEL_MLIRT ? 0 : N + 2 * J;           // :66 (MlIrt's rt stays [])
-        case ERM_TRACE_QR:
-            switch (cfg.model) {
-            case ERM_MODEL_MLIRT: return F + 1;                                           // :45
-            case ERM_MODEL_RTIRT: return 2 * (F + 1) + 4;                                 // :67
-            case ERM_MODEL_CROSSQR: return J + 4 + N * J;                                 // src/GibbsRtIrtCross.pl.jl:65
-            case ERM_MODEL_LATENTQR: return F + 2 + 4 + N;                                // src/GibbsRtIrtLatent.pl.jl:60
-            case ERM_MODEL_NULL: return 2 * (F + 1) + 4;                                  // OutputPost, src/GibbsRtIrt.pl.jl:67
-            case ERM_MODEL_CROSS: return J + 4;                                           // OutputPostCross, src/GibbsRtIrtCross.pl.jl:46
-            case ERM_MODEL_LATENT: return F + 2 + 4;                                      // OutputPostRtIrtLatent, src/GibbsRtIrtLatent.pl.jl:43
-            }
-            return 0;
-        case ERM_TRACE_LOGLIKE: return 1;
-        }
-        return 0;
-    }
-    int nq() const {
-        switch (cfg.model) {
-        case ERM_MODEL_MLIRT: return cfg.n_feat + 1;
-        case ERM_MODEL_RTIRT: return 2 * (cfg.n_feat + 1) + 4;
-        case ERM_MODEL_CROSSQR: case ERM_MODEL_CROSS: return cfg.n_item + 4;
-        case ERM_MODEL_NULL: return 2 + 4;            // the kernels see no covariates: [beta_theta0, beta_zeta0] = 0, then Sigp
-        default: return cfg.n_feat + 2 + 4;
-        }
-    }
-    int64_t item_trace_width() const { return 4 * (int64_t)cfg.n_item + nq(); }
+    // the per-model facts and every width that follows from them: one table (erm_model.hpp)
+    ModelTraits mt() const { return model_traits(cfg.model); }
+    int64_t trace_width(int which) const { return erm::trace_width(cfg.model, which, cfg.n_subj, cfg.n_item, cfg.n_feat); }
+    int nq() const { return erm::nq(cfg.model, cfg.n_item, cfg.n_feat); }
+    int nbeta() const { return erm::nbeta(cfg.model, cfg.n_feat); }
+    int64_t nu_len() const { return erm::nu_len(cfg.model, cfg.n_subj, cfg.n_item); }
+    int64_t item_trace_width() const { return erm::item_trace_width(cfg.model, cfg.n_item, cfg.n_feat); }
 };
 
 template <typename real> struct Engine : EngineBase {
@@ -262,11 +240,15 @@ template <typename real> struct Engine : EngineBase {
         if (stream) (void)hipStreamDestroy(stream);
     }
 
-    bool is_rt() const { return cfg.model != ERM_MODEL_MLIRT; }
-    bool m_cq() const { return fam_cq(cfg.model); }
-    bool m_nu() const { return has_nu(cfg.model); }
+    bool is_rt() const { return mt().rt; }
+    bool m_cq() const { return mt().rho; }                // the cross-relation models: two row passes per sweep
+    bool m_nu() const { return mt().nu != NU_NONE; }
     int p() const { return Fk + 1; }
-    // calls f(std::integral_constant<int, MODEL>) for the configured model
+    // calls f(std::integral_constant<int, MODEL>) for the configured model: with the range check in init() the one place that names the models (the rest
+    // reads erm_model.hpp's table, which is indexed by erm::Model -- the same numbers, as is asserted here)
+    static_assert(MLIRT == ERM_MODEL_MLIRT && RTIRT == ERM_MODEL_RTIRT && CROSSQR == ERM_MODEL_CROSSQR && LATENTQR == ERM_MODEL_LATENTQR && NULLM == ERM_MODEL_NULL &&
+                  CROSS == ERM_MODEL_CROSS && LATENT == ERM_MODEL_LATENT, "erm::Model and ERM_MODEL_* number the models differently");
+    static_assert(TRACE_RA == ERM_TRACE_RA && TRACE_RT == ERM_TRACE_RT && TRACE_QR == ERM_TRACE_QR && TRACE_LOGLIKE == ERM_TRACE_LOGLIKE, "erm::Trace and ERM_TRACE_* differ");
     template <typename Fn> int dispatch(Fn&& f) {
         switch (cfg.model) {
         case ERM_MODEL_MLIRT: return f(std::integral_constant<int, MLIRT>{});
@@ -281,7 +263,7 @@ template <typename real> struct Engine : EngineBase {
     }
     // LatentQr with sigp_mode 1 also accumulates the 1/nu-weighted Gram entries of [1 X theta | u]
     int ngx() const {
-        if (cfg.model != ERM_MODEL_LATENTQR || cfg.sigp_mode != 1) return 0;
+        if (mt().nu != NU_SUBJECT || cfg.sigp_mode != 1) return 0;      // (one weight per subject: of the seven models that is LatentQr alone)
         const int q = p() + 1;
         return q * (q + 1) / 2 + q + 1;
     }
@@ -289,7 +271,7 @@ template <typename real> struct Engine : EngineBase {
 
     int init() override {
         N = cfg.n_subj; J = cfg.n_item; F = cfg.n_feat;
-        Fk = (m_cq() || cfg.model == ERM_MODEL_NULL) ? 0 : F;     // the Cross family and Null never touch Data.X
+        Fk = kernel_feat(cfg.model, F);
         if (N <= 0 || J <= 0 || F < 0) return fail(ERM_ERR_ARG, "n_subj, n_item must be positive and n_feat non-negative");
         if (N >= (1LL << 32)) return fail(ERM_ERR_ARG, "n_subj must fit 32 bits");
         if (cfg.model < 0 || cfg.model > ERM_MODEL_LATENT) return fail(ERM_ERR_ARG, "unknown model");
@@ -339,8 +321,7 @@ template <typename real> struct Engine : EngineBase {
         rc |= dY.alloc(NJ);
         rc |= dOmega.alloc(NJ * sizeof(real));
         if (is_rt()) rc |= dC.alloc(NJ * sizeof(real));
-        if (cfg.model == ERM_MODEL_CROSSQR) rc |= dNu.alloc(NJ * sizeof(real));
-        if (cfg.model == ERM_MODEL_LATENTQR) rc |= dNu.alloc((size_t)N * sizeof(real));
+        rc |= dNu.alloc((size_t)nu_len() * sizeof(real));
         if (Fk > 0) rc |= dX.alloc((size_t)N * Fk * sizeof(real));
         rc |= dTheta.alloc((size_t)N * sizeof(real));
         rc |= dZeta.alloc((size_t)N * sizeof(real));
@@ -359,15 +340,14 @@ template <typename real> struct Engine : EngineBase {
         for (int k = 0; k < 2; ++k) rc |= dCtlB[k].alloc(sizeof(Ctl));
         rc |= dSumTheta.alloc((size_t)N * sizeof(double));
         rc |= dSumZeta.alloc((size_t)N * sizeof(double));
-        if (cfg.model == ERM_MODEL_CROSSQR) rc |= dSumNu.alloc(NJ * sizeof(double));
-        if (cfg.model == ERM_MODEL_LATENTQR) rc |= dSumNu.alloc((size_t)N * sizeof(double));
+        rc |= dSumNu.alloc((size_t)nu_len() * sizeof(double));
         rc |= dTrItem.alloc((size_t)std::max<int64_t>(rows_cap, 1) * item_trace_width() * sizeof(double));
         rc |= dTrLl.alloc((size_t)std::max<int64_t>(rows_cap, 1) * sizeof(double));
         if (cfg.trace_mode == ERM_TRACE_FULL && rows_cap > 0) {
             rc |= dTrTheta.alloc((size_t)rows_cap * N * sizeof(real));
             if (is_rt()) rc |= dTrZeta.alloc((size_t)rows_cap * N * sizeof(real));
-            if (cfg.model == ERM_MODEL_LATENTQR) rc |= dTrNu.alloc((size_t)rows_cap * N * sizeof(real));
-            if (cfg.model == ERM_MODEL_CROSSQR) {
+            if (mt().nu == NU_SUBJECT) rc |= dTrNu.alloc((size_t)rows_cap * N * sizeof(real));
+            if (mt().nu == NU_CELL) {
                 // Post.qr of GibbsRtIrtCrossQr carries vec(nu) (N*J values) per sweep (src/GibbsRtIrtCross.pl.jl:65,296): kept on the device
                 // when it fits the budget (erm_config.nu_trace_max_gb, default 16 GiB), otherwise only nu's running mean is available
                 const double cap_gb = cfg.nu_trace_max_gb > 0.0 ? cfg.nu_trace_max_gb : 16.0;
@@ -632,7 +612,7 @@ template <typename real> struct Engine : EngineBase {
         if constexpr (fam_cq(MODEL)) {
             if (int rc = launch_tiny<MODEL, 1>(0)) return rc;
             // WAIC / predictive checks on GibbsRtIrtCrossQr: pass B overwrites nu_t with nu_{t+1} in the phase that uses it, so nu_t is copied first (a memcpy node inside a graph)
-            if (MODEL == CROSSQR && aux_pass()) HIPCHK(hipMemcpyAsync(dNuSnap.p, dNu.p, dNu.bytes, hipMemcpyDeviceToDevice, stream));
+            if (model_traits(MODEL).nu == NU_CELL && aux_pass()) HIPCHK(hipMemcpyAsync(dNuSnap.p, dNu.p, dNu.bytes, hipMemcpyDeviceToDevice, stream));
             if (int rc = launch_pass<MODEL, 1>(1, timed, true)) return rc;
         }
         return 0;
@@ -643,7 +623,7 @@ template <typename real> struct Engine : EngineBase {
     // the resident cell as every pass behind a sweep reads it (CellArgs, erm_waic_kernels.hpp)
     CellArgs cell_args(int buf) const {
         CellArgs c{};
-        c.Y = dY.as<uint8_t>(); c.C = dC.p; c.nu = cfg.model == ERM_MODEL_CROSSQR ? dNuSnap.p : nullptr; c.theta = dTheta.p; c.zeta = dZeta.p;
+        c.Y = dY.as<uint8_t>(); c.C = dC.p; c.nu = mt().nu == NU_CELL ? dNuSnap.p : nullptr; c.theta = dTheta.p; c.zeta = dZeta.p;
         c.par = dParB[buf].template as<double>(); c.cm = dCst.as<double>() + cst_off_m(J); c.ctl = dCtlB[buf].template as<Ctl>();
         c.N = N; c.J = J; c.logW = pass_log_lanes(J);
         const QuantileConsts k = quantile_consts();
@@ -680,7 +660,7 @@ template <typename real> struct Engine : EngineBase {
         const int prev = sw;
         sw = want;      // what follows is a function of the resulting state (put back if an allocation fails)
         // GibbsRtIrtCrossQr's copy of nu_t: kept iff any pass is on
-        bufs.push_back({&dNuSnap, cfg.model == ERM_MODEL_CROSSQR && aux_pass() ? dNu.bytes : 0, snap_what});
+        bufs.push_back({&dNuSnap, mt().nu == NU_CELL && aux_pass() ? dNu.bytes : 0, snap_what});
         std::vector<DevBuf> staged(bufs.size());
         for (size_t k = 0; k < bufs.size(); ++k) {
             if (bufs[k].bytes == bufs[k].buf->bytes) continue;
@@ -751,7 +731,7 @@ template <typename real> struct Engine : EngineBase {
             if (pw_unit == PW_SUBJECT) { HIPCHK(hipMemcpy(dst, d.p, (size_t)U * sizeof(double), hipMemcpyDeviceToHost)); return 0; }
             std::vector<double> t((size_t)U);      // cells: device order (row-major) -> the caller's column-major [nSubj][nItem]
             HIPCHK(hipMemcpy(t.data(), d.p, t.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) dst[(size_t)j * N + i] = t[(size_t)i * J + j];
+            rows_to_cols(t.data(), dst, N, J);
             return 0;
         };
         if (int rc = down(dL, lppd_u)) return rc;
@@ -895,16 +875,17 @@ template <typename real> struct Engine : EngineBase {
     // there), and the post-burn-in sums.
     template <typename Fn> void snap_each(Fn&& f) const {
         f(dTheta); if (is_rt()) f(dZeta);
-        f(dOmega); if (cfg.model == ERM_MODEL_LATENTQR) f(dNu);
+        f(dOmega); if (mt().nu == NU_SUBJECT) f(dNu);
         f(dParB[0]); f(dGslab0B[0]);
         f(dSumTheta); if (is_rt()) f(dSumZeta); if (dSumNu.p) f(dSumNu);
     }
     size_t snap_bytes() const {
         // (called before the buffers exist: sizes from the configuration and the planned geometry)
         const size_t NJ = (size_t)N * J, r = sizeof(real);
-        size_t b = (size_t)N * r + (is_rt() ? (size_t)N * r : 0) + NJ * r + (cfg.model == ERM_MODEL_LATENTQR ? (size_t)N * r : 0);
+        const size_t nnu = mt().nu == NU_SUBJECT ? (size_t)N : 0;      // (a persistent launch never serves CrossQr: two passes per sweep)
+        size_t b = (size_t)N * r + (is_rt() ? (size_t)N * r : 0) + NJ * r + nnu * r;
         b += (size_t)par_size(J) * 8 + (size_t)std::max(G.n_groups, GROUP) * G.ns[0] * 8;
-        b += (size_t)N * 8 + (is_rt() ? (size_t)N * 8 : 0) + (cfg.model == ERM_MODEL_LATENTQR ? (size_t)N * 8 : 0);
+        b += (size_t)N * 8 + (is_rt() ? (size_t)N * 8 : 0) + nnu * 8;
         return b + 10 * 256;                         // every segment starts on a 256-byte boundary
     }
     int snap_copy(bool restore) {
@@ -1199,16 +1180,9 @@ template <typename real> struct Engine : EngineBase {
         if (!tr || !tr->a || !tr->b) return fail(ERM_ERR_ARG, "truth needs a and b");
         if (is_rt() && (!tr->lambda || !tr->sig2t)) return fail(ERM_ERR_ARG, "truth needs lambda and sig2t for response-time models");
         if (noise < 0 || noise > 2) return fail(ERM_ERR_ARG, "noise must be 0 (norm), 1 (tail) or 2 (skew)");
-        int gen;
-        switch (cfg.model) {
-        case ERM_MODEL_MLIRT: gen = 0; break;
-        case ERM_MODEL_RTIRT: gen = 1; break;
-        case ERM_MODEL_NULL: gen = 2; break;
-        case ERM_MODEL_CROSS: case ERM_MODEL_CROSSQR: gen = 3; break;
-        default: gen = 4;
-        }
-        if ((gen == 0 || gen == 1 || gen == 4) && Fk > 0 && !tr->beta) return fail(ERM_ERR_ARG, "truth needs beta");
-        if (gen == 3 && !tr->rho) return fail(ERM_ERR_ARG, "truth needs rho");
+        const int gen = mt().gen;
+        if ((gen == GEN_MLIRT || gen == GEN_RTIRT || gen == GEN_LATENT) && Fk > 0 && !tr->beta) return fail(ERM_ERR_ARG, "truth needs beta");
+        if (gen == GEN_CROSS && !tr->rho) return fail(ERM_ERR_ARG, "truth needs rho");
         HIPCHK(hipSetDevice(cfg.device));
         HIPCHK(hipStreamSynchronize(stream));
         has_data = false; stats_valid = false;
@@ -1226,9 +1200,9 @@ template <typename real> struct Engine : EngineBase {
         // beta: the generators' truth has no intercept row (src/SimTools.jl:86,107,283): RtIrt [nFeat][2] column-major -> (f, c) at 2f + c
         double* bt = &tv[5 * J + 3];
         if (tr->beta) {
-            if (gen == 1) for (int f = 0; f < Fk; ++f) { bt[2 * f] = tr->beta[f]; bt[2 * f + 1] = tr->beta[Fk + f]; }
-            else if (gen == 0) for (int f = 0; f < Fk; ++f) bt[f] = tr->beta[f];
-            else if (gen == 4) for (int f = 0; f <= Fk; ++f) bt[f] = tr->beta[f];
+            if (gen == GEN_RTIRT) for (int f = 0; f < Fk; ++f) { bt[2 * f] = tr->beta[f]; bt[2 * f + 1] = tr->beta[Fk + f]; }
+            else if (gen == GEN_MLIRT) for (int f = 0; f < Fk; ++f) bt[f] = tr->beta[f];
+            else if (gen == GEN_LATENT) for (int f = 0; f <= Fk; ++f) bt[f] = tr->beta[f];
         }
         DevBuf dT;
         if (int rc = dT.alloc(tv.size() * sizeof(double))) return rc;
@@ -1283,15 +1257,15 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipSetDevice(cfg.device));
         HIPCHK(hipStreamSynchronize(stream));
         const size_t NJ = (size_t)N * J;
-        if (Y) { std::vector<uint8_t> t(NJ); HIPCHK(hipMemcpy(t.data(), dY.p, NJ, hipMemcpyDeviceToHost)); for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) Y[(size_t)j * N + i] = t[(size_t)i * J + j]; }
+        if (Y) { std::vector<uint8_t> t(NJ); HIPCHK(hipMemcpy(t.data(), dY.p, NJ, hipMemcpyDeviceToHost)); rows_to_cols(t.data(), Y, N, J); }
         if (logT && is_rt()) {
             std::vector<double> cst(cst_size(J));
             HIPCHK(hipMemcpy(cst.data(), dCst.p, cst.size() * sizeof(double), hipMemcpyDeviceToHost));
             std::vector<real> t(NJ);
             HIPCHK(hipMemcpy(t.data(), dC.p, NJ * sizeof(real), hipMemcpyDeviceToHost));
-            for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) logT[(size_t)j * N + i] = (double)t[(size_t)i * J + j] + cst[cst_off_m(J) + j];
+            rows_to_cols(t.data(), logT, N, J, [&](real v, int64_t j) { return (double)v + cst[cst_off_m(J) + j]; });
         }
-        if (X && Fk > 0) { std::vector<real> t((size_t)N * Fk); HIPCHK(hipMemcpy(t.data(), dX.p, t.size() * sizeof(real), hipMemcpyDeviceToHost)); for (int f = 0; f < Fk; ++f) for (int64_t i = 0; i < N; ++i) X[(size_t)f * N + i] = (double)t[(size_t)i * Fk + f]; }
+        if (X && Fk > 0) { std::vector<real> t((size_t)N * Fk); HIPCHK(hipMemcpy(t.data(), dX.p, t.size() * sizeof(real), hipMemcpyDeviceToHost)); rows_to_cols(t.data(), X, N, Fk); }
         return 0;
     }
     int get_truth(double* theta, double* zeta) override {
@@ -1301,16 +1275,6 @@ template <typename real> struct Engine : EngineBase {
         if (theta) HIPCHK(hipMemcpy(theta, dTruthTheta.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
         if (zeta) HIPCHK(hipMemcpy(zeta, dTruthZeta.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
         return 0;
-    }
-
-    int nbeta() const {
-        switch (cfg.model) {
-        case ERM_MODEL_MLIRT: return F + 1;
-        case ERM_MODEL_RTIRT: return 2 * (F + 1);
-        case ERM_MODEL_LATENTQR: case ERM_MODEL_LATENT: return F + 2;
-        case ERM_MODEL_NULL: return 2 * (F + 1);          // always zero (src/GibbsRtIrt.pl.jl:380)
-        default: return 0;
-        }
     }
 
     int up_real(DevBuf& d, const double* src, size_t n) {
@@ -1343,22 +1307,18 @@ template <typename real> struct Engine : EngineBase {
         if (st->beta) {
             double* b = &par[par_off_beta(J)];
             const int pp = F + 1;
-            if (cfg.model == ERM_MODEL_RTIRT) { for (int u = 0; u < pp; ++u) { b[u] = st->beta[u]; b[PMAX + u] = st->beta[pp + u]; } }
-            else if (cfg.model != ERM_MODEL_NULL) for (int u = 0; u < nbeta(); ++u) b[u] = st->beta[u];
+            if (mt().beta == BETA_PAIR) { for (int u = 0; u < pp; ++u) { b[u] = st->beta[u]; b[PMAX + u] = st->beta[pp + u]; } }
+            else if (mt().beta != BETA_ZERO_PAIR) for (int u = 0; u < nbeta(); ++u) b[u] = st->beta[u];
         }
         { double t = 0.0; for (int j = 0; j < J; ++j) t += 1.0 / par[3 * J + j]; par[par_off_derived(J)] = t; }
         H2D(dParB[cur].p, par.data(), par.size() * sizeof(double));
         if (st->theta) if (int rc = up_real(dTheta, st->theta, N)) return rc;
         if (st->zeta) if (int rc = up_real(dZeta, st->zeta, N)) return rc;
         if (st->nu && dNu.p) {
-            if (cfg.model == ERM_MODEL_LATENTQR) { if (int rc = up_real(dNu, st->nu, N)) return rc; }
+            if (mt().nu == NU_SUBJECT) { if (int rc = up_real(dNu, st->nu, N)) return rc; }
             else {
                 std::vector<real> t((size_t)N * J);
-                for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) {
-                    const double v = st->nu[(size_t)j * N + i];
-                    if (!(v > 0.0)) return fail(ERM_ERR_ARG, "nu must be positive");   // @assert src/Draw.pl.jl:477
-                    t[(size_t)i * J + j] = (real)v;
-                }
+                if (!cols_to_rows(st->nu, t.data(), N, J, AsIs(), [](double v) { return v > 0.0; })) return fail(ERM_ERR_ARG, "nu must be positive");   // @assert src/Draw.pl.jl:477
                 H2D(dNu.p, t.data(), t.size() * sizeof(real));
             }
         }
@@ -1381,18 +1341,18 @@ template <typename real> struct Engine : EngineBase {
         if (st->beta) {
             const double* b = &par[par_off_beta(J)];
             const int pp = F + 1;
-            if (cfg.model == ERM_MODEL_RTIRT) { for (int u = 0; u < pp; ++u) { st->beta[u] = b[u]; st->beta[pp + u] = b[PMAX + u]; } }
-            else if (cfg.model == ERM_MODEL_NULL) for (int u = 0; u < nbeta(); ++u) st->beta[u] = 0.0;
+            if (mt().beta == BETA_PAIR) { for (int u = 0; u < pp; ++u) { st->beta[u] = b[u]; st->beta[pp + u] = b[PMAX + u]; } }
+            else if (mt().beta == BETA_ZERO_PAIR) for (int u = 0; u < nbeta(); ++u) st->beta[u] = 0.0;
             else for (int u = 0; u < nbeta(); ++u) st->beta[u] = b[u];
         }
         if (st->theta) if (int rc = down_real(dTheta, st->theta, N)) return rc;
         if (st->zeta) if (int rc = down_real(dZeta, st->zeta, N)) return rc;
         if (st->nu && dNu.p) {
-            if (cfg.model == ERM_MODEL_LATENTQR) { if (int rc = down_real(dNu, st->nu, N)) return rc; }
+            if (mt().nu == NU_SUBJECT) { if (int rc = down_real(dNu, st->nu, N)) return rc; }
             else {
                 std::vector<real> t((size_t)N * J);
                 HIPCHK(hipMemcpy(t.data(), dNu.p, t.size() * sizeof(real), hipMemcpyDeviceToHost));
-                for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) st->nu[(size_t)j * N + i] = (double)t[(size_t)i * J + j];
+                rows_to_cols(t.data(), st->nu, N, J);
             }
         }
         return 0;
@@ -1426,7 +1386,7 @@ template <typename real> struct Engine : EngineBase {
             return 0;
         }
         if (cfg.trace_mode != ERM_TRACE_FULL) return fail(ERM_ERR_NOTRACE, "subject-level traces need trace_mode = ERM_TRACE_FULL");
-        if (which == ERM_TRACE_QR && cfg.model == ERM_MODEL_CROSSQR && !dTrNu.p)
+        if (which == ERM_TRACE_QR && mt().nu == NU_CELL && !dTrNu.p)
             return fail(ERM_ERR_NOTRACE, "the per-sweep nu trace (N*J values per sweep) exceeds erm_config.nu_trace_max_gb; use erm_get_item_trace (rho, Sigp) + erm_get_mean (nu)");
         std::vector<double> it;
         if (int rc = fetch_item_trace(it)) return rc;
@@ -1465,18 +1425,18 @@ template <typename real> struct Engine : EngineBase {
             for (int64_t r = 0; r < rows_cap; ++r) for (int j = 0; j < J; ++j) { at(r, N + j) = it[r * wi + 2 * J + j]; at(r, N + J + j) = it[r * wi + 3 * J + j]; }
         } else {                                 // qr  :241,319 ; Latent :308
             const int q = nq();
-            if (cfg.model == ERM_MODEL_NULL) {          // [vec(beta) = 0 (2(nFeat+1)); vec(Sigp)]  src/GibbsRtIrt.pl.jl:398
-                const int nb = 2 * ((int)F + 1);
-                for (int64_t r = 0; r < rows_cap; ++r) { for (int k = 0; k < nb; ++k) at(r, k) = 0.0; for (int k = 0; k < 4; ++k) at(r, nb + k) = it[r * wi + 4 * J + 2 + k]; }
+            if (mt().beta == BETA_ZERO_PAIR) {          // [vec(beta) = 0 (2(nFeat+1)); vec(Sigp)]  src/GibbsRtIrt.pl.jl:398
+                const int nb = nbeta(), so = qr_sigp_off(cfg.model, J, F);
+                for (int64_t r = 0; r < rows_cap; ++r) { for (int k = 0; k < nb; ++k) at(r, k) = 0.0; for (int k = 0; k < 4; ++k) at(r, nb + k) = it[r * wi + 4 * J + so + k]; }
                 return 0;
             }
             for (int64_t r = 0; r < rows_cap; ++r) for (int k = 0; k < q; ++k) at(r, k) = it[r * wi + 4 * J + k];
-            if (cfg.model == ERM_MODEL_LATENTQR) if (int rc = subj(dTrNu, q)) return rc;
-            if (cfg.model == ERM_MODEL_CROSSQR) {       // vec(nu): column-major N x J after [rho; vec(Sigp)]
+            if (mt().nu == NU_SUBJECT) if (int rc = subj(dTrNu, q)) return rc;
+            if (mt().nu == NU_CELL) {                   // vec(nu): column-major N x J after [rho; vec(Sigp)]
                 std::vector<real> cells((size_t)N * J);
                 for (int64_t r = 0; r < rows_cap; ++r) {
                     HIPCHK(hipMemcpy(cells.data(), dTrNu.as<real>() + (size_t)r * N * J, cells.size() * sizeof(real), hipMemcpyDeviceToHost));
-                    for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) at(r, q + i + N * j) = (double)cells[(size_t)i * J + j];
+                    rows_to_cols(cells.data(), &at(r, q), N, J, AsIs(), nIter);
                 }
             }
         }
@@ -1517,17 +1477,17 @@ template <typename real> struct Engine : EngineBase {
         } else if (which == ERM_TRACE_RT) {     // [zeta; lambda; sig2t]
             if (int rc = launch_real(dTrZeta, N, 0)) return rc;
             if (int rc = launch_item(2 * J, 2 * J, N)) return rc;
-        } else if (cfg.model == ERM_MODEL_NULL) {   // [vec(beta) = 0; vec(Sigp)]: the zeros are constant -> NaN
-            const int nb = 2 * ((int)F + 1);
+        } else if (mt().beta == BETA_ZERO_PAIR) {   // [vec(beta) = 0; vec(Sigp)]: the zeros are constant -> NaN
+            const int nb = nbeta();
             std::vector<double> nanv(nb, std::nan(""));
             HIPCHK(hipMemcpyAsync(dE.p, nanv.data(), nb * sizeof(double), hipMemcpyHostToDevice, stream));
             HIPCHK(hipMemcpyAsync(dR.p, nanv.data(), nb * sizeof(double), hipMemcpyHostToDevice, stream));
             HIPCHK(hipStreamSynchronize(stream));
-            if (int rc = launch_item(4 * J + 2, 4, nb)) return rc;
+            if (int rc = launch_item(4 * J + qr_sigp_off(cfg.model, J, F), 4, nb)) return rc;
         } else {
             if (int rc = launch_item(4 * J, q, 0)) return rc;
-            if (cfg.model == ERM_MODEL_LATENTQR) { if (int rc = launch_real(dTrNu, N, q)) return rc; }
-            if (cfg.model == ERM_MODEL_CROSSQR) {
+            if (mt().nu == NU_SUBJECT) { if (int rc = launch_real(dTrNu, N, q)) return rc; }
+            if (mt().nu == NU_CELL) {
                 if (!dTrNu.p) return fail(ERM_ERR_NOTRACE, "the per-sweep nu trace was not recorded (erm_config.nu_trace_max_gb)");
                 if (int rc = launch_real(dTrNu, (int64_t)N * J, q)) return rc;
                 *nu_block = true;
@@ -1548,14 +1508,15 @@ template <typename real> struct Engine : EngineBase {
         if (nu_block) {      // device order (row-major N x J) -> Julia's vec(nu) (column-major)
             const int q = nq();
             std::vector<double> he(ess + q, ess + wd), hr(rhat + q, rhat + wd);
-            for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) { ess[q + i + N * j] = he[(size_t)i * J + j]; rhat[q + i + N * j] = hr[(size_t)i * J + j]; }
+            rows_to_cols(he.data(), ess + q, N, J);
+            rows_to_cols(hr.data(), rhat + q, N, J);
         }
         return 0;
     }
     // checkConvergence's summary (src/SimTools.jl:419-443) without the N-wide vectors: counts of the columns with a defined ESS / R-hat and of those with
     // ESS > 400 / R-hat < 1.1 (the reference's thresholds), counted on the device
     int get_convergence(int which, int64_t* c4) override {
-        DevBuf dE, dR, dC;
+        DevBuf dE, dR;
         bool nu_block = false;
         if (int rc = diag_device(which, dE, dR, &nu_block)) return rc;
         return count_converged(dE, dR, trace_width(which), stream, c4);
@@ -1576,14 +1537,11 @@ template <typename real> struct Engine : EngineBase {
         if (out->b) memcpy(out->b, &m[J], J * sizeof(double));
         if (out->lambda) memcpy(out->lambda, &m[2 * J], J * sizeof(double));
         if (out->sig2t) memcpy(out->sig2t, &m[3 * J], J * sizeof(double));
-        const double* q = &m[4 * J];
-        switch (cfg.model) {
-        case ERM_MODEL_MLIRT: if (out->beta) memcpy(out->beta, q, (F + 1) * sizeof(double)); break;
-        case ERM_MODEL_RTIRT: if (out->beta) memcpy(out->beta, q, 2 * (F + 1) * sizeof(double)); if (out->sigp) memcpy(out->sigp, q + 2 * (F + 1), 4 * sizeof(double)); break;
-        case ERM_MODEL_CROSSQR: case ERM_MODEL_CROSS: if (out->rho) memcpy(out->rho, q, J * sizeof(double)); if (out->sigp) memcpy(out->sigp, q + J, 4 * sizeof(double)); break;
-        case ERM_MODEL_NULL: if (out->beta) memset(out->beta, 0, 2 * (F + 1) * sizeof(double)); if (out->sigp) memcpy(out->sigp, q + 2, 4 * sizeof(double)); break;
-        default: if (out->beta) memcpy(out->beta, q, (F + 2) * sizeof(double)); if (out->sigp) memcpy(out->sigp, q + F + 2, 4 * sizeof(double));
-        }
+        const double* q = &m[4 * J];                  // the kernels' small part of qr: [beta or rho | Sigp at qr_sigp_off]
+        if (out->beta && mt().beta == BETA_ZERO_PAIR) memset(out->beta, 0, nbeta() * sizeof(double));
+        else if (out->beta) memcpy(out->beta, q, nbeta() * sizeof(double));
+        if (out->rho && mt().rho) memcpy(out->rho, q, J * sizeof(double));
+        if (out->sigp && is_rt()) memcpy(out->sigp, q + qr_sigp_off(cfg.model, J, F), 4 * sizeof(double));
     }
     int get_mean(erm_state* out) override {
         if (!out) return fail(ERM_ERR_ARG, "state is NULL");
@@ -1595,15 +1553,12 @@ template <typename real> struct Engine : EngineBase {
             std::vector<double> t(n);
             HIPCHK(hipMemcpy(t.data(), d.p, n * sizeof(double), hipMemcpyDeviceToHost));
             if (!transpose) for (size_t k = 0; k < n; ++k) dst[k] = t[k] * inv;
-            else for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) dst[(size_t)j * N + i] = t[(size_t)i * J + j] * inv;
+            else rows_to_cols(t.data(), dst, N, J, [&](double v, int64_t) { return v * inv; });
             return 0;
         };
         if (out->theta) if (int rc = subj(dSumTheta, out->theta, N, false)) return rc;
         if (out->zeta && is_rt()) if (int rc = subj(dSumZeta, out->zeta, N, false)) return rc;
-        if (out->nu && dSumNu.p) {
-            if (cfg.model == ERM_MODEL_LATENTQR) { if (int rc = subj(dSumNu, out->nu, N, false)) return rc; }
-            else if (int rc = subj(dSumNu, out->nu, (size_t)N * J, true)) return rc;
-        }
+        if (out->nu && dSumNu.p) if (int rc = subj(dSumNu, out->nu, (size_t)nu_len(), mt().nu == NU_CELL)) return rc;
         std::vector<double> m;
         if (int rc = item_sums(m)) return rc;
         for (auto& v : m) v *= inv;
@@ -1612,8 +1567,8 @@ template <typename real> struct Engine : EngineBase {
     }
 
     // ---- chain farms: [item sums (wi) | sum theta (N) | sum zeta (N, response-time models) | sum nu (N or N*J, quantile models)]
-    int64_t nu_len() const { return cfg.model == ERM_MODEL_LATENTQR ? N : (cfg.model == ERM_MODEL_CROSSQR ? N * (int64_t)J : 0); }
-    int64_t summary_len() const override { return item_trace_width() + N + (is_rt() ? N : 0) + nu_len(); }
+    SummaryLayout summary() const { return summary_layout(cfg.model, N, J, F); }
+    int64_t summary_len() const override { return summary().len; }
     int summary_add(double* acc) override {
         HIPCHK(hipSetDevice(cfg.device));
         auto add = [&](double* dst, const double* src, int64_t n) {
@@ -1622,10 +1577,10 @@ template <typename real> struct Engine : EngineBase {
         // item-level columns: summed over the post-burn-in rows of the resident item trace ON the device, in row order (the order erm_get_mean's host sum uses)
         const int64_t wi = item_trace_width(), burn = (int64_t)cfg.n_burnin * cfg.n_chain;
         hipLaunchKernelGGL(item_sum_kernel, dim3((unsigned)((wi + 255) / 256)), dim3(256), 0, stream, dTrItem.as<double>(), (long long)wi, (long long)std::min(burn, rows_done), (long long)rows_done, acc);
-        int64_t o = wi;
-        add(acc + o, dSumTheta.as<double>(), N); o += N;
-        if (is_rt()) { add(acc + o, dSumZeta.as<double>(), N); o += N; }
-        if (nu_len() > 0) add(acc + o, dSumNu.as<double>(), nu_len());
+        const SummaryLayout L = summary();
+        add(acc + L.theta, dSumTheta.as<double>(), N);
+        if (L.zeta >= 0) add(acc + L.zeta, dSumZeta.as<double>(), N);
+        if (L.nu >= 0) add(acc + L.nu, dSumNu.as<double>(), nu_len());
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
@@ -1641,8 +1596,8 @@ template <typename real> struct Engine : EngineBase {
         LogLikArgs D{};
         D.Y = dY.as<uint8_t>(); D.C = dC.p; D.X = dX.p; D.cm = dCst.as<double>() + cst_off_m(J);
         D.sum = dsum; D.inv = inv; D.N = N; D.J = J; D.F = Fk; D.model = cfg.model;
-        const int64_t wi = item_trace_width();
-        D.off_theta = wi; D.off_zeta = is_rt() ? wi + N : -1; D.off_nu = nu_len() > 0 ? wi + N + (is_rt() ? N : 0) : -1;
+        const SummaryLayout L = summary();
+        D.off_theta = L.theta; D.off_zeta = L.zeta; D.off_nu = L.nu;
         const QuantileConsts k = quantile_consts();
         D.k1 = k.k1; D.k2 = k.k2;
         D.rows_per_block = (N + nb - 1) / nb; D.part = dPart.as<double>();
@@ -1693,13 +1648,12 @@ template <typename real> struct Engine : EngineBase {
     }
     int summary_unpack(const double* mean, erm_state* out) const override {
         unpack_items(mean, out);
-        int64_t o = item_trace_width();
-        if (out->theta) memcpy(out->theta, mean + o, N * sizeof(double));
-        o += N;
-        if (is_rt()) { if (out->zeta) memcpy(out->zeta, mean + o, N * sizeof(double)); o += N; }
-        if (out->nu && nu_len() > 0) {
-            if (cfg.model == ERM_MODEL_LATENTQR) memcpy(out->nu, mean + o, N * sizeof(double));
-            else for (int j = 0; j < J; ++j) for (int64_t i = 0; i < N; ++i) out->nu[(size_t)j * N + i] = mean[o + (size_t)i * J + j];     // device row-major -> column-major
+        const SummaryLayout L = summary();
+        if (out->theta) memcpy(out->theta, mean + L.theta, N * sizeof(double));
+        if (out->zeta && L.zeta >= 0) memcpy(out->zeta, mean + L.zeta, N * sizeof(double));
+        if (out->nu && L.nu >= 0) {
+            if (mt().nu == NU_SUBJECT) memcpy(out->nu, mean + L.nu, N * sizeof(double));
+            else rows_to_cols(mean + L.nu, out->nu, N, J);
         }
         return 0;
     }

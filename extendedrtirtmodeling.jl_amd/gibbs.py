@@ -80,9 +80,24 @@ class _GibbsBase:
             if np.size(v) == ntot:
                 setattr(self.Para, f, np.ascontiguousarray(np.asarray(v)[base:base + local.nSubj]))
 
-    # -- per-model hooks
+    @property
+    def _traits(self):
+        return _lib.MODEL_TRAITS[self._model]
+
     def setInitialValues(self):
-        raise NotImplementedError
+        """The constructors' initial values (setInitialValues of src/GibbsRtIrt.pl.jl:84,122,159; src/GibbsRtIrtCross.pl.jl:85,123;
+        src/GibbsRtIrtLatent.pl.jl:78,113), from the sampler's own stream.  The draws come in this order: theta, zeta if the model has response
+        times, then beta or rho."""
+        C, g, t = self.Cond, self._rng(), self._traits
+        init = dict(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem))
+        if t.rt:
+            init.update(zeta=g.standard_normal(C.nSubj), lam=np.zeros(C.nItem), sig2t=np.ones(C.nItem), Sigp=np.eye(2))
+        if t.beta in ("vec", "pair", "latent"):
+            init["beta"] = g.standard_normal(_lib.beta_shape(self._model, C.nFeat))
+        if t.rho:
+            init["rho"] = g.standard_normal(C.nItem)
+        self.Para = InputPara(**init)
+        return self
 
     def _rng(self):
         return np.random.default_rng(np.random.SeedSequence([self.seed, self.chain_id, 0x1217]))
@@ -90,13 +105,13 @@ class _GibbsBase:
     def _state_for_engine(self):
         P = self.Para
         d = dict(theta=P.theta, a=P.a, b=P.b)
-        if self._model != _lib.MODEL_MLIRT:
+        if self._traits.rt:
             d.update(zeta=P.zeta, lambda_=P.lam, sig2t=P.sig2t, sigp=np.asarray(P.Sigp, dtype=np.float64).reshape(-1, order="F"))
         if P.beta.size:
             d["beta"] = np.asarray(P.beta, dtype=np.float64).reshape(-1, order="F")
         if P.rho.size:
             d["rho"] = P.rho
-        if P.nu.size and self._model in (_lib.MODEL_CROSSQR, _lib.MODEL_LATENTQR):
+        if P.nu.size and self._traits.nu != "none":
             d["nu"] = np.asarray(P.nu, dtype=np.float64).reshape(-1, order="F")
         return d
 
@@ -133,12 +148,12 @@ class _GibbsBase:
         if Y.shape != (C.nSubj, C.nItem):
             raise ValueError(f"Data.Y must be {C.nSubj}x{C.nItem}, got {Y.shape}")
         logT = None
-        if self._model != _lib.MODEL_MLIRT:
+        if self._traits.rt:
             logT = np.asarray(D.logT, dtype=np.float64)
             if logT.shape != (C.nSubj, C.nItem):
                 raise ValueError(f"Data.logT must be {C.nSubj}x{C.nItem}, got {logT.shape}")
         X = None
-        if self._model not in (_lib.MODEL_CROSSQR, _lib.MODEL_CROSS, _lib.MODEL_NULL) and C.nFeat > 0:
+        if self._traits.sees_x and C.nFeat > 0:
             X = np.asarray(D.X, dtype=np.float64)
             if X.shape != (C.nSubj, C.nFeat):
                 raise ValueError(f"Data.X must be {C.nSubj}x{C.nFeat}, got {X.shape}")
@@ -153,12 +168,12 @@ class _GibbsBase:
         Post.logLike = eng.trace(_lib.TRACE_LOGLIKE)
         if full:
             Post.ra = eng.trace(_lib.TRACE_RA)
-            if self._model != _lib.MODEL_MLIRT:
+            if self._traits.rt:
                 Post.rt = eng.trace(_lib.TRACE_RT)
             try:
                 Post.qr = eng.trace(_lib.TRACE_QR)
             except _lib.ErmError:
-                if self._model != _lib.MODEL_CROSSQR:
+                if self._traits.nu != "cell":
                     raise
                 # vec(nu) per sweep did not fit the device budget: Post.qr keeps [rho; vec(Sigp)] (the reference's first nItem+4 columns)
                 it = eng.item_trace()
@@ -166,12 +181,12 @@ class _GibbsBase:
         Post.item_trace = eng.item_trace()
         m = eng.get_mean()
         mean = InputPara(theta=m["theta"], a=m["a"], b=m["b"])
-        if self._model != _lib.MODEL_MLIRT:
+        if self._traits.rt:
             mean.zeta, mean.lam, mean.sig2t = m["zeta"], m["lambda_"], m["sig2t"]
             mean.Sigp = m["sigp"]
         if m["beta"] is not None:
             mean.beta = m["beta"]
-        if self._model in (_lib.MODEL_CROSSQR, _lib.MODEL_CROSS):
+        if self._traits.rho:
             mean.rho = m["rho"]
         if m["nu"] is not None:
             mean.nu = m["nu"]
@@ -181,17 +196,18 @@ class _GibbsBase:
         s = eng.get_state()
         C = self.Cond
         P = self.Para
+        t = self._traits
         P.theta, P.a, P.b = s["theta"], s["a"], s["b"]
-        if self._model != _lib.MODEL_MLIRT:
+        if t.rt:
             P.zeta, P.lam, P.sig2t = s["zeta"], s["lambda_"], s["sig2t"]
             P.Sigp = s["sigp"].reshape(2, 2, order="F")
         if s["beta"] is not None:
-            P.beta = s["beta"].reshape(C.nFeat + 1, 2, order="F") if self._model in (_lib.MODEL_RTIRT, _lib.MODEL_NULL) else s["beta"]
-        if self._model in (_lib.MODEL_CROSSQR, _lib.MODEL_CROSS):
+            P.beta = s["beta"].reshape(_lib.beta_shape(self._model, C.nFeat), order="F")
+        if t.rho:
             P.rho = s["rho"]
-        if self._model == _lib.MODEL_CROSSQR:
+        if t.nu == "cell":
             P.nu = s["nu"].reshape(C.nSubj, C.nItem, order="F")
-        if self._model == _lib.MODEL_LATENTQR:
+        if t.nu == "subject":
             P.nu = s["nu"]
 
     def timing(self):
@@ -215,7 +231,7 @@ def simulateData(MCMC: _GibbsBase, truePara: InputPara, *, type="norm", seed=432
     eng = MCMC._engine_for(intercept, itemtype == "1pl", MCMC._cov2one_default if cov2one is None else cov2one, upload=False)
     noise = {"norm": 0, "tail": 1, "skew": 2}[type]
     truth = dict(a=truePara.a, b=truePara.b)
-    if MCMC._model != _lib.MODEL_MLIRT:
+    if MCMC._traits.rt:
         truth.update(lambda_=truePara.lam, sig2t=truePara.sig2t if truePara.sig2t.size else np.ones(MCMC.Cond.nItem))
         if np.size(truePara.Sigp):
             truth["sigp"] = np.asarray(truePara.Sigp, dtype=np.float64).reshape(-1, order="F")
@@ -250,9 +266,9 @@ def _sample_farm(MCMC: _GibbsBase, intercept, onepl, cov2one, devices):
                      intercept=int(intercept), one_pl=int(onepl), cov2one=int(cov2one), q_rt=C.qRt, seed=MCMC.seed, precision=_PREC[MCMC.precision],
                      trace_mode=_TRACE[MCMC.trace], **MCMC.engine_opts)
     D = MCMC.Data
-    logT = None if MCMC._model == _lib.MODEL_MLIRT else np.asarray(D.logT, dtype=np.float64)
+    logT = np.asarray(D.logT, dtype=np.float64) if MCMC._traits.rt else None
     X = None
-    if MCMC._model not in (_lib.MODEL_CROSSQR, _lib.MODEL_CROSS, _lib.MODEL_NULL) and C.nFeat > 0:
+    if MCMC._traits.sees_x and C.nFeat > 0:
         X = np.asarray(D.X, dtype=np.float64)
     farm.set_data(np.asarray(D.Y), logT, X)
     for l in range(C.nChain):
@@ -325,23 +341,10 @@ class GibbsMlIrt(_GibbsBase):
     :85-91, :228; its likelihood uses Normal(mu, 1.) :201)."""
     _model = _lib.MODEL_MLIRT
 
-    def setInitialValues(self):
-        C, g = self.Cond, self._rng()
-        self.Para = InputPara(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem),
-                              beta=g.standard_normal(C.nFeat + 1))
-        return self
-
 
 class GibbsRtIrt(_GibbsBase):
     """src/GibbsRtIrt.pl.jl:114-146"""
     _model = _lib.MODEL_RTIRT
-
-    def setInitialValues(self):
-        C, g = self.Cond, self._rng()
-        self.Para = InputPara(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem),
-                              zeta=g.standard_normal(C.nSubj), lam=np.zeros(C.nItem), sig2t=np.ones(C.nItem),
-                              beta=g.standard_normal((C.nFeat + 1, 2)), Sigp=np.eye(2))
-        return self
 
 
 class GibbsRtIrtCrossQr(_GibbsBase):
@@ -349,25 +352,11 @@ class GibbsRtIrtCrossQr(_GibbsBase):
     _model = _lib.MODEL_CROSSQR
     _has_intercept = False
 
-    def setInitialValues(self):
-        C, g = self.Cond, self._rng()
-        self.Para = InputPara(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem),
-                              zeta=g.standard_normal(C.nSubj), lam=np.zeros(C.nItem), sig2t=np.ones(C.nItem),
-                              rho=g.standard_normal(C.nItem), Sigp=np.eye(2))
-        return self
-
 
 class GibbsRtIrtLatentQr(_GibbsBase):
     """src/GibbsRtIrtLatent.pl.jl:105-137 (sample! default cov2one = false, :271)"""
     _model = _lib.MODEL_LATENTQR
     _cov2one_default = False
-
-    def setInitialValues(self):
-        C, g = self.Cond, self._rng()
-        self.Para = InputPara(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem),
-                              zeta=g.standard_normal(C.nSubj), lam=np.zeros(C.nItem), sig2t=np.ones(C.nItem),
-                              beta=g.standard_normal(C.nFeat + 2), Sigp=np.eye(2))
-        return self
 
 
 class GibbsRtIrtNull(_GibbsBase):
@@ -375,37 +364,17 @@ class GibbsRtIrtNull(_GibbsBase):
     _model = _lib.MODEL_NULL
     _has_intercept = False
 
-    def setInitialValues(self):
-        C, g = self.Cond, self._rng()
-        self.Para = InputPara(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem),
-                              zeta=g.standard_normal(C.nSubj), lam=np.zeros(C.nItem), sig2t=np.ones(C.nItem), Sigp=np.eye(2))
-        return self
-
 
 class GibbsRtIrtCross(_GibbsBase):
     """src/GibbsRtIrtCross.pl.jl:77-110: cross-relation rho without quantile weights."""
     _model = _lib.MODEL_CROSS
     _has_intercept = False
 
-    def setInitialValues(self):
-        C, g = self.Cond, self._rng()
-        self.Para = InputPara(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem),
-                              zeta=g.standard_normal(C.nSubj), lam=np.zeros(C.nItem), sig2t=np.ones(C.nItem),
-                              rho=g.standard_normal(C.nItem), Sigp=np.eye(2))
-        return self
-
 
 class GibbsRtIrtLatent(_GibbsBase):
     """src/GibbsRtIrtLatent.pl.jl:70-102 (sample! default cov2one = false, :168): zeta regressed on [1 X theta], beta drawn."""
     _model = _lib.MODEL_LATENT
     _cov2one_default = False
-
-    def setInitialValues(self):
-        C, g = self.Cond, self._rng()
-        self.Para = InputPara(theta=g.standard_normal(C.nSubj), a=np.ones(C.nItem), b=np.zeros(C.nItem),
-                              zeta=g.standard_normal(C.nSubj), lam=np.zeros(C.nItem), sig2t=np.ones(C.nItem),
-                              beta=g.standard_normal(C.nFeat + 2), Sigp=np.eye(2))
-        return self
 
 
 # README.md:22,95 names `GibbsRtIrtQuantile`; the export is commented out in the reference (src/ExtendedRtIrtModeling.jl:65) and
@@ -752,7 +721,7 @@ def checkConvergence(MCMC: _GibbsBase, *, detail=True) -> dict:
     ess_n = rhat_n = ess_ok = rhat_ok = 0
     out = {}
     for name, which in (("ra", _lib.TRACE_RA), ("rt", _lib.TRACE_RT), ("qr", _lib.TRACE_QR)):
-        if which == _lib.TRACE_RT and MCMC._model == _lib.MODEL_MLIRT:
+        if which == _lib.TRACE_RT and not MCMC._traits.rt:
             continue
         try:
             if detail:
@@ -776,13 +745,13 @@ def coef(MCMC: _GibbsBase) -> dict:
     """Posterior-mean tables of `coef` (src/GibbsRtIrt.pl.jl:479-538) as plain arrays (pretty-printing is out of scope)."""
     C, M = MCMC.Cond, MCMC.Post.mean
     out = {"a": M.a, "b": M.b}
-    if MCMC._model != _lib.MODEL_MLIRT:
+    if MCMC._traits.rt:
         out.update({"λ": M.lam, "σ²t": M.sig2t, "Σp": np.asarray(M.Sigp).reshape(2, 2, order="F")})
-    if MCMC._model in (_lib.MODEL_RTIRT, _lib.MODEL_NULL):
+    if MCMC._traits.beta in ("pair", "zero_pair"):
         out["β"] = np.asarray(M.beta).reshape(C.nFeat + 1, 2, order="F")
     elif M.beta.size:
         out["β"] = M.beta
-    if MCMC._model in (_lib.MODEL_CROSSQR, _lib.MODEL_CROSS):
+    if MCMC._traits.rho:
         out["ρ"] = M.rho
     return out
 

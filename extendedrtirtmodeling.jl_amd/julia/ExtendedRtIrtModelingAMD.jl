@@ -36,6 +36,7 @@ struct ErmState
     theta::Ptr{Float64}; a::Ptr{Float64}; b::Ptr{Float64}; zeta::Ptr{Float64}; lambda::Ptr{Float64}; sig2t::Ptr{Float64}
     beta::Ptr{Float64}; sigp::Ptr{Float64}; rho::Ptr{Float64}; nu::Ptr{Float64}
 end
+# (the per-model widths below -- nb, nnu, which models read X or have rt / ρ -- restate the table of csrc/erm_model.hpp and _lib.py's MODEL_TRAITS)
 const MODEL_MLIRT, MODEL_RTIRT, MODEL_CROSSQR, MODEL_LATENTQR = Int32(0), Int32(1), Int32(2), Int32(3)
 const MODEL_NULL, MODEL_CROSS, MODEL_LATENT = Int32(4), Int32(5), Int32(6)
 const TRACE_RA, TRACE_RT, TRACE_QR, TRACE_LOGLIKE = Int32(0), Int32(1), Int32(2), Int32(3)

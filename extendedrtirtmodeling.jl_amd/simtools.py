@@ -180,9 +180,9 @@ def _device_generator(funcData, funcGibbs):
     """True when funcData is one of this module's own generators and it is the one the sampler's device generator restates (erm_simulate_data picks the
     generator by model: src/SimTools.jl:117-368), so that a replication's data set can be made on the device."""
     from . import _lib
-    pairs = {setDataMlIrt: (_lib.MODEL_MLIRT,), setDataRtIrt: (_lib.MODEL_RTIRT,), setDataRtIrtNull: (_lib.MODEL_NULL,),
-             setDataRtIrtCross: (_lib.MODEL_CROSS, _lib.MODEL_CROSSQR), setDataRtIrtLatent: (_lib.MODEL_LATENT, _lib.MODEL_LATENTQR)}
-    return funcData in pairs and getattr(funcGibbs, "_model", None) in pairs[funcData]
+    gens = (setDataMlIrt, setDataRtIrt, setDataRtIrtNull, setDataRtIrtCross, setDataRtIrtLatent)      # in the order of ModelTraits.gen
+    model = getattr(funcGibbs, "_model", None)
+    return model in _lib.MODEL_TRAITS and gens[_lib.MODEL_TRAITS[model].gen] is funcData
 
 
 def runSimulation(Cond: SimConditions, truePara: InputPara, *, Para=("a", "b", "λ", "σ²t"), funcData=None, funcGibbs=None, typeName="norm",

@@ -94,6 +94,44 @@ def test_constructors_initialise_para_like_the_reference():
     assert not np.array_equal(_toy(pkg.GibbsRtIrt, seed=5).Para.theta, _toy(pkg.GibbsRtIrt, seed=5, chain_id=1).Para.theta)
 
 
+_SAMPLERS = ("GibbsMlIrt", "GibbsRtIrt", "GibbsRtIrtCrossQr", "GibbsRtIrtLatentQr", "GibbsRtIrtNull", "GibbsRtIrtCross", "GibbsRtIrtLatent")
+
+
+def _restated_initial_values(name, N, J, F, seed, chain_id):
+    """setInitialValues of every sampler, written out: the stream is default_rng(SeedSequence([seed, chain_id, 0x1217])), and the draws come as theta, then zeta
+    if the model has response times, then beta or rho (GibbsRtIrtNull draws neither)."""
+    g = np.random.default_rng(np.random.SeedSequence([seed, chain_id, 0x1217]))
+    e = np.zeros(0)
+    P = dict(omega=e, theta=g.standard_normal(N), a=np.ones(J), b=np.zeros(J), zeta=e, lam=e, sig2t=e, nu=e, beta=e, rho=e, Sigp=e)
+    if name != "GibbsMlIrt":
+        P.update(zeta=g.standard_normal(N), lam=np.zeros(J), sig2t=np.ones(J), Sigp=np.eye(2))
+    if name == "GibbsMlIrt":
+        P["beta"] = g.standard_normal(F + 1)
+    elif name == "GibbsRtIrt":
+        P["beta"] = g.standard_normal((F + 1, 2))
+    elif name in ("GibbsRtIrtLatentQr", "GibbsRtIrtLatent"):
+        P["beta"] = g.standard_normal(F + 2)
+    elif name in ("GibbsRtIrtCrossQr", "GibbsRtIrtCross"):
+        P["rho"] = g.standard_normal(J)
+    return P
+
+
+@pytest.mark.parametrize("chain_id", [0, 3])
+@pytest.mark.parametrize("seed", [1234, 77])
+@pytest.mark.parametrize("name", _SAMPLERS)
+def test_initial_values_are_the_restated_draws_bit_for_bit(name, seed, chain_id):
+    """Constructing a sampler creates no engine: Para is compared field by field, shape and bytes, with the explicit restatement."""
+    N, J, F = 30, 4, 2
+    M = getattr(pkg, name)(pkg.setCond(nSubj=N, nItem=J, nFeat=F, nIter=6, nChain=2, qRt=0.85), seed=seed, chain_id=chain_id)
+    assert M._engine is None
+    want = _restated_initial_values(name, N, J, F, seed, chain_id)
+    assert set(want) == set(pkg.InputPara._fields)
+    for f, w in want.items():
+        got = np.asarray(getattr(M.Para, f), dtype=np.float64)
+        assert got.shape == w.shape and got.tobytes() == w.tobytes(), (name, f)
+    assert M.setInitialValues() is M and np.asarray(M.Para.theta).tobytes() == want["theta"].tobytes()      # every call draws the same values again
+
+
 def test_sample_validates_itemtype_with_the_reference_error_text():
     M = _toy(pkg.GibbsRtIrt)
     with pytest.raises(ValueError, match="Invalid input: the item type must be '1pl' or '2pl'."):
