@@ -16,6 +16,7 @@
 #pragma once
 #include <type_traits>
 #include "erm_layout.hpp"
+#include "erm_model.hpp"      // the per-model table: loglik_kernel reads the offsets of the small part of qr from it
 #include "erm_rng.hpp"
 
 namespace erm {
@@ -2375,16 +2376,10 @@ __global__ void __launch_bounds__(256) loglik_kernel(LogLikArgs D)
     __shared__ double red[256];
     for (int e = tid; e < 4 * J; e += 256) sa[e] = D.sum[e] * D.inv;
     const double* q = D.sum + 4 * J;                      // the small part of qr (tiny_publish's order)
-    // (the offsets below restate qr_sigp_off / beta_len of erm_model.hpp, the host's table: a change there is a change here)
-    for (int j = tid; j < J; j += 256) sr[j] = fam_cq(M) ? q[j] * D.inv : 0.0;
-    if (tid < 4) sS[tid] = (M == MLIRT) ? (tid == 0 || tid == 3 ? 1.0 : 0.0) : q[(fam_cq(M) ? J : (fam_rt(M) ? 2 * p : p + 1)) + tid] * D.inv;
-    if (tid < 2 * PMAX) {
-        double v = 0.0;
-        if (M == MLIRT) { if (tid < p) v = q[tid] * D.inv; }
-        else if (M == RTIRT) { if (tid < p) v = q[tid] * D.inv; else if (tid >= PMAX && tid < PMAX + p) v = q[p + tid - PMAX] * D.inv; }      // [theta column | zeta column at PMAX]
-        else if (fam_lq(M)) { if (tid < p + 1) v = q[tid] * D.inv; }
-        sbeta[tid] = v;
-    }
+    // the small part's offsets and beta's slots come from the per-model table (erm_model.hpp); F is the number of columns the kernels see
+    for (int j = tid; j < J; j += 256) sr[j] = model_traits(M).rho ? q[j] * D.inv : 0.0;
+    if (tid < 4) sS[tid] = !model_traits(M).rt ? (tid == 0 || tid == 3 ? 1.0 : 0.0) : q[qr_sigp_off(M, J, F) + tid] * D.inv;
+    if (tid < 2 * PMAX) { const int u = beta_slot_src(model_traits(M).beta, F, tid); sbeta[tid] = u >= 0 ? q[u] * D.inv : 0.0; }
     __syncthreads();
     const real* C = reinterpret_cast<const real*>(D.C);
     const real* X = reinterpret_cast<const real*>(D.X);

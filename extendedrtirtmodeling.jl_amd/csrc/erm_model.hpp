@@ -61,19 +61,78 @@ constexpr int qr_head(int model, int J, int F) { return model_traits(model).rho 
 constexpr int64_t item_trace_width(int model, int J, int F) { return 4 * (int64_t)J + nq(model, J, F); }
 // erm_state.nu (CrossQr: N x J, row-major on the device and column-major for the caller)
 constexpr int64_t nu_len(int model, int64_t N, int J) { return model_traits(model).nu == NU_SUBJECT ? N : model_traits(model).nu == NU_CELL ? N * (int64_t)J : 0; }
-// Post.ra = [theta; a; b] (src/GibbsRtIrt.pl.jl:44,65), Post.rt = [zeta; lambda; sig2t] (:66; MlIrt's stays []), Post.qr = [small part; nu], logLike
-constexpr int64_t trace_width(int model, int which, int64_t N, int J, int F)
+// A trace as the caller sees it: at most four consecutive blocks of columns.  Post.ra = [theta; a; b] (src/GibbsRtIrt.pl.jl:44,65), Post.rt = [zeta; lambda; sig2t]
+// (:66; MlIrt's stays []), Post.qr = [beta or rho | vec(Sigp) | nu] -- where Null's beta is 2 (nFeat + 1) constant zeros that no kernel stores (:398) and CrossQr's
+// vec(nu) is column-major for the caller and row-major on the device.  Every routine that reads a trace back walks this list; nothing else says what a trace is made of.
+enum BlockKind : int {
+    BLK_SUBJECT = 0,      // one column per subject, from the subject-level trace `src` (SubjTrace)
+    BLK_CELL = 1,         // one column per cell of N x J from the nu trace, kept in DEVICE order: column i * J + j of the block is the caller's j * N + i
+    BLK_ITEM = 2,         // columns [src, src + ncol) of the item-level trace
+    BLK_ZERO = 3          // constant zeros, stored nowhere
+};
+enum SubjTrace : int { SUBJ_THETA = 0, SUBJ_ZETA = 1, SUBJ_NU = 2 };
+struct TraceBlock {
+    int kind; int64_t ncol, col0, src;      // col0: the block's first column in the caller's trace
+    constexpr bool device_order() const { return kind == BLK_CELL; }
+};
+struct TraceBlocks {
+    int n = 0; TraceBlock b[4] = {};
+    constexpr int64_t width() const { return n > 0 ? b[n - 1].col0 + b[n - 1].ncol : 0; }
+    constexpr void add(int kind, int64_t ncol, int64_t src) { if (ncol > 0) { b[n] = TraceBlock{kind, ncol, width(), src}; ++n; } }      // (an empty block is no block)
+    constexpr const TraceBlock* begin() const { return b; }
+    constexpr const TraceBlock* end() const { return b + n; }
+};
+constexpr TraceBlocks trace_blocks(int model, int which, int64_t N, int J, int F)
 {
     const ModelTraits t = model_traits(model);
-    return which == TRACE_RA ? N + 2 * (int64_t)J : which == TRACE_RT ? (t.rt ? N + 2 * (int64_t)J : 0) :
-           which == TRACE_QR ? qr_head(model, J, F) + (t.rt ? 4 : 0) + nu_len(model, N, J) : which == TRACE_LOGLIKE ? 1 : 0;
+    TraceBlocks tb;
+    if (which == TRACE_RA) { tb.add(BLK_SUBJECT, N, SUBJ_THETA); tb.add(BLK_ITEM, 2 * (int64_t)J, 0); }
+    if (which == TRACE_RT && t.rt) { tb.add(BLK_SUBJECT, N, SUBJ_ZETA); tb.add(BLK_ITEM, 2 * (int64_t)J, 2 * (int64_t)J); }
+    if (which == TRACE_QR) {
+        const int64_t q0 = 4 * (int64_t)J;      // the kernels' small part of qr in the item trace
+        if (t.beta == BETA_ZERO_PAIR) { tb.add(BLK_ZERO, nbeta(model, F), 0); tb.add(BLK_ITEM, 4, q0 + qr_sigp_off(model, J, F)); }
+        else tb.add(BLK_ITEM, nq(model, J, F), q0);
+        tb.add(t.nu == NU_CELL ? BLK_CELL : BLK_SUBJECT, nu_len(model, N, J), SUBJ_NU);
+    }
+    return tb;
 }
+// columns of a trace: its blocks' -- and logLike's one, which is made of no block (a column of its own on the device)
+constexpr int64_t trace_width(int model, int which, int64_t N, int J, int F) { return which == TRACE_LOGLIKE ? 1 : trace_blocks(model, which, N, J, F).width(); }
 // the chain farm's summary vector: [item-level trace columns | theta (N) | zeta (N, response-time models) | nu (quantile models)]; an absent block's offset is -1
 struct SummaryLayout { int64_t theta, zeta, nu, len; };
 constexpr SummaryLayout summary_layout(int model, int64_t N, int J, int F)
 {
     const int64_t wi = item_trace_width(model, J, F), nz = model_traits(model).rt ? N : 0, nn = nu_len(model, N, J);
     return {wi, nz > 0 ? wi + N : -1, nn > 0 ? wi + N + nz : -1, wi + N + nz + nn};
+}
+
+// The item-level fields of the parameter block (erm_layout.hpp: a, b, lambda, sig2t, rho : 5 x J), each with the erm_state member that carries it, its offset
+// k * J and the constructors' value.  A template over the state struct: this header stays free of the C ABI's, the host side reads PAR_FIELDS<erm_state>.
+enum ParFieldId : int { PAR_A = 0, PAR_B = 1, PAR_LAMBDA = 2, PAR_SIG2T = 3, PAR_RHO = 4, N_PAR_FIELDS = 5 };
+template <typename State> struct ParField {
+    const char* name; double* State::* member; int k; double init;
+    constexpr int off(int J) const { return k * J; }
+};
+template <typename State> constexpr ParField<State> PAR_FIELDS[N_PAR_FIELDS] = {
+    {"a", &State::a, PAR_A, 1.0}, {"b", &State::b, PAR_B, 0.0}, {"lambda", &State::lambda, PAR_LAMBDA, 0.0}, {"sig2t", &State::sig2t, PAR_SIG2T, 1.0}, {"rho", &State::rho, PAR_RHO, 0.0}};
+// an item-trace row starts with the block's first fields at the same offsets: a, b, lambda, sig2t -- and rho, the head of the small part of qr, where the model has one
+constexpr int item_trace_fields(int model) { return model_traits(model).rho ? N_PAR_FIELDS : PAR_RHO; }
+// beta between its dense form (erm_state.beta = vec(beta) over F covariate columns; the item trace's small part of qr) and the block's [2 PMAX]: the dense entry that
+// slot t of the block holds, -1 for none.  BETA_PAIR's two columns sit at [u] and [PMAX + u], BETA_ZERO_PAIR is never stored and reads as zeros, the others are copied.
+constexpr int beta_slot_src(int shape, int F, int t)
+{
+    const int pp = F + 1;
+    if (shape == BETA_PAIR) return t < pp ? t : (t >= PMAX && t < PMAX + pp) ? pp + t - PMAX : -1;
+    return ((shape == BETA_VEC || shape == BETA_LATENT) && t < beta_len(shape, F)) ? t : -1;
+}
+inline void beta_pack(int shape, int F, const double* dense, double* block)
+{
+    for (int t = 0; t < 2 * PMAX; ++t) if (const int u = beta_slot_src(shape, F, t); u >= 0) block[t] = dense[u];
+}
+inline void beta_unpack(int shape, int F, const double* block, double* dense)
+{
+    for (int u = 0; u < beta_len(shape, F); ++u) dense[u] = 0.0;
+    for (int t = 0; t < 2 * PMAX; ++t) if (const int u = beta_slot_src(shape, F, t); u >= 0) dense[u] = block[t];
 }
 
 // The layout change of an N x J block between the device (row-major, element (i, j) at [i * J + j]) and the caller (column-major, at [j * N + i]):

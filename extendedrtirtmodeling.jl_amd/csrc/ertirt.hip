@@ -165,22 +165,40 @@ struct EngineBase {
     virtual int get_truth(double*, double*) = 0;
     virtual int reset_trace() = 0;
     virtual int set_shard(int, int, int64_t, int64_t, erm_exchange_fn, void*, const void*) = 0;
-    // chain farms (erm_farm_*): this chain's post-burn-in SUMS [item-level trace columns | theta | zeta | nu] added into `acc` (device memory
-    // of this engine's device, summary_len() doubles), and the inverse step from a vector of means to an erm_state
+    // Post.mean and DIC, of one engine and of a chain farm (erm_farm_*): this chain's post-burn-in SUMS [item-level trace columns | theta | zeta | nu] added into
+    // `acc` (device memory of this engine's device, summary_len() doubles; only the subject-level blocks `want` names, all of them if NULL), and the inverse step
+    // from the accumulated sums to the fields of an erm_state
     virtual int64_t summary_len() const = 0;
-    virtual int summary_add(double* acc) = 0;
-    virtual int summary_unpack(const double* mean, erm_state* out) const = 0;
+    virtual int summary_add(double* acc, const erm_state* want) = 0;
+    virtual int mean_from_summary(const double* dacc, double inv, erm_state* out) = 0;
     int64_t rows_done = 0;
     int64_t post_rows = 0;
     erm_timing timing{};
     // the per-model facts and every width that follows from them: one table (erm_model.hpp)
     ModelTraits mt() const { return model_traits(cfg.model); }
     int64_t trace_width(int which) const { return erm::trace_width(cfg.model, which, cfg.n_subj, cfg.n_item, cfg.n_feat); }
+    TraceBlocks trace_blocks(int which) const { return erm::trace_blocks(cfg.model, which, cfg.n_subj, cfg.n_item, cfg.n_feat); }
     int nq() const { return erm::nq(cfg.model, cfg.n_item, cfg.n_feat); }
     int nbeta() const { return erm::nbeta(cfg.model, cfg.n_feat); }
     int64_t nu_len() const { return erm::nu_len(cfg.model, cfg.n_subj, cfg.n_item); }
     int64_t item_trace_width() const { return erm::item_trace_width(cfg.model, cfg.n_item, cfg.n_feat); }
 };
+
+// getDic's four numbers {Dbar, Dhat, pD, DIC} from the accumulated summary `dacc` of `rows` post-burn-in rows (on eng[0]'s device, which evaluates the
+// log-likelihood at the mean) and the logLike rows of the n chains
+int dic_from_summary(EngineBase* const* eng, size_t n, const double* dacc, int64_t rows, double* out4)
+{
+    double ll_hat = 0.0;
+    if (int rc = eng[0]->loglik_at(dacc, 1.0 / (double)rows, &ll_hat)) return rc;
+    double ll_sum = 0.0; int64_t ll_rows = 0;
+    for (size_t l = 0; l < n; ++l) { double t = 0.0; if (int rc = eng[l]->ll_trace_sum(&t)) return rc; ll_sum += t; ll_rows += eng[l]->rows_done; }
+    if (ll_rows <= 0) return fail(ERM_ERR_STATE, "no sweeps recorded");
+    const double Dhat = -2.0 * ll_hat, Dbar = -2.0 * ll_sum / (double)ll_rows;
+    out4[0] = Dbar; out4[1] = Dhat; out4[2] = Dbar - Dhat; out4[3] = Dbar + (Dbar - Dhat);
+    return 0;
+}
+
+constexpr const ParField<erm_state> (&FIELDS)[N_PAR_FIELDS] = PAR_FIELDS<erm_state>;      // the parameter block's item-level fields (erm_model.hpp)
 
 template <typename real> struct Engine : EngineBase {
     hipStream_t stream = nullptr;
@@ -215,6 +233,7 @@ template <typename real> struct Engine : EngineBase {
     bool persist = false;
     bool fused() const { return !m_cq() && G.fused; }  // single-pass models run the tiny step inside the row-pass kernel (G.fused is false when its LDS layout cannot fit: very long tests)
     DevBuf dSumTheta, dSumZeta, dSumNu, dTrTheta, dTrZeta, dTrNu, dTrItem, dTrLl;
+    const DevBuf& subj_trace(int64_t which) const { return which == SUBJ_THETA ? dTrTheta : which == SUBJ_ZETA ? dTrZeta : dTrNu; }      // a TraceBlock's `src`
     // WAIC (erm_set_pointwise): the unit, the accumulators {m, s}[units] and {mean, m2}[units] (erm_pointwise.hpp), GibbsRtIrtCrossQr's copy of nu_t
     // (taken ahead of pass B of every sweep, which overwrites nu_t with nu_{t+1}: N * J values of the engine's cell type)
     int pw_unit = PW_OFF;
@@ -366,7 +385,7 @@ template <typename real> struct Engine : EngineBase {
 
         // ---- default state (constructors' deterministic part: a = 1, b = 0, lambda = 0, sig2t = 1, Sigp = I)
         std::vector<double> par(par_size(J), 0.0);
-        for (int j = 0; j < J; ++j) { par[j] = 1.0; par[3 * J + j] = 1.0; }
+        for (const auto& f : FIELDS) std::fill_n(&par[f.off(J)], J, f.init);
         par[par_off_sigp(J) + 0] = 1.0; par[par_off_sigp(J) + 3] = 1.0;
         par[par_off_derived(J)] = (double)J;
         for (int k = 0; k < 2; ++k) H2D(dParB[k].p, par.data(), par.size() * sizeof(double));
@@ -1044,9 +1063,8 @@ template <typename real> struct Engine : EngineBase {
         stats_valid = back.err == 0;
         if (back.err) {
             const int e = (int)back.err - 1;
-            const char* names[] = {"a", "b", "lambda", "sig2t", "rho"};
-            std::string what = e < 5 * J ? std::string(names[e / J]) + "[" + std::to_string(e % J) + "]"
-                             : (e < 5 * J + 4 ? "Sigp[" + std::to_string(e - 5 * J) + "]" : "beta[" + std::to_string(e - 5 * J - 4) + "]");
+            std::string what = e < par_off_sigp(J) ? std::string(FIELDS[e / J].name) + "[" + std::to_string(e % J) + "]"
+                             : (e < par_off_beta(J) ? "Sigp[" + std::to_string(e - par_off_sigp(J)) + "]" : "beta[" + std::to_string(e - par_off_beta(J)) + "]");
             return fail(ERM_ERR_NONFINITE, "non-finite parameter " + what + " at sweep " + std::to_string(back.sweep));
         }
         return 0;
@@ -1188,11 +1206,8 @@ template <typename real> struct Engine : EngineBase {
         has_data = false; stats_valid = false;
         // truth vector: a b lambda sig2t rho | chol(Sigp) | beta
         std::vector<double> tv((size_t)5 * J + 3 + 2 * PMAX + 2, 0.0);
-        for (int j = 0; j < J; ++j) {
-            tv[j] = tr->a[j]; tv[J + j] = tr->b[j];
-            tv[2 * J + j] = tr->lambda ? tr->lambda[j] : 0.0; tv[3 * J + j] = tr->sig2t ? tr->sig2t[j] : 1.0; tv[4 * J + j] = tr->rho ? tr->rho[j] : 0.0;
-            if (is_rt() && !(tv[3 * J + j] > 0.0)) return fail(ERM_ERR_ARG, "sig2t must be positive");
-        }
+        for (const auto& f : FIELDS) { const double* src = tr->*f.member; for (int j = 0; j < J; ++j) tv[f.off(J) + j] = src ? src[j] : f.init; }
+        for (int j = 0; j < J; ++j) if (is_rt() && !(tv[PAR_SIG2T * J + j] > 0.0)) return fail(ERM_ERR_ARG, "sig2t must be positive");
         double S00 = 1.0, S10 = 0.0, S11 = 1.0;
         if (tr->sigp) { S00 = tr->sigp[0]; S10 = tr->sigp[1]; S11 = tr->sigp[3]; }
         if (!(S00 > 0.0) || !(S11 - S10 * S10 / S00 > 0.0)) return fail(ERM_ERR_ARG, "Sigp must be positive definite");
@@ -1298,19 +1313,15 @@ template <typename real> struct Engine : EngineBase {
         stats_valid = false;
         std::vector<double> par(par_size(J));
         HIPCHK(hipMemcpy(par.data(), dParB[cur].p, par.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if (st->a) memcpy(&par[0], st->a, J * sizeof(double));
-        if (st->b) memcpy(&par[J], st->b, J * sizeof(double));
-        if (st->lambda) memcpy(&par[2 * J], st->lambda, J * sizeof(double));
-        if (st->sig2t) { for (int j = 0; j < J; ++j) if (!(st->sig2t[j] > 0.0)) return fail(ERM_ERR_ARG, "sig2t must be positive"); memcpy(&par[3 * J], st->sig2t, J * sizeof(double)); }
-        if (st->rho) memcpy(&par[4 * J], st->rho, J * sizeof(double));
-        if (st->sigp) memcpy(&par[par_off_sigp(J)], st->sigp, 4 * sizeof(double));
-        if (st->beta) {
-            double* b = &par[par_off_beta(J)];
-            const int pp = F + 1;
-            if (mt().beta == BETA_PAIR) { for (int u = 0; u < pp; ++u) { b[u] = st->beta[u]; b[PMAX + u] = st->beta[pp + u]; } }
-            else if (mt().beta != BETA_ZERO_PAIR) for (int u = 0; u < nbeta(); ++u) b[u] = st->beta[u];
+        for (const auto& f : FIELDS) {
+            const double* src = st->*f.member;
+            if (!src) continue;
+            if (f.k == PAR_SIG2T) for (int j = 0; j < J; ++j) if (!(src[j] > 0.0)) return fail(ERM_ERR_ARG, "sig2t must be positive");
+            memcpy(&par[f.off(J)], src, J * sizeof(double));
         }
-        { double t = 0.0; for (int j = 0; j < J; ++j) t += 1.0 / par[3 * J + j]; par[par_off_derived(J)] = t; }
+        if (st->sigp) memcpy(&par[par_off_sigp(J)], st->sigp, 4 * sizeof(double));
+        if (st->beta) beta_pack(mt().beta, F, st->beta, &par[par_off_beta(J)]);
+        { double t = 0.0; for (int j = 0; j < J; ++j) t += 1.0 / par[PAR_SIG2T * J + j]; par[par_off_derived(J)] = t; }
         H2D(dParB[cur].p, par.data(), par.size() * sizeof(double));
         if (st->theta) if (int rc = up_real(dTheta, st->theta, N)) return rc;
         if (st->zeta) if (int rc = up_real(dZeta, st->zeta, N)) return rc;
@@ -1332,19 +1343,9 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipStreamSynchronize(stream));
         std::vector<double> par(par_size(J));
         HIPCHK(hipMemcpy(par.data(), dParB[cur].p, par.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if (st->a) memcpy(st->a, &par[0], J * sizeof(double));
-        if (st->b) memcpy(st->b, &par[J], J * sizeof(double));
-        if (st->lambda) memcpy(st->lambda, &par[2 * J], J * sizeof(double));
-        if (st->sig2t) memcpy(st->sig2t, &par[3 * J], J * sizeof(double));
-        if (st->rho) memcpy(st->rho, &par[4 * J], J * sizeof(double));
+        for (const auto& f : FIELDS) if (double* dst = st->*f.member) memcpy(dst, &par[f.off(J)], J * sizeof(double));
         if (st->sigp) memcpy(st->sigp, &par[par_off_sigp(J)], 4 * sizeof(double));
-        if (st->beta) {
-            const double* b = &par[par_off_beta(J)];
-            const int pp = F + 1;
-            if (mt().beta == BETA_PAIR) { for (int u = 0; u < pp; ++u) { st->beta[u] = b[u]; st->beta[pp + u] = b[PMAX + u]; } }
-            else if (mt().beta == BETA_ZERO_PAIR) for (int u = 0; u < nbeta(); ++u) st->beta[u] = 0.0;
-            else for (int u = 0; u < nbeta(); ++u) st->beta[u] = b[u];
-        }
+        if (st->beta) beta_unpack(mt().beta, F, &par[par_off_beta(J)], st->beta);
         if (st->theta) if (int rc = down_real(dTheta, st->theta, N)) return rc;
         if (st->zeta) if (int rc = down_real(dZeta, st->zeta, N)) return rc;
         if (st->nu && dNu.p) {
@@ -1386,7 +1387,8 @@ template <typename real> struct Engine : EngineBase {
             return 0;
         }
         if (cfg.trace_mode != ERM_TRACE_FULL) return fail(ERM_ERR_NOTRACE, "subject-level traces need trace_mode = ERM_TRACE_FULL");
-        if (which == ERM_TRACE_QR && mt().nu == NU_CELL && !dTrNu.p)
+        const TraceBlocks blocks = trace_blocks(which);
+        for (const TraceBlock& b : blocks) if (b.kind == BLK_CELL && !dTrNu.p)
             return fail(ERM_ERR_NOTRACE, "the per-sweep nu trace (N*J values per sweep) exceeds erm_config.nu_trace_max_gb; use erm_get_item_trace (rho, Sigp) + erm_get_mean (nu)");
         std::vector<double> it;
         if (int rc = fetch_item_trace(it)) return rc;
@@ -1417,37 +1419,27 @@ template <typename real> struct Engine : EngineBase {
             }
             return 0;
         };
-        if (which == ERM_TRACE_RA) {            // [theta; a; b]  src/GibbsRtIrt.pl.jl:242,320
-            if (int rc = subj(dTrTheta, 0)) return rc;
-            for (int64_t r = 0; r < rows_cap; ++r) for (int j = 0; j < J; ++j) { at(r, N + j) = it[r * wi + j]; at(r, N + J + j) = it[r * wi + J + j]; }
-        } else if (which == ERM_TRACE_RT) {     // [zeta; lambda; sig2t]  :321
-            if (int rc = subj(dTrZeta, 0)) return rc;
-            for (int64_t r = 0; r < rows_cap; ++r) for (int j = 0; j < J; ++j) { at(r, N + j) = it[r * wi + 2 * J + j]; at(r, N + J + j) = it[r * wi + 3 * J + j]; }
-        } else {                                 // qr  :241,319 ; Latent :308
-            const int q = nq();
-            if (mt().beta == BETA_ZERO_PAIR) {          // [vec(beta) = 0 (2(nFeat+1)); vec(Sigp)]  src/GibbsRtIrt.pl.jl:398
-                const int nb = nbeta(), so = qr_sigp_off(cfg.model, J, F);
-                for (int64_t r = 0; r < rows_cap; ++r) { for (int k = 0; k < nb; ++k) at(r, k) = 0.0; for (int k = 0; k < 4; ++k) at(r, nb + k) = it[r * wi + 4 * J + so + k]; }
-                return 0;
-            }
-            for (int64_t r = 0; r < rows_cap; ++r) for (int k = 0; k < q; ++k) at(r, k) = it[r * wi + 4 * J + k];
-            if (mt().nu == NU_SUBJECT) if (int rc = subj(dTrNu, q)) return rc;
-            if (mt().nu == NU_CELL) {                   // vec(nu): column-major N x J after [rho; vec(Sigp)]
-                std::vector<real> cells((size_t)N * J);
+        for (const TraceBlock& b : blocks) {
+            switch (b.kind) {
+            case BLK_SUBJECT: if (int rc = subj(subj_trace(b.src), b.col0)) return rc; break;
+            case BLK_CELL: {                    // vec(nu): column-major N x J for the caller
+                std::vector<real> cells((size_t)b.ncol);
                 for (int64_t r = 0; r < rows_cap; ++r) {
-                    HIPCHK(hipMemcpy(cells.data(), dTrNu.as<real>() + (size_t)r * N * J, cells.size() * sizeof(real), hipMemcpyDeviceToHost));
-                    rows_to_cols(cells.data(), &at(r, q), N, J, AsIs(), nIter);
+                    HIPCHK(hipMemcpy(cells.data(), dTrNu.as<real>() + (size_t)r * cells.size(), cells.size() * sizeof(real), hipMemcpyDeviceToHost));
+                    rows_to_cols(cells.data(), &at(r, b.col0), N, J, AsIs(), nIter);
                 }
+                break;
+            }
+            case BLK_ITEM: for (int64_t r = 0; r < rows_cap; ++r) for (int64_t k = 0; k < b.ncol; ++k) at(r, b.col0 + k) = it[r * wi + b.src + k]; break;
+            case BLK_ZERO: for (int64_t r = 0; r < rows_cap; ++r) for (int64_t k = 0; k < b.ncol; ++k) at(r, b.col0 + k) = 0.0; break;
             }
         }
         return 0;
     }
 
-    // ess / rhat of every column of Post.ra / rt / qr, computed on the device from the resident traces (diag_kernel)
-    // ess / rhat of every column of trace `which` into device arrays of trace_width(which) doubles.  GibbsRtIrtCrossQr's vec(nu) block of Post.qr is
-    // column-major N x J in Julia's layout and row-major on the device: it is diagnosed in DEVICE order (entry q + i * J + j), *nu_block says so.
-    int diag_device(int which, DevBuf& dE, DevBuf& dR, bool* nu_block) {
-        *nu_block = false;
+    // ess / rhat of every column of trace `which` into device arrays of trace_width(which) doubles, block by block (diag_kernel); a block in device order
+    // (TraceBlock::device_order) is diagnosed in that order
+    int diag_device(int which, DevBuf& dE, DevBuf& dR) {
         HIPCHK(hipSetDevice(cfg.device));
         const int64_t wd = trace_width(which);
         if (which == ERM_TRACE_LOGLIKE || wd <= 0) return fail(ERM_ERR_ARG, "diagnostics exist for the ra / rt / qr traces");
@@ -1459,57 +1451,42 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipStreamSynchronize(stream));
         if (int rc = dE.alloc((size_t)wd * sizeof(double))) return rc;
         if (int rc = dR.alloc((size_t)wd * sizeof(double))) return rc;
-        auto launch_real = [&](const DevBuf& tr, int64_t ncol, int64_t off) -> int {
-            if (!tr.p) return fail(ERM_ERR_NOTRACE, "this trace was not recorded");
-            hipLaunchKernelGGL((diag_kernel<real>), dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, stream, tr.as<real>(), (long long)ncol, (long long)ncol,
-                               cfg.n_iter, cfg.n_chain, cfg.n_burnin, dE.as<double>() + off, dR.as<double>() + off);
-            return 0;
-        };
-        auto launch_item = [&](int64_t col0, int64_t ncol, int64_t off) -> int {
-            hipLaunchKernelGGL((diag_kernel<double>), dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, stream, dTrItem.as<double>() + col0, (long long)ncol,
-                               (long long)item_trace_width(), cfg.n_iter, cfg.n_chain, cfg.n_burnin, dE.as<double>() + off, dR.as<double>() + off);
-            return 0;
-        };
-        const int q = nq();
-        if (which == ERM_TRACE_RA) {            // [theta; a; b]
-            if (int rc = launch_real(dTrTheta, N, 0)) return rc;
-            if (int rc = launch_item(0, 2 * J, N)) return rc;
-        } else if (which == ERM_TRACE_RT) {     // [zeta; lambda; sig2t]
-            if (int rc = launch_real(dTrZeta, N, 0)) return rc;
-            if (int rc = launch_item(2 * J, 2 * J, N)) return rc;
-        } else if (mt().beta == BETA_ZERO_PAIR) {   // [vec(beta) = 0; vec(Sigp)]: the zeros are constant -> NaN
-            const int nb = nbeta();
-            std::vector<double> nanv(nb, std::nan(""));
-            HIPCHK(hipMemcpyAsync(dE.p, nanv.data(), nb * sizeof(double), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(dR.p, nanv.data(), nb * sizeof(double), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            if (int rc = launch_item(4 * J + qr_sigp_off(cfg.model, J, F), 4, nb)) return rc;
-        } else {
-            if (int rc = launch_item(4 * J, q, 0)) return rc;
-            if (mt().nu == NU_SUBJECT) { if (int rc = launch_real(dTrNu, N, q)) return rc; }
-            if (mt().nu == NU_CELL) {
-                if (!dTrNu.p) return fail(ERM_ERR_NOTRACE, "the per-sweep nu trace was not recorded (erm_config.nu_trace_max_gb)");
-                if (int rc = launch_real(dTrNu, (int64_t)N * J, q)) return rc;
-                *nu_block = true;
+        for (const TraceBlock& b : trace_blocks(which)) {
+            double* e = dE.as<double>() + b.col0; double* r = dR.as<double>() + b.col0;
+            const dim3 grid((unsigned)((b.ncol + 255) / 256));
+            switch (b.kind) {
+            case BLK_SUBJECT: case BLK_CELL: {
+                const DevBuf& tr = subj_trace(b.src);
+                if (!tr.p) return fail(ERM_ERR_NOTRACE, b.kind == BLK_CELL ? "the per-sweep nu trace was not recorded (erm_config.nu_trace_max_gb)" : "this trace was not recorded");
+                hipLaunchKernelGGL((diag_kernel<real>), grid, dim3(256), 0, stream, tr.as<real>(), (long long)b.ncol, (long long)b.ncol, cfg.n_iter, cfg.n_chain, cfg.n_burnin, e, r);
+                break;
+            }
+            case BLK_ITEM:
+                hipLaunchKernelGGL((diag_kernel<double>), grid, dim3(256), 0, stream, dTrItem.as<double>() + b.src, (long long)b.ncol, (long long)item_trace_width(), cfg.n_iter, cfg.n_chain,
+                                   cfg.n_burnin, e, r);
+                break;
+            case BLK_ZERO: {                    // constant columns: NaN
+                const std::vector<double> nanv((size_t)b.ncol, std::nan(""));
+                HIPCHK(hipMemcpyAsync(e, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(r, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                break;
+            }
             }
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
-    // ess / rhat of every column of Post.ra / rt / qr, computed on the device from the resident traces (diag_kernel)
+    // ess / rhat of every column of Post.ra / rt / qr in the caller's order
     int get_diagnostics(int which, double* ess, double* rhat) override {
         DevBuf dE, dR;
-        bool nu_block = false;
-        if (int rc = diag_device(which, dE, dR, &nu_block)) return rc;
+        if (int rc = diag_device(which, dE, dR)) return rc;
         const int64_t wd = trace_width(which);
         HIPCHK(hipMemcpy(ess, dE.p, (size_t)wd * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(rhat, dR.p, (size_t)wd * sizeof(double), hipMemcpyDeviceToHost));
-        if (nu_block) {      // device order (row-major N x J) -> Julia's vec(nu) (column-major)
-            const int q = nq();
-            std::vector<double> he(ess + q, ess + wd), hr(rhat + q, rhat + wd);
-            rows_to_cols(he.data(), ess + q, N, J);
-            rows_to_cols(hr.data(), rhat + q, N, J);
+        for (const TraceBlock& b : trace_blocks(which)) if (b.device_order()) {      // row-major N x J -> Julia's vec (column-major)
+            for (double* v : {ess, rhat}) { const std::vector<double> h(v + b.col0, v + b.col0 + b.ncol); rows_to_cols(h.data(), v + b.col0, N, J); }
         }
         return 0;
     }
@@ -1517,72 +1494,72 @@ template <typename real> struct Engine : EngineBase {
     // ESS > 400 / R-hat < 1.1 (the reference's thresholds), counted on the device
     int get_convergence(int which, int64_t* c4) override {
         DevBuf dE, dR;
-        bool nu_block = false;
-        if (int rc = diag_device(which, dE, dR, &nu_block)) return rc;
+        if (int rc = diag_device(which, dE, dR)) return rc;
         return count_converged(dE, dR, trace_width(which), stream, c4);
     }
 
-    // sums over the post-burn-in rows of the item-level trace columns (a, b, lambda, sig2t, small part of qr)
-    int item_sums(std::vector<double>& m) {
-        std::vector<double> it;
-        if (int rc = fetch_item_trace(it)) return rc;
-        const int64_t wi = item_trace_width(), burn = (int64_t)cfg.n_burnin * cfg.n_chain;
-        m.assign(wi, 0.0);
-        for (int64_t r = burn; r < rows_done; ++r) for (int64_t k = 0; k < wi; ++k) m[k] += it[r * wi + k];
-        return 0;
-    }
-    // item-level means -> the fields of Post.mean (src/GibbsRtIrt.pl.jl:249-254, 327-343; Cross :304-318; Latent :316-330)
+    // item-level means (an item-trace row's layout) -> the fields of Post.mean (src/GibbsRtIrt.pl.jl:249-254, 327-343; Cross :304-318; Latent :316-330)
     void unpack_items(const double* m, erm_state* out) const {
-        if (out->a) memcpy(out->a, &m[0], J * sizeof(double));
-        if (out->b) memcpy(out->b, &m[J], J * sizeof(double));
-        if (out->lambda) memcpy(out->lambda, &m[2 * J], J * sizeof(double));
-        if (out->sig2t) memcpy(out->sig2t, &m[3 * J], J * sizeof(double));
+        for (int k = 0; k < item_trace_fields(cfg.model); ++k) if (double* dst = out->*FIELDS[k].member) memcpy(dst, &m[FIELDS[k].off(J)], J * sizeof(double));
         const double* q = &m[4 * J];                  // the kernels' small part of qr: [beta or rho | Sigp at qr_sigp_off]
         if (out->beta && mt().beta == BETA_ZERO_PAIR) memset(out->beta, 0, nbeta() * sizeof(double));
         else if (out->beta) memcpy(out->beta, q, nbeta() * sizeof(double));
-        if (out->rho && mt().rho) memcpy(out->rho, q, J * sizeof(double));
         if (out->sigp && is_rt()) memcpy(out->sigp, q + qr_sigp_off(cfg.model, J, F), 4 * sizeof(double));
     }
+    // Post.mean of one engine: a farm of one.  Only the blocks `out` asks for are added, copied or transposed (the accumulator ends with the last of them).
     int get_mean(erm_state* out) override {
         if (!out) return fail(ERM_ERR_ARG, "state is NULL");
         HIPCHK(hipSetDevice(cfg.device));
         HIPCHK(hipStreamSynchronize(stream));
         if (post_rows <= 0) return fail(ERM_ERR_STATE, "no post-burn-in sweeps recorded");
-        const double inv = 1.0 / (double)post_rows;
-        auto subj = [&](const DevBuf& d, double* dst, size_t n, bool transpose) -> int {
-            std::vector<double> t(n);
-            HIPCHK(hipMemcpy(t.data(), d.p, n * sizeof(double), hipMemcpyDeviceToHost));
-            if (!transpose) for (size_t k = 0; k < n; ++k) dst[k] = t[k] * inv;
-            else rows_to_cols(t.data(), dst, N, J, [&](double v, int64_t) { return v * inv; });
-            return 0;
-        };
-        if (out->theta) if (int rc = subj(dSumTheta, out->theta, N, false)) return rc;
-        if (out->zeta && is_rt()) if (int rc = subj(dSumZeta, out->zeta, N, false)) return rc;
-        if (out->nu && dSumNu.p) if (int rc = subj(dSumNu, out->nu, (size_t)nu_len(), mt().nu == NU_CELL)) return rc;
-        std::vector<double> m;
-        if (int rc = item_sums(m)) return rc;
-        for (auto& v : m) v *= inv;
-        unpack_items(m.data(), out);
-        return 0;
+        const SummaryLayout L = summary();
+        DevBuf acc;
+        if (int rc = acc.alloc((size_t)(wants_nu(out) ? L.len : wants_zeta(out) ? L.zeta + N : out->theta ? L.theta + N : L.theta) * sizeof(double))) return rc;
+        if (int rc = summary_add(acc.as<double>(), out)) return rc;
+        return mean_from_summary(acc.as<double>(), 1.0 / (double)post_rows, out);
     }
 
-    // ---- chain farms: [item sums (wi) | sum theta (N) | sum zeta (N, response-time models) | sum nu (N or N*J, quantile models)]
+    // ---- the summary vector (chain farms, Post.mean, DIC): [item sums (wi) | sum theta (N) | sum zeta (N, response-time models) | sum nu (N or N*J, quantile models)]
     SummaryLayout summary() const { return summary_layout(cfg.model, N, J, F); }
     int64_t summary_len() const override { return summary().len; }
-    int summary_add(double* acc) override {
+    // the subject-level blocks a request for Post.mean names (want == NULL: all the model has)
+    bool wants_zeta(const erm_state* want) const { return is_rt() && (!want || want->zeta); }
+    bool wants_nu(const erm_state* want) const { return m_nu() && (!want || want->nu); }
+    int summary_add(double* acc, const erm_state* want) override {
         HIPCHK(hipSetDevice(cfg.device));
-        auto add = [&](double* dst, const double* src, int64_t n) {
-            hipLaunchKernelGGL(acc_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, stream, dst, src, (long long)n);
+        auto add = [&](int64_t off, const DevBuf& src, int64_t n) {
+            hipLaunchKernelGGL(acc_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, stream, acc + off, src.as<double>(), (long long)n);
         };
-        // item-level columns: summed over the post-burn-in rows of the resident item trace ON the device, in row order (the order erm_get_mean's host sum uses)
+        // item-level columns: summed over the post-burn-in rows of the resident item trace ON the device, in row order from 0.0
         const int64_t wi = item_trace_width(), burn = (int64_t)cfg.n_burnin * cfg.n_chain;
         hipLaunchKernelGGL(item_sum_kernel, dim3((unsigned)((wi + 255) / 256)), dim3(256), 0, stream, dTrItem.as<double>(), (long long)wi, (long long)std::min(burn, rows_done), (long long)rows_done, acc);
         const SummaryLayout L = summary();
-        add(acc + L.theta, dSumTheta.as<double>(), N);
-        if (L.zeta >= 0) add(acc + L.zeta, dSumZeta.as<double>(), N);
-        if (L.nu >= 0) add(acc + L.nu, dSumNu.as<double>(), nu_len());
+        if (!want || want->theta) add(L.theta, dSumTheta, N);
+        if (wants_zeta(want)) add(L.zeta, dSumZeta, N);
+        if (wants_nu(want)) add(L.nu, dSumNu, nu_len());
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // the inverse step: the blocks `out` asks for copied down from the accumulated sums `dacc` (this engine's device), scaled by inv, in the caller's layout
+    int mean_from_summary(const double* dacc, double inv, erm_state* out) override {
+        HIPCHK(hipSetDevice(cfg.device));
+        const SummaryLayout L = summary();
+        std::vector<double> t;
+        auto down = [&](int64_t off, int64_t n, double* dst) -> int {      // dst == NULL: into t
+            if (!dst) { t.resize((size_t)n); dst = t.data(); }
+            HIPCHK(hipMemcpy(dst, dacc + off, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+            for (int64_t k = 0; k < n; ++k) dst[k] *= inv;
+            return 0;
+        };
+        if (int rc = down(0, item_trace_width(), nullptr)) return rc;
+        unpack_items(t.data(), out);
+        if (out->theta) if (int rc = down(L.theta, N, out->theta)) return rc;
+        if (wants_zeta(out)) if (int rc = down(L.zeta, N, out->zeta)) return rc;
+        if (wants_nu(out)) {
+            if (int rc = down(L.nu, nu_len(), mt().nu == NU_CELL ? nullptr : out->nu)) return rc;
+            if (mt().nu == NU_CELL) rows_to_cols(t.data(), out->nu, N, J);
+        }
         return 0;
     }
 
@@ -1629,13 +1606,9 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipSetDevice(cfg.device));
         DevBuf acc;
         if (int rc = acc.alloc((size_t)summary_len() * sizeof(double))) return rc;
-        if (int rc = summary_add(acc.as<double>())) return rc;
-        double ll_hat = 0.0, ll_sum = 0.0;
-        if (int rc = loglik_at(acc.as<double>(), 1.0 / (double)post_rows, &ll_hat)) return rc;
-        if (int rc = ll_trace_sum(&ll_sum)) return rc;
-        const double Dhat = -2.0 * ll_hat, Dbar = -2.0 * ll_sum / (double)rows_done;
-        out4[0] = Dbar; out4[1] = Dhat; out4[2] = Dbar - Dhat; out4[3] = Dbar + (Dbar - Dhat);
-        return 0;
+        if (int rc = summary_add(acc.as<double>(), nullptr)) return rc;
+        EngineBase* self = this;
+        return dic_from_summary(&self, 1, acc.as<double>(), post_rows, out4);
     }
     int set_seed(uint64_t seed) override {
         HIPCHK(hipSetDevice(cfg.device));
@@ -1645,17 +1618,6 @@ template <typename real> struct Engine : EngineBase {
         drop_graphs();               // the captured launches carry the seed as a kernel argument
         stats_valid = false;         // the resident omega_{t+1} / nu_{t+1} were drawn from the old streams: the next run draws them again
         return pred_clear();         // the replicates of the old chain do not mix with the new one's
-    }
-    int summary_unpack(const double* mean, erm_state* out) const override {
-        unpack_items(mean, out);
-        const SummaryLayout L = summary();
-        if (out->theta) memcpy(out->theta, mean + L.theta, N * sizeof(double));
-        if (out->zeta && L.zeta >= 0) memcpy(out->zeta, mean + L.zeta, N * sizeof(double));
-        if (out->nu && L.nu >= 0) {
-            if (mt().nu == NU_SUBJECT) memcpy(out->nu, mean + L.nu, N * sizeof(double));
-            else rows_to_cols(mean + L.nu, out->nu, N, J);
-        }
-        return 0;
     }
 };
 
@@ -1922,7 +1884,7 @@ static int farm_reduce(erm_farm_handle f, std::vector<DevBuf>& acc, int64_t* tot
     for (size_t l = 0; l < f->eng.size(); ++l) {
         int d = 0;
         while (f->udev[d] != f->dev[l]) ++d;
-        if (int rc = f->eng[l]->e->summary_add(acc[d].as<double>())) return fail(rc, "chain " + std::to_string(l) + ": " + g_err);      // synchronises its stream
+        if (int rc = f->eng[l]->e->summary_add(acc[d].as<double>(), nullptr)) return fail(rc, "chain " + std::to_string(l) + ": " + g_err);      // synchronises its stream
     }
     const bool force = (f->cfg.flags & ERM_FLAG_FARM_FORCE_RCCL) != 0;
     f->used_rccl = false;
@@ -1971,13 +1933,7 @@ int erm_farm_get_mean(erm_farm_handle f, erm_state* out)
     int64_t total = 0;
     double init_ms = 0.0;
     if (int rc = farm_reduce(f, acc, &total, &init_ms)) return rc;
-    const int64_t len = f->eng[0]->e->summary_len();
-    std::vector<double> m((size_t)len);
-    HIPCHK(hipSetDevice(f->udev[0]));
-    HIPCHK(hipMemcpy(m.data(), acc[0].p, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
-    const double inv = 1.0 / (double)total;
-    for (auto& v : m) v *= inv;
-    const int rc = f->eng[0]->e->summary_unpack(m.data(), out);
+    const int rc = f->eng[0]->e->mean_from_summary(acc[0].as<double>(), 1.0 / (double)total, out);      // (chain 0 runs on the first distinct device)
     f->tm.gather_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - init_ms;
     return rc;
 }
@@ -1993,14 +1949,9 @@ int erm_farm_get_dic(erm_farm_handle f, double* out4)
     if (int rc = farm_reduce(f, acc, &total, &init_ms)) return rc;
     int d0 = 0;
     while (f->udev[d0] != f->dev[0]) ++d0;
-    double ll_hat = 0.0;
-    if (int rc = f->eng[0]->e->loglik_at(acc[d0].as<double>(), 1.0 / (double)total, &ll_hat)) return rc;
-    double ll_sum = 0.0; int64_t rows = 0;
-    for (auto& e : f->eng) { double t = 0.0; if (int rc = e->e->ll_trace_sum(&t)) return rc; ll_sum += t; rows += e->e->rows_done; }
-    if (rows <= 0) return fail(ERM_ERR_STATE, "no sweeps recorded");
-    const double Dhat = -2.0 * ll_hat, Dbar = -2.0 * ll_sum / (double)rows;
-    out4[0] = Dbar; out4[1] = Dhat; out4[2] = Dbar - Dhat; out4[3] = Dbar + (Dbar - Dhat);
-    return 0;
+    std::vector<EngineBase*> chains;
+    for (auto& e : f->eng) chains.push_back(e->e.get());
+    return dic_from_summary(chains.data(), chains.size(), acc[d0].as<double>(), total, out4);
 }
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed)
 {

@@ -14,12 +14,13 @@ pkg = pu.ge.load_package()
 _RN, _RJ, _RF = 5, 3, 2
 
 
-def _readout_engine(model, precision, n_iter):
+def _readout_engine(model, precision, n_iter, n_feat=_RF, cov2one=None):
     g = np.random.default_rng(3)
     Y = g.random((_RN, _RJ)) < 0.5
     logT = None if model == "mlirt" else g.normal(1.0, 0.3, (_RN, _RJ))
-    X = g.standard_normal((_RN, _RF)) if model in pu.X_MODELS else None
-    eng = pkg._lib.Engine(model=pu.MODELS[model], n_item=_RJ, n_subj=_RN, n_feat=_RF, n_iter=n_iter, n_chain=1, n_burnin=1, cov2one=int(model not in ("latentqr", "latent")),
+    X = g.standard_normal((_RN, n_feat)) if model in pu.X_MODELS and n_feat else None
+    eng = pkg._lib.Engine(model=pu.MODELS[model], n_item=_RJ, n_subj=_RN, n_feat=n_feat, n_iter=n_iter, n_chain=1, n_burnin=1,
+                          cov2one=int(model not in ("latentqr", "latent")) if cov2one is None else cov2one,
                           q_rt=0.85, seed=11, precision={"f32": 0, "f64": 1}[precision], trace_mode=1)
     eng.set_data(Y, logT, X)
     return eng, Y, logT, X
@@ -107,3 +108,78 @@ def test_every_readout_has_the_tables_width_and_layout(table, model, precision):
         ess, rhat = eng.diagnostics(which)
         assert ess.shape == rhat.shape == (t[key],)
     eng.close()
+
+
+# What Post.qr is made of at N = 5, J = 3, written out per (model, F) and derived from no table: (source, first column, columns) in order, where an item-trace row is
+# [a 0:3 | b 3:6 | lambda 6:9 | sig2t 9:12 | the kernels' small part of qr 12:].  GibbsRtIrtNull's kernels see no covariates and publish [beta_theta0, beta_zeta0]
+# at 12:14 and vec(Sigp) at 14:18 whatever F is; its Post.qr starts with 2 (F + 1) zeros that are stored nowhere.
+_QR_CONTENT = {
+    ("mlirt", 2): [("item", 12, 3)],                                        # beta (F + 1)
+    ("rtirt", 2): [("item", 12, 6), ("item", 18, 4)],                       # vec(beta) (2 (F + 1)), vec(Sigp)
+    ("null", 2): [("zero", 0, 6), ("item", 14, 4)],
+    ("null", 0): [("zero", 0, 2), ("item", 14, 4)],
+    ("cross", 2): [("item", 12, 3), ("item", 15, 4)],                       # rho (J), vec(Sigp)
+    ("crossqr", 2): [("item", 12, 3), ("item", 15, 4), ("nu", 0, 15)],      # ..., vec(nu) (N J)
+    ("latent", 2): [("item", 12, 4), ("item", 16, 4)],                      # beta (F + 2), vec(Sigp)
+    ("latentqr", 2): [("item", 12, 4), ("item", 16, 4), ("nu", 0, 5)],      # ..., nu (N)
+}
+_ITEM_WIDTH = {("mlirt", 2): 15, ("rtirt", 2): 22, ("null", 2): 18, ("null", 0): 18, ("cross", 2): 19, ("crossqr", 2): 19, ("latent", 2): 20, ("latentqr", 2): 20}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+@pytest.mark.parametrize("model,F", sorted(_QR_CONTENT))
+def test_every_trace_column_holds_what_its_name_says(model, F, precision):
+    """erm_get_trace and the diagnostics read one list of blocks, so comparing one with the other cannot notice a list that is wrong; this pins the CONTENTS against
+    read-outs that do not go through it.  nIter = 4, one chain, full traces, one erm_run per row: row r of Post.ra starts with the theta erm_get_state returns after
+    that run and goes on with columns a, b of the item trace; Post.rt the same with zeta, lambda, sig2t; Post.qr is the literal map above (its nu block is pinned by
+    test_every_readout_has_the_tables_width_and_layout).  All exact.  Then, for GibbsRtIrtNull at nIter = 9 with all four entries of Sigp drawn, the NaN entries
+    of the diagnostics of Post.qr are exactly its zero columns."""
+    L = pkg._lib
+    N, J = _RN, _RJ
+    start = dict(theta=0.1 + 0.01 * np.arange(N)) if model == "mlirt" else dict(theta=0.1 + 0.01 * np.arange(N), zeta=-0.3 + 0.02 * np.arange(N))
+    eng = _readout_engine(model, precision, 4, F)[0]
+    eng.set_state(**start)          # (subjects that all start at zero leave the latent regression of zeta on theta nothing to estimate)
+    theta, zeta = [], []
+    for _ in range(4):
+        eng.run(1)
+        st = eng.get_state(which=("theta", "zeta"))
+        theta.append(st["theta"])
+        zeta.append(st["zeta"])
+    item = eng.item_trace()
+    assert item.shape == (4, _ITEM_WIDTH[model, F]) and np.all(np.isfinite(item))
+    ra = eng.trace(L.TRACE_RA)[:, :, 0]
+    assert ra.shape == (4, N + 2 * J)
+    assert np.array_equal(ra[:, :N], np.array(theta)) and len({tuple(v) for v in theta}) == 4
+    assert np.array_equal(ra[:, N:N + J], item[:, 0:J]) and np.array_equal(ra[:, N + J:], item[:, J:2 * J])
+    if model == "mlirt":
+        assert eng.trace(L.TRACE_RT).size == 0
+    else:
+        rt = eng.trace(L.TRACE_RT)[:, :, 0]
+        assert rt.shape == (4, N + 2 * J)
+        assert np.array_equal(rt[:, :N], np.array(zeta)) and len({tuple(v) for v in zeta}) == 4
+        assert np.array_equal(rt[:, N:N + J], item[:, 2 * J:3 * J]) and np.array_equal(rt[:, N + J:], item[:, 3 * J:4 * J])
+    qr = eng.trace(L.TRACE_QR)[:, :, 0]
+    content = _QR_CONTENT[model, F]
+    assert qr.shape == (4, sum(n for _, _, n in content))
+    col = 0
+    for source, first, n in content:
+        if source == "item":
+            assert np.array_equal(qr[:, col:col + n], item[:, first:first + n]), (source, first, n)
+        elif source == "zero":
+            assert np.all(qr[:, col:col + n] == 0.0)
+        col += n
+    if model == "null":
+        assert np.all(qr[:, :2 * (F + 1)] == 0.0) and np.array_equal(qr[:, -4:], item[:, -4:]) and qr.shape[1] == 2 * (F + 1) + 4
+    # the item-level draws are all different from one another in every row, so a shifted or swapped item block cannot pass for the right one
+    drawn = 2 * J if model == "mlirt" else 4 * J
+    assert all(len(set(row[:drawn])) == drawn for row in item)
+    eng.close()
+    if model == "null":
+        eng = _readout_engine(model, precision, 9, F, cov2one=0)[0]          # (cov2one would pin Sigp's diagonal at 1: two more constant columns)
+        eng.set_state(**start)
+        eng.run(9)
+        ess, rhat = eng.diagnostics(L.TRACE_QR)
+        zero = np.arange(2 * (F + 1) + 4) < 2 * (F + 1)
+        assert np.array_equal(np.isnan(ess), zero) and np.array_equal(np.isnan(rhat), zero)
+        eng.close()
