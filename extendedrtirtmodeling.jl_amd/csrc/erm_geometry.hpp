@@ -43,10 +43,7 @@ struct Geom {
 
 // Small data sets -- up to this many cells, of at most this many items (every workgroup polls every workgroup's statistics row: ~5 J doubles each) -- run all
 // sweeps of an erm_run in one persistent launch of at most PERSIST_MAX_GRID workgroups (never more than one per CU) of at most PERSIST_THREADS threads
-#ifndef ERM_PERSIST_MAX_CELLS
-#define ERM_PERSIST_MAX_CELLS (1 << 17)
-#endif
-constexpr long long PERSIST_MAX_CELLS = ERM_PERSIST_MAX_CELLS;
+constexpr long long PERSIST_MAX_CELLS = 1 << 17;
 constexpr int PERSIST_MAX_ITEMS = 128;
 constexpr long long PERSIST_MAX_SUBJ = 6000;      // beyond it the subject phases of <= 64 workgroups outweigh the boundary saved (8 000 x 16: 27.6 against 26.3 us per sweep)
 constexpr int PERSIST_MAX_GRID = 64;

@@ -145,10 +145,7 @@ constexpr double LOG_2PI = 1.8378770664093454836;
 //             - sum_j G_j / sig2t_j - zz/2 sum_j 1/sig2t_j + sz sum_j lc_j / sig2t_j                     (linear in the statistics: every workgroup, from its own sums)
 // -- statistics the column phase accumulates anyway for the lambda / sig2t draws (tiny_items forms the same expansion).  The column phase loses the residual,
 // its square and the per-item constants of every cell (it is VALU-issue-bound), the head the logarithm of sig2t per item.  Same log-likelihood to ~1e-14.
-#ifndef ERM_RTLL_STATS
-#define ERM_RTLL_STATS 1
-#endif
-template <int MODEL, int PHASE> constexpr bool rtll_stats() { return ERM_RTLL_STATS != 0 && PHASE == 0 && (fam_rt(MODEL) || fam_lq(MODEL)); }
+template <int MODEL, int PHASE> constexpr bool rtll_stats() { return PHASE == 0 && (fam_rt(MODEL) || fam_lq(MODEL)); }
 constexpr int KB = 4;     // items per lane whose loads are in flight together in the row-sum phase
 
 // Stage-timing / counting diagnostics (early returns that leave GARBAGE results, PG attempt counters) exist only in a library built with
@@ -591,7 +588,7 @@ __device__ __forceinline__ void tiny_struct(const TinyArgs& T, double* par, cons
         if (lane == 0) par[par_off_derived(J)] = t;
     }
     if constexpr (rtll_stats<MODEL, 0>() && STEP == 0) {
-        // the part of this sweep's response-time log-likelihood that does not depend on the subjects (see ERM_RTLL_STATS): derived[1]
+        // the part of this sweep's response-time log-likelihood that does not depend on the subjects (see rtll_stats): derived[1]
         // (explicit fma everywhere in this statistic: every instantiation of the kernels must form the same bits, whatever the compiler would contract)
         double cc = 0.0;
         for (int jj = lane; jj < J; jj += 64) {
@@ -749,12 +746,9 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
                                                                                    // (the region holds nWaves * 4 * rows_per_wave >= 4 * rows_per_block values)
     // the per-item product of the cell streams' Philox blocks (philox4x32_10_vk_cell), one uint2 per item, in the two item arrays these models never read
     // (log sig2t: the response-time log-likelihood comes from statistics; rho: the Cross family's) -- 2 J reals = J uint2 in either engine
-#ifndef ERM_PHILOX_HOIST
-#define ERM_PHILOX_HOIST 1
-#endif
     // (not in the persistent small-data kernel: a workgroup draws about one cell per lane there, so the item products are not amortised and their two multiplications
     // sit in the head's dependent chain -- 1 000 x 15 GibbsMlIrt 13.6 against 13.4 us per sweep)
-    constexpr bool PHX = ERM_PHILOX_HOIST != 0 && !PERSIST && PHASE == 0 && !fam_cq(MODEL) && (MODEL == MLIRT || rtll_stats<MODEL, PHASE>());
+    constexpr bool PHX = !PERSIST && PHASE == 0 && !fam_cq(MODEL) && (MODEL == MLIRT || rtll_stats<MODEL, PHASE>());
     [[maybe_unused]] uint2* sh_phx = reinterpret_cast<uint2*>(sh_lsig);
     const int NV = nv_of(MODEL, A.nFeat);
     real* sh_val = sh_item + NITEMARR * JS + (size_t)nWaves * 4 * A.rows_per_wave;   // [rows_per_block][NV] per-subject values of the global statistics
@@ -939,7 +933,7 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
         sweep = c_sweep + 1u;
         ERM_DIAG_STOP(A, 30);
         trow = k_first ? prev_row : prev_row + 1u;
-        // log-likelihood of the sweep the last pass completed (+ the subject-free part its tiny step left in the parameter block: ERM_RTLL_STATS)
+        // log-likelihood of the sweep the last pass completed (+ the subject-free part its tiny step left in the parameter block: rtll_stats)
         if (writer && tid == 0 && !k_first && T.tr_ll) T.tr_ll[prev_row] = st0[NS0 - 1] + (rtll_stats<MODEL, PHASE>() ? lp[par_off_derived(J) + 1] : 0.0);
         // item draws now; the structural chain (beta_t -> Sigma_p_t, ~7 us of dependent fp64 work on one wave) runs on wave 0 AFTER the
         // staging barrier below, concurrently with the other waves' row sums, which do not need it (see `sh_ready`)
@@ -968,7 +962,7 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
             for (int j = tid - ioff - rt_off; tid >= ioff + rt_off && j < J; j += jstep) {
                 const double lam = lp[2 * J + j], sg = lp[3 * J + j];
                 sh_lamc[j] = (real)(lam - lcst[cst_off_m(J) + j]); sh_isig[j] = (real)(1.0 / sg);
-                if constexpr (!rtll_stats<MODEL, PHASE>() && !PHX) sh_lsig[j] = (real)log(sg);
+                if constexpr (!rtll_stats<MODEL, PHASE>() && !PHX) sh_lsig[j] = (real)log(sg);      // (the persistent GibbsMlIrt kernel only: nothing reads it there, and the kernel's assembly moves without it)
             }
             if (tid == 0) { *reinterpret_cast<int*>(sh_struct + 5) = 0; *reinterpret_cast<unsigned int*>(sh_struct + 7) = 0u; }       // sh_ready, row-group counter
             for (int e = tid; e < nWaves * NG; e += nthr) sh_gacc[e] = 0.0;
@@ -986,11 +980,10 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
     for (int j = threadIdx.x; j < J; j += blockDim.x) {
         const double a = parsrc[j], b = parsrc[J + j], lam = parsrc[2 * J + j], sg = parsrc[3 * J + j], rho = parsrc[4 * J + j];
         sh_a[j] = (real)a; sh_b[j] = (real)b; sh_a2[j] = (real)(a * a); sh_a2b[j] = (real)(a * a * b);
-        sh_lamc[j] = (real)(lam - (FUSED ? lcst[cst_off_m(J) + j] : A.cst[cst_off_m(J) + j])); sh_isig[j] = (real)(1.0 / sg);
+        sh_lamc[j] = (real)(lam - A.cst[cst_off_m(J) + j]); sh_isig[j] = (real)(1.0 / sg);
         if constexpr (PHX) sh_phx[j] = philox_item_product((uint32_t)j, sweep + 1u, (uint32_t)A.seed); else { sh_lsig[j] = (real)log(sg); sh_rho[j] = (real)rho; }
     }
-    if (FUSED && threadIdx.x == 0) *sh_ready = 0;
-    if (!FUSED && threadIdx.x < 8 + 2 * PMAX) {
+    if (threadIdx.x < 8 + 2 * PMAX) {
         double v = 0.0;
         if (threadIdx.x < 4) v = parsrc[par_off_sigp(J) + threadIdx.x];
         else if (threadIdx.x >= 8) v = parsrc[par_off_beta(J) + threadIdx.x - 8];
@@ -1050,13 +1043,10 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
         if (lane == 0) g = atomicAdd(reinterpret_cast<unsigned int*>(sh_struct + 7), 1u);
         return (int)__builtin_amdgcn_readfirstlane(g);
     };
-#ifndef ERM_PAIRS_F32
-#define ERM_PAIRS_F32 1       // round 3: the fp32 engine takes item pairs too (8-byte loads; fewer address computations per cell): 53.4 -> 52.9 us in an A/B
-#endif
-    if (A.mode == 1 && (sizeof(real) == 8 || ERM_PAIRS_F32) && (J & 1) == 0) {
-        // fp64 engine, even test lengths: a lane takes PAIRS of neighbouring items (2s, 2s+1), (2(s+W), ...), so that omega and logT come in
-        // 16-byte loads and a wave-instruction covers whole 128-byte lines of a row instead of 64-byte halves (120.4 -> 113.9 us per sweep;
-        // the fp32 engine's 8-byte pairs gained nothing and stay on the scalar path)
+    if (A.mode == 1 && (J & 1) == 0) {
+        // even test lengths, both engines: a lane takes PAIRS of neighbouring items (2s, 2s+1), (2(s+W), ...).  fp64: omega and logT come in 16-byte loads
+        // and a wave-instruction covers whole 128-byte lines of a row instead of 64-byte halves (120.4 -> 113.9 us per sweep).  fp32: 8-byte loads and
+        // fewer address computations per cell (round 3: 53.4 -> 52.9 us in an A/B)
         using real2 = typename std::conditional<sizeof(real) == 8, double2, float2>::type;
         const int P = J >> 1, IPP = (P + W - 1) / W;
         // the loop twice: with the item arrays' stride a compile-time constant (test lengths up to ITEM_STRIDE: the arrays' reads share one address) and as a variable
@@ -1113,7 +1103,7 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
             if (rowok && s == 0) { real* o = sh_rs + 3 * qrow; o[0] = s0; o[1] = s1; o[2] = s2; }
         }
         };
-        if (ITEM_STRIDE > 0 && JS == ITEM_STRIDE) pair_sums(std::integral_constant<int, ITEM_STRIDE>{}); else pair_sums(JS);
+        if (JS == ITEM_STRIDE) pair_sums(std::integral_constant<int, ITEM_STRIDE>{}); else pair_sums(JS);
     } else if (A.mode == 1) {
         for (;;) {
             const int g = next_group();
@@ -1341,12 +1331,10 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
         };
         if (active) cell_words(rr, j);
         [[maybe_unused]] unsigned int n_att = 0, n_trip = 0;
-#ifndef ERM_PG_VKEYS
-#define ERM_PG_VKEYS 20      // (8 until the end of round 4; with two rounds of the block hoisted out of the attempt the loop has the registers for all of them: 67.8 -> 67.6 us, 6 / 12 lose)
-#endif
-        constexpr int NVK = PERSIST ? 20 : ERM_PG_VKEYS;         // round keys of the attempts' Philox blocks kept in vector registers (philox4x32_10_vk)
-        uint32_t pgk[NVK > 0 ? NVK : 1];
-        philox_vector_keys<NVK>((uint32_t)A.seed, (uint32_t)(A.seed >> 32), pgk);
+        // all twenty round keys of the attempts' Philox blocks live in vector registers (philox4x32_10_vk; 8 until the end of round 4: with two rounds of
+        // the block hoisted out of the attempt the loop has the registers for all of them, 67.8 -> 67.6 us, 6 / 12 lose)
+        uint32_t pgk[20];
+        philox_vector_keys((uint32_t)A.seed, (uint32_t)(A.seed >> 32), pgk);
         // (letting a wave whose queue ran dry serve other waves' queues was tried: the hardware favours a SIMD's oldest wave, so the
         // four waves of a SIMD finish up to 17 us apart -- but the phase is VALU-throughput-bound, the SIMD is busy until the last
         // one ends either way, and the stealing logic only added instructions: 78.5 vs 75.3 us per sweep)
@@ -1361,8 +1349,8 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
 #endif
             if (active) {
                 uint32_t w0, w1, w2, w3;
-                if constexpr (PHX) philox4x32_10_vk_cell<NVK>(ph_hi, ph_m2, ph_m3, c3 | att, ph_n1k, (uint32_t)A.seed, (uint32_t)(A.seed >> 32), pgk, w0, w1, w2, w3);
-                else philox4x32_10_vk<NVK>((uint32_t)(qrow0 + rr) + A.row_base, (uint32_t)j, sweep + 1u, c3 | att, (uint32_t)A.seed, (uint32_t)(A.seed >> 32), pgk, w0, w1, w2, w3);
+                if constexpr (PHX) philox4x32_10_vk_cell(ph_hi, ph_m2, ph_m3, c3 | att, ph_n1k, pgk, w0, w1, w2, w3);
+                else philox4x32_10_vk((uint32_t)(qrow0 + rr) + A.row_base, (uint32_t)j, sweep + 1u, c3 | att, pgk, w0, w1, w2, w3);
                 real w;
                 bool acc_, unsure;
                 if constexpr (sizeof(real) == 8) acc_ = pg1_attempt_f64<true>(z, w0, w1, w2, w3, sh_pgf[kb], sh_pgc[kb], logtab, w, unsure);
@@ -1420,7 +1408,7 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
             real w_h = real(0);
             if (work) {
                 uint32_t w0, w1, w2, w3;
-                philox4x32_10_vk<NVK>((uint32_t)(qrow0 + rr_h) + A.row_base, (uint32_t)j_h, sweep + 1u, c3 | att_h, (uint32_t)A.seed, (uint32_t)(A.seed >> 32), pgk, w0, w1, w2, w3);
+                philox4x32_10_vk((uint32_t)(qrow0 + rr_h) + A.row_base, (uint32_t)j_h, sweep + 1u, c3 | att_h, pgk, w0, w1, w2, w3);
                 bool unsure;
                 if constexpr (sizeof(real) == 8) acc_h = pg1_attempt_f64<true>(z_h, w0, w1, w2, w3, sh_pgf[kb_h], sh_pgc[kb_h], logtab, w_h, unsure);
                 else { acc_h = pg1_attempt(z_h, w0, w1, w2, w3, sh_pgf[kb_h], w_h); unsure = !(z_h < (real)PG_ZMAX); }
@@ -1548,7 +1536,7 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
             accg = bfly_sum(accg, 1, 64);
             if (tl == 0) sh_gacc[g] = accg;          // wave 0's slot of the per-wave table summed by the epilogue (the other waves' stay 0)
             if constexpr (rtll_stats<MODEL, PHASE>()) {
-                // ERM_RTLL_STATS: this workgroup's share of the response-time log-likelihood that is linear in sum zeta and sum zeta^2
+                // rtll_stats: this workgroup's share of the response-time log-likelihood that is linear in sum zeta and sum zeta^2
                 const int g_sz = fam_rt(MODEL) ? p : 2 * p + 5, g_zz = fam_rt(MODEL) ? 2 * p + 2 : 2 * p + 6;
                 if (A.mode == 1 && g == g_sz) {
                     double sl = 0.0;
@@ -1582,6 +1570,9 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
                 const bool jv = j0 < J;
                 const int jc = jv ? j0 : 0;
                 const double a0 = sh_a[jc], a1 = sh_a[jc + 1], b0 = sh_b[jc], b1 = sh_b[jc + 1];
+                // The response-time log-likelihood comes from the statistics (rtll_stats), so nothing reads lamc0/1, lsig0/1, rtq or the cell lambda's lamc / isig
+                // parameters any more (in the fp32 loop below: lamc0/1, lconst and the same two parameters).  Each of them stays because taking it out, unread
+                // as it is, moves the assembly of persistent kernels of the response-time models (a commuted v_add_u32, renamed registers): checked group by group.
                 constexpr bool RTLL = rtll_stats<MODEL, PHASE>();      // the response-time log-likelihood comes from the statistics: no residual per cell
                 [[maybe_unused]] const double lamc0 = RTLL ? 0.0 : (double)sh_lamc[jc], lamc1 = RTLL ? 0.0 : (double)sh_lamc[jc + 1];
                 [[maybe_unused]] const double isig0 = sh_isig[jc], isig1 = sh_isig[jc + 1];
@@ -1590,11 +1581,10 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
 #pragma unroll
                 for (int q = 0; q < NSTAT; ++q) { S0[q] = 0.0; S1[q] = 0.0; }
                 // The phase is VALU-issue-bound (tools/stage_budget.py: 7.5 M wave-instructions, 14 of its 16 us), so the per-cell work is pared down:
-                // statistics go straight into the fp64 accumulators by fma (theta^2 and theta/2 once per subject); the cell log-likelihood
-                //   y eta - log(1 + e^eta) - (log 2 pi + log sig2t_j + er^2 / sig2t_j) / 2
-                // is kept as three per-lane partial sums -- -max(s, 0) with s = eta or -eta by y, the PRODUCT of the factors 1 + e^{-|eta|} (each in
-                // (1, 2]: one logarithm per lane at the end, or every 512 factors), and sum er^2 / sig2t_j -- and the per-item constants enter
-                // once, times the number of cells.
+                // statistics go straight into the fp64 accumulators by fma (theta^2 and theta/2 once per subject); the cell's response log-likelihood
+                //   y eta - log(1 + e^eta)
+                // is kept as two per-lane partial sums -- -max(s, 0) with s = eta or -eta by y, and the PRODUCT of the factors 1 + e^{-|eta|} (each in
+                // (1, 2]: one logarithm per lane at the end, or every 512 factors); the response-time part comes from the statistics, no residual per cell.
                 double lmax = 0.0, bprod = 1.0, rtq = 0.0, asum = 0.0;
                 int ncells = 0, nfac = 0, ny0 = 0, ny1 = 0;
                 for (int bt = nbatch - 1 - ((nbatch - 1 - wave) % nWaves + nWaves) % nWaves; bt >= 0; bt -= nWaves) {      // a batch: 2 slots x 2 half-waves = 4 subjects, 4 cells per lane
@@ -1634,10 +1624,6 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
                                 asum += fabs(eta);
                                 ny += y ? 1 : 0;
                                 bprod *= 1.0 + fm::exp_neg_ll(fabs(eta));
-                                if constexpr (!RTLL && (fam_rt(MODEL) || fam_lq(MODEL))) {
-                                    const double er = c + ze - lamc;
-                                    rtq = fma(er * er, isig, rtq);
-                                }
                             }
                         };
                         cell(wv[u].x, (yv[u] & 0xFFu) != 0u, cv[u].x, a0, b0, lamc0, isig0, S0, ny0);
@@ -1652,7 +1638,6 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
                     const double hn = 0.5 * (double)ncells;
                     const double sketa = fma(a0, fma(-b0, (double)ny0 - hn, S0[3]), a1 * fma(-b1, (double)ny1 - hn, S1[3]));      // sum kappa eta of this lane's cells (S[3]: before the half-waves are added)
                     llc = -(fma(0.5, asum, -sketa) + lmax + fm::log(bprod, logtab));
-                    if constexpr (!RTLL && (fam_rt(MODEL) || fam_lq(MODEL))) llc -= 0.5 * (rtq + (double)ncells * (2.0 * LOG_2PI + lsig0 + lsig1));
                 }
 #pragma unroll
                 for (int q = 0; q < NSTAT; ++q) { S0[q] += __shfl_xor(S0[q], 32, 64); S1[q] += __shfl_xor(S1[q], 32, 64); }
@@ -1706,7 +1691,6 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
                     float bs0[NSTAT], bs1[NSTAT], bl = 0.0f;
 #pragma unroll
                     for (int q = 0; q < NSTAT; ++q) { bs0[q] = 0.0f; bs1[q] = 0.0f; }
-                    int nrow = 0;
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
                         if (!okv[u]) continue;
@@ -1717,20 +1701,14 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
                             {   // (in every mode, as in the fp64 loop: no branch per cell)
                                 const float eta = a * (th - b);
                                 float t = (y ? eta : 0.0f) - log1pexp_r(eta);
-                                if constexpr (!RTLL && (fam_rt(MODEL) || fam_lq(MODEL))) {
-                                    const float er = c + ze - lamc;
-                                    t = fmaf(-0.5f * er * er, isig, t);
-                                }
                                 bl += t;
                             }
                         };
                         cell(wv[u].x, (yv[u] & 0xFFu) != 0u, cv[u].x, a0, b0, lamc0, isig0, bs0);
                         cell(wv[u].y, (yv[u] >> 8) != 0u, cv[u].y, a1, b1, lamc1, isig1, bs1);
-                        ++nrow;
                     }
 #pragma unroll
                     for (int q = 0; q < NSTAT; ++q) { S0[q] += (double)bs0[q]; S1[q] += (double)bs1[q]; }
-                    if constexpr (!RTLL) { if (A.mode == 1 && (fam_rt(MODEL) || fam_lq(MODEL))) bl = fmaf(-0.5f * (float)nrow, lconst, bl); }
                     llc += (double)bl;
                 }
 #pragma unroll
@@ -1803,10 +1781,6 @@ __global__ void __launch_bounds__(PERSIST ? PERSIST_THREADS : max_block_threads(
                             t = (y ? eta : 0.0) - (eta > 0.0 ? eta : 0.0);
                             bprod *= 1.0 + fm::exp_neg_ll(fabs(eta));
                         } else t = (y ? eta : real(0)) - log1pexp_r(eta);
-                        if constexpr (!rtll_stats<MODEL, PHASE>() && (fam_rt(MODEL) || fam_lq(MODEL))) {
-                            const real er = c + ze - lamc;
-                            t += real(-0.5) * ((real)LOG_2PI + lsig + er * er * isig);
-                        }
                         bl += t;
                     }
                     if constexpr (fam_cq(MODEL)) {
@@ -2022,7 +1996,7 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_kernel(TinyArgs T)
     if (STEP == 0 && tid == 0 && !first && T.tr_ll) {
         double llv = st0[NS0 - 1];
         if (fam_cq(MODEL)) llv += st1[NS1 - 1];
-        if (rtll_stats<MODEL, 0>()) llv += lp[par_off_derived(J) + 1];         // ERM_RTLL_STATS: the subject-free part, left by the tiny step that drew the sweep's lambda / sig2t
+        if (rtll_stats<MODEL, 0>()) llv += lp[par_off_derived(J) + 1];         // rtll_stats: the subject-free part, left by the tiny step that drew the sweep's lambda / sig2t
         T.tr_ll[prev_row] = llv;
     }
     if (T.mode == 1) return;
@@ -2032,488 +2006,7 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_kernel(TinyArgs T)
     tiny_publish<MODEL, STEP>(T, lp, sweep, row, tid, TINY_THREADS);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Convergence diagnostics on the device-resident traces (the reference pulls Post.ra/rt/qr through MCMCChains'
-// ess_rhat in checkConvergence, src/SimTools.jl:419-443): split-R-hat and the effective sample size by Geyer's initial monotone
-// sequence over the split chains (Gelman et al., BDA3 sec. 11.4-11.5; the non-rank-normalised estimator), one thread per parameter.
-//   draws: trace row (m * nChain + l), m >= nBurnin; each chain l is split into its first and last n = floor((nIter - nBurnin)/2)
-//   draws  => M = 2 nChain sequences.  W = mean of the sequences' variances (n-1 denominator), B/n = variance of their means,
-//   var+ = (n-1)/n W + B/n, rhat = sqrt(var+ / W), rho_t = 1 - (W - mean_c acov_c(t)) / var+ with acov_c(t) = 1/n sum_i (x_i - mu_c)
-//   (x_{i+t} - mu_c); P_k = rho_{2k} + rho_{2k+1} summed while positive and made non-increasing; ess = M n / (-1 + 2 sum_k P_k).
-// A parameter that never moves (beta[1] = 0, Sigma_p[1,1] = 1 ...) gets NaN, as MCMCChains reports it.  "Never moves" means that every used draw (the 2 n
-// draws of every chain; an odd length leaves the middle one out) equals the first one: decided on the draws themselves, not by W > 0, because the rounded mean of n
-// copies of a non-dyadic constant is not that constant and leaves a W of rounding noise (gibbs.ess_rhat carries the same rule).  The sampler's constant columns hold 0
-// or 1, whose sums are exact, so on a device trace the two rules agree: the difference shows on host traces only.
-// The sum over k stops BEFORE the first P_k that is not positive, P_0 included: a column whose first pair sum is not positive gets -M n (sum = 0, so the denominator
-// is -1); x_i = (-1)^i is such a column.  More generally the value is negative whenever the pair sums add up to less than 1 / 2, which sampler traces with n = 4 .. 8
-// draws per sequence do show.  The estimator is left as it is; a caller that counts "ESS defined" counts such a column too.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int DIAG_MAXSEQ = 32;
-// Subject-sharded chains: a device's reduced statistics (the nb group rows of a pass) summed into ONE row, the unit the devices
-// all-gather before every tiny step; reduce_rows order, so the result does not depend on the launch geometry of this kernel
-__global__ void __launch_bounds__(256) shard_pack_kernel(const double* gslab, int nb, int NS, double* out)
-{
-    reduce_rows(gslab, nb, NS, out, (int)threadIdx.x, (int)blockDim.x);
-}
-
-// erm_set_data on the device.  The caller's arrays are column-major (Julia): uploaded as they are, then
-//   colstats_cm_kernel : one workgroup per column j: K0_j = sum_i (Y_ij - 1/2), sum_i logT_ij (fp64, fixed order), validity flags
-//                        (bit 0: a Y that is not 0/1, bit 1: a non-finite logT);
-//   to_rows_kernel     : 32 x 32 tiles through LDS, dst[i][j] = (T)(src[j][i] - shift[j]) -- Y bytes, logT centred by its column mean
-//                        (subtracted in fp64 BEFORE the value is rounded to the engine's cell type), X;
-//   colsq_kernel       : per-workgroup partial sums over rows of the squared centred values ([block][J]).
-__global__ void __launch_bounds__(256) colstats_cm_kernel(const uint8_t* Y, const double* L, long long N, int has_l, double* out, int J, unsigned int* flags)
-{
-    const int j = blockIdx.x, tid = threadIdx.x;
-    double sk = 0.0, sl = 0.0;
-    unsigned int bad = 0u;
-    for (long long i = tid; i < N; i += 256) {
-        const uint8_t y = Y[(size_t)j * N + i];
-        bad |= (y > 1) ? 1u : 0u;
-        sk += (double)y - 0.5;
-        if (has_l) { const double v = L[(size_t)j * N + i]; bad |= (fabs(v) < 1.79e308) ? 0u : 2u; sl += v; }
-    }
-    __shared__ double shk[256], shl[256];
-    shk[tid] = sk; shl[tid] = sl;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { shk[tid] += shk[tid + w]; shl[tid] += shl[tid + w]; } __syncthreads(); }
-    if (tid == 0) { out[j] = shk[0]; out[J + j] = shl[0]; }
-    if (bad) atomicOr(flags, bad);
-}
-template <typename S, typename T>
-__global__ void __launch_bounds__(256) to_rows_kernel(const S* src, long long N, int J, const double* shift, T* dst)
-{
-    __shared__ double tile[32][33];
-    const long long i0 = (long long)blockIdx.x * 32;
-    const int j0 = (int)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int r = ty; r < 32; r += 8) {
-        const int j = j0 + r; const long long i = i0 + tx;
-        if (j < J && i < N) tile[r][tx] = (double)src[(size_t)j * N + i] - (shift ? shift[j] : 0.0);
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const long long i = i0 + r; const int j = j0 + tx;
-        if (i < N && j < J) dst[(size_t)i * J + j] = (T)tile[tx][r];
-    }
-}
-template <typename real>
-__global__ void __launch_bounds__(128) colsq_kernel(const real* C, long long N, int J, double* part)
-{
-    const long long per = (N + gridDim.x - 1) / gridDim.x, r0 = (long long)blockIdx.x * per, r1 = (r0 + per < N) ? r0 + per : N;
-    for (int j = threadIdx.x; j < J; j += blockDim.x) {
-        double sq = 0.0;
-        for (long long i = r0; i < r1; ++i) { const double c = (double)C[(size_t)i * J + j]; sq += c * c; }
-        part[(size_t)blockIdx.x * J + j] = sq;
-    }
-}
-
-// Post.ra / rt / qr in Julia layout: the device keeps a subject-level trace as [row = m * nChain + l][subject] (coalesced stores, one row per
-// sweep); Julia's array is [nIter][width][nChain] with the iteration fastest.  dst[i * nIter + m] = (double) src[(m * nChain + l) * ld + i] for ONE
-// chain l, 32 x 32 tiles through LDS so that both the reads (along subjects) and the writes (along iterations) are coalesced.
-template <typename T>
-__global__ void __launch_bounds__(256) trace_transpose_kernel(const T* src, long long ld, long long ncol, int nIter, int nChain, int l, double* dst)
-{
-    __shared__ double tile[32][33];
-    const long long i0 = (long long)blockIdx.x * 32;
-    const int m0 = (int)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
-    for (int r = ty; r < 32; r += 8) {
-        const int m = m0 + r; const long long i = i0 + tx;
-        if (m < nIter && i < ncol) tile[r][tx] = (double)src[((long long)m * nChain + l) * ld + i];
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const long long i = i0 + r; const int m = m0 + tx;
-        if (i < ncol && m < nIter) dst[i * nIter + m] = tile[tx][r];
-    }
-}
-
-// dst[i] += src[i] (chain farms: post-burn-in sums of the chains that share a device, before the RCCL all-reduce over the devices)
-__global__ void __launch_bounds__(256) acc_kernel(double* dst, const double* src, long long n)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dst[i] += src[i];
-}
-
-template <typename T>
-__global__ void diag_kernel(const T* tr, long long ncol, long long ld, int nIter, int nChain, int nBurnin, double* ess, double* rhat)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= ncol) return;
-    const int Tn = nIter - nBurnin, n = Tn / 2, M = 2 * nChain;
-    auto at = [&](int c, int i) -> double {                      // draw i of split sequence c
-        const int l = c >> 1, m0 = nBurnin + ((c & 1) ? Tn - n : 0);
-        return (double)tr[((long long)(m0 + i) * nChain + l) * ld + k];
-    };
-    double mu[DIAG_MAXSEQ];
-    double W = 0.0, mbar = 0.0;
-    const double x0 = at(0, 0);
-    bool moves = false;                                          // some used draw differs from the first one
-    for (int c = 0; c < M; ++c) {
-        double s1 = 0.0;
-        for (int i = 0; i < n; ++i) { const double x = at(c, i); moves = moves || (x != x0); s1 += x; }
-        mu[c] = s1 / n; mbar += mu[c];
-        double s2 = 0.0;
-        for (int i = 0; i < n; ++i) { const double d = at(c, i) - mu[c]; s2 += d * d; }
-        W += s2 / (n - 1);
-    }
-    W /= M; mbar /= M;
-    double Bn = 0.0;
-    for (int c = 0; c < M; ++c) Bn += (mu[c] - mbar) * (mu[c] - mbar);
-    Bn /= (M - 1);
-    const double varp = W * (n - 1) / n + Bn;
-    if (!moves) { ess[k] = __builtin_nan(""); rhat[k] = __builtin_nan(""); return; }
-    rhat[k] = sqrt(varp / W);
-    auto rho = [&](int t) -> double {
-        double a = 0.0;
-        for (int c = 0; c < M; ++c) {
-            double s = 0.0;
-            for (int i = 0; i + t < n; ++i) s += (at(c, i) - mu[c]) * (at(c, i + t) - mu[c]);
-            a += s / n;
-        }
-        return 1.0 - (W - a / M) / varp;
-    };
-    double sum = 0.0, prev = 1e300;
-    for (int t = 0; t + 1 < n; t += 2) {
-        double P = (t == 0 ? 1.0 - (W - W * (n - 1) / n) / varp : rho(t)) + rho(t + 1);
-        if (!(P > 0.0)) break;
-        if (P > prev) P = prev;
-        prev = P;
-        sum += P;
-    }
-    ess[k] = (double)M * n / (-1.0 + 2.0 * sum);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Synthetic data on the device: the generators of src/SimTools.jl -- setDataRtIrt :149-178, setDataRtIrtNull
-// :117-144, setDataMlIrt :349-368, setDataRtIrtCross :220-255, setDataRtIrtLatent :304-343 -- written straight into the engine's
-// resident buffers, one thread per subject.  Streams (DATA_SUBJ, i) / (DATA_CELL, i, j) of the data seed: like the host generators,
-// this is the reference's distribution, not Julia's Random.seed! stream.
-//   gen 0 MlIrt : X[:,1] ~ Bernoulli(1/2), X[:,2:] ~ N(0,1), theta ~ N(X beta, 1)
-//   gen 1 RtIrt : X ~ N(0,1), (theta, zeta) = X beta + N2(0, Sigp), logT ~ N(lambda_j - zeta_i, sig2t_j) truncated to (0, inf)
-//   gen 2 Null  : (theta, zeta) ~ N2(0, Sigp), logT as RtIrt
-//   gen 3 Cross : (theta, zeta) ~ N2(0, Sigp), logT = lambda_j - zeta_i - theta_i rho_j + e
-//   gen 4 Latent: theta ~ N(0,1), X ~ N(0,1), zeta = [X theta] beta + e, logT = lambda_j - zeta_i + N(0,1)
-//   e ("noise"): 0 N(0, 0.3), 1 t_5, 2 Gamma(1/2, 1) - 1   (the 0.3 belongs to the normal type only: src/SimTools.jl:238-247)
-// Y_ij ~ Bernoulli(logistic(a_j (theta_i - b_j))) always.  logT is written raw; center_kernel subtracts the column means afterwards.
-// ---------------------------------------------------------------------------------------------------------------------
-struct GenArgs {
-    uint8_t* Y; void* C; void* X; double* theta; double* zeta;   // C, X in the engine's cell type
-    const double* truth;       // a[J] b[J] lambda[J] sig2t[J] rho[J] | Sigp chol L00 L10 L11 | beta (RtIrt: [F][2] row-major; MlIrt [F]; Latent [F+1])
-    long long N; int J, F, gen, noise; uint64_t seed;
-};
-__device__ inline double gen_noise(Stream& s, int kind)      // src/SimTools.jl:238-247, 322-328: Normal(0, 0.3) | TDist(5) | Gamma(1/2, 1) - 1
-{
-    if (kind == 0) return 0.3 * normal<double>(s);
-    if (kind == 1) { const double zn = normal<double>(s); return zn / sqrt(chisq(s, 5.0) / 5.0); }
-    const double u = uniform<double>(s);
-    const double g = gamma_mt(s, 1.5) * u * u;                            // Gamma(a) = Gamma(a + 1) U^(1/a), a = 1/2 (Marsaglia-Tsang needs a >= 1)
-    return g - 1.0;
-}
-template <typename real>
-__global__ void gen_kernel(GenArgs G)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= G.N) return;
-    const int J = G.J, F = G.F;
-    const double* a = G.truth, *b = a + J, *lam = b + J, *sg = lam + J, *rho = sg + J, *L = rho + J, *beta = L + 3;
-    real* X = reinterpret_cast<real*>(G.X);
-    real* C = reinterpret_cast<real*>(G.C);
-    Stream ss(G.seed, 0u, SITE_DATA_SUBJ, (uint32_t)i, 0u, 0u);
-    double mt = 0.0, mz = 0.0;
-    for (int f = 0; f < F; ++f) {
-        double x = normal<double>(ss);
-        if (G.gen == 0 && f == 0) x = uniform<double>(ss) < 0.5 ? 1.0 : 0.0;
-        const real xr = (real)x;                          // the model sees the stored value
-        X[(size_t)i * F + f] = xr;
-        if (G.gen == 0) mt += (double)xr * beta[f];
-        else if (G.gen == 1) { mt += (double)xr * beta[2 * f]; mz += (double)xr * beta[2 * f + 1]; }
-        else if (G.gen == 4) mz += (double)xr * beta[f];
-    }
-    const double z0 = normal<double>(ss), z1 = normal<double>(ss);
-    double th, ze;
-    if (G.gen == 0) { th = mt + z0; ze = 0.0; }
-    else if (G.gen == 4) { th = z0; ze = mz + th * beta[F] + gen_noise(ss, G.noise); }
-    else { th = mt + L[0] * z0; ze = mz + L[1] * z0 + L[2] * z1; }
-    G.theta[i] = th; G.zeta[i] = ze;
-    for (int j = 0; j < J; ++j) {
-        Stream sc(G.seed, 0u, SITE_DATA_CELL, (uint32_t)i, (uint32_t)j, 0u);
-        const double eta = a[j] * (th - b[j]);
-        G.Y[(size_t)i * J + j] = uniform<double>(sc) < 1.0 / (1.0 + exp(-eta)) ? 1 : 0;
-        if (G.gen == 0) continue;
-        double lt;
-        if (G.gen == 1 || G.gen == 2) lt = truncnorm0(sc, lam[j] - ze, sqrt(sg[j]));
-        else if (G.gen == 3) lt = lam[j] - ze - th * rho[j] + gen_noise(sc, G.noise);
-        else lt = lam[j] - ze + normal<double>(sc);
-        C[(size_t)i * J + j] = (real)lt;
-    }
-}
-// per-workgroup partial column sums of the generated data: [block][3][J] = sum kappa, sum logT, sum logT^2 (fp64), then x'x partials
-template <typename real>
-__global__ void colsum_kernel(const uint8_t* Y, const real* C, const real* X, long long N, int J, int F, int has_c, double* part)
-{
-    const long long per = (N + gridDim.x - 1) / gridDim.x, r0 = (long long)blockIdx.x * per, r1 = (r0 + per < N) ? r0 + per : N;
-    const int p = F + 1;
-    double* out = part + (size_t)blockIdx.x * (3 * J + p * p);
-    for (int j = threadIdx.x; j < J; j += blockDim.x) {
-        double sk = 0.0, s1 = 0.0, s2 = 0.0;
-        for (long long i = r0; i < r1; ++i) {
-            sk += (double)Y[(size_t)i * J + j] - 0.5;
-            if (has_c) { const double c = (double)C[(size_t)i * J + j]; s1 += c; s2 += c * c; }
-        }
-        out[j] = sk; out[J + j] = s1; out[2 * J + j] = s2;
-    }
-    for (int e = threadIdx.x; e < p * p; e += blockDim.x) {
-        const int u = e % p, v = e / p;
-        double t = 0.0;
-        for (long long i = r0; i < r1; ++i) {
-            const double xu = u == 0 ? 1.0 : (double)X[(size_t)i * F + u - 1], xv = v == 0 ? 1.0 : (double)X[(size_t)i * F + v - 1];
-            t += xu * xv;
-        }
-        out[3 * J + e] = t;
-    }
-}
-// logT -> logT - column mean, and the centred sums of squares per workgroup ([block][J])
-template <typename real>
-__global__ void center_kernel(real* C, long long N, int J, const double* mean, double* part)
-{
-    const long long per = (N + gridDim.x - 1) / gridDim.x, r0 = (long long)blockIdx.x * per, r1 = (r0 + per < N) ? r0 + per : N;
-    for (int j = threadIdx.x; j < J; j += blockDim.x) {
-        const double m = mean[j];
-        double sq = 0.0;
-        for (long long i = r0; i < r1; ++i) {
-            const double c = (double)C[(size_t)i * J + j] - m;
-            const real cr = (real)c;
-            C[(size_t)i * J + j] = cr;
-            sq += (double)cr * (double)cr;
-        }
-        part[(size_t)blockIdx.x * J + j] = sq;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// erm_run's bookkeeping in two small launches.  As separate stream operations (two host -> device copies of the counters, a fill of the tickets, three
-// device -> host copies at the end) they were ~45 us of device time per erm_run -- more than two microseconds per sweep of a 20-sweep call.
-//   run_begin_kernel : both copies of the chain's counters, the group tickets zeroed, the persistent launch's wait bound and test hook;
-//   run_end_kernel   : the counters of both buffers and the time-out word into PINNED HOST memory (visible to the host once the stream has drained).
-// ---------------------------------------------------------------------------------------------------------------------
-// (the call's parameters come from PINNED HOST memory the host fills before it enqueues the call: the kernel's arguments never change, so it can sit at the head of a
-// replayed graph that holds the whole call -- erm_run: whole_graph)
-struct RunParams { Ctl v; unsigned int tmo_ticks, tmo_fault; };
-__global__ void __launch_bounds__(256) run_begin_kernel(Ctl* c0, Ctl* c1, const RunParams* hp, unsigned int* gcnt, int n_gcnt)
-{
-    const int t = (int)threadIdx.x;
-    const RunParams rp = *hp;
-    if (t == 0) { *c0 = rp.v; *c1 = rp.v; }
-    for (int k = t; k < n_gcnt; k += (int)blockDim.x) gcnt[k] = (k == n_gcnt - 3) ? rp.tmo_ticks : ((k == n_gcnt - 2) ? rp.tmo_fault : 0u);      // [tickets | tmo flag, ticks, fault, pad]
-}
-__global__ void __launch_bounds__(64) run_end_kernel(const Ctl* c0, const Ctl* c1, const unsigned int* tmo, Ctl* host_out, unsigned int* host_tmo)
-{
-    if (threadIdx.x == 0) { host_out[0] = *c0; host_out[1] = *c1; *host_tmo = *tmo; }
-}
-// up to 10 device buffers copied by ONE launch: the state a persistent erm_run saves before it starts (and restores if the launch times out)
-struct CopySegs { const void* src[10]; void* dst[10]; unsigned long long bytes[10]; int n; };
-__global__ void __launch_bounds__(256) copy_segments_kernel(CopySegs S)
-{
-    const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gn = (size_t)gridDim.x * blockDim.x;
-    for (int k = 0; k < S.n; ++k) {
-        const size_t nb = (size_t)S.bytes[k], nw = nb / 16;                       // hipMalloc'd buffers: 256-byte aligned
-        const uint4* s = reinterpret_cast<const uint4*>(S.src[k]);
-        uint4* d = reinterpret_cast<uint4*>(S.dst[k]);
-        for (size_t i = gt; i < nw; i += gn) d[i] = s[i];
-        for (size_t i = nw * 16 + gt; i < nb; i += gn) reinterpret_cast<unsigned char*>(S.dst[k])[i] = reinterpret_cast<const unsigned char*>(S.src[k])[i];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// DIC on the device.  getDic (src/GibbsRtIrt.pl.jl:432-472, src/GibbsRtIrtCross.pl.jl:330-353, src/GibbsRtIrtLatent.pl.jl:342-365):
-//   Dhat = -2 logLik(Post.mean), Dbar = -2 mean(Post.logLike) over all iterations, pD = Dbar - Dhat, DIC = Dbar + pD.
-// Post.mean never leaves the device: the post-burn-in SUMS of the subject-level draws are resident (sum_theta / sum_zeta / sum_nu), the item-level
-// ones are summed from the resident item trace (item_sum_kernel, row order), and loglik_kernel evaluates the model's log-likelihood
-//   getLogLikelihoodMlIrt / RtIrt / RtIrtNull (src/GibbsRtIrt.pl.jl:195-204, 262-272, 351-362), ...Cross / CrossQr (src/GibbsRtIrtCross.pl.jl:158-170, 240-258),
-//   ...Latent / LatentQr (src/GibbsRtIrtLatent.pl.jl:151-162, 243-264)
-// at sums * inv over the resident data set.  Plain fp64 with libm's log1p / exp / log (this runs once per sample!, not per sweep); every thread adds its
-// terms in a fixed order, a workgroup's threads are summed by a fixed tree, the host adds the workgroups' partial sums in order: reproducible bit for bit.
-// `sum` layout (the chain farm's summary vector): [item-level trace columns: a b lambda sig2t | small part of qr][theta N][zeta N, response-time models][nu N or N*J].
-// ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) item_sum_kernel(const double* tr_item, long long wi, long long row0, long long row1, double* out)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= wi) return;
-    double t = 0.0;
-    for (long long r = row0; r < row1; ++r) t += tr_item[r * wi + k];
-    out[k] += t;
-}
-// sum of the first n entries of the log-likelihood trace: thread t adds entries t, t + 256, ... in order, then a fixed tree
-__global__ void __launch_bounds__(256) ll_trace_sum_kernel(const double* tr_ll, long long n, double* out)
-{
-    __shared__ double sh[256];
-    double t = 0.0;
-    for (long long r = threadIdx.x; r < n; r += 256) t += tr_ll[r];
-    sh[threadIdx.x] = t;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
-    if (threadIdx.x == 0) *out = sh[0];
-}
-struct LogLikArgs {
-    const uint8_t* Y; const void* C; const void* X;      // resident data set: Y u8 [N][J], centred logT and X in the engine's cell type, row-major
-    const double* cm;                                     // column means of logT [J]
-    const double* sum; double inv;                        // Post.mean = sum * inv
-    long long N; int J, F, model;                         // F = covariate columns the kernels see
-    long long off_theta, off_zeta, off_nu;                // offsets into `sum` (off_zeta / off_nu < 0: absent)
-    double k1, k2;
-    long long rows_per_block;
-    double* part;                                         // [gridDim.x]
-};
-__device__ inline double ll_log1pexp(double x) { return x > 0.0 ? x + log1p(exp(-x)) : log1p(exp(x)); }
-template <typename real>
-__global__ void __launch_bounds__(256) loglik_kernel(LogLikArgs D)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double* sa = reinterpret_cast<double*>(smem);        // a b lambda sig2t rho [5][J] | Sigp [4] | beta [2 PMAX]
-    const int J = D.J, F = D.F, p = F + 1, M = D.model, tid = (int)threadIdx.x;
-    double* sb = sa + J, *sl = sa + 2 * J, *sg = sa + 3 * J, *sr = sa + 4 * J, *sS = sa + 5 * J, *sbeta = sS + 4;
-    __shared__ double red[256];
-    for (int e = tid; e < 4 * J; e += 256) sa[e] = D.sum[e] * D.inv;
-    const double* q = D.sum + 4 * J;                      // the small part of qr (tiny_publish's order)
-    // the small part's offsets and beta's slots come from the per-model table (erm_model.hpp); F is the number of columns the kernels see
-    for (int j = tid; j < J; j += 256) sr[j] = model_traits(M).rho ? q[j] * D.inv : 0.0;
-    if (tid < 4) sS[tid] = !model_traits(M).rt ? (tid == 0 || tid == 3 ? 1.0 : 0.0) : q[qr_sigp_off(M, J, F) + tid] * D.inv;
-    if (tid < 2 * PMAX) { const int u = beta_slot_src(model_traits(M).beta, F, tid); sbeta[tid] = u >= 0 ? q[u] * D.inv : 0.0; }
-    __syncthreads();
-    const real* C = reinterpret_cast<const real*>(D.C);
-    const real* X = reinterpret_cast<const real*>(D.X);
-    const long long r0 = (long long)blockIdx.x * D.rows_per_block, r1 = (r0 + D.rows_per_block < D.N) ? r0 + D.rows_per_block : D.N;
-    const long long ncell = (r1 > r0 ? r1 - r0 : 0) * J;
-    double ll = 0.0;
-    const bool qw = M == CROSSQR;                         // per-cell quantile weights
-    for (long long c = tid; c < ncell; c += 256) {
-        const long long i = r0 + c / J;
-        const int j = (int)(c % J);
-        const size_t e = (size_t)i * J + j;
-        const double th = D.sum[D.off_theta + i] * D.inv;
-        const double eta = sa[j] * (th - sb[j]);
-        ll += (D.Y[e] ? eta : 0.0) - ll_log1pexp(eta);
-        if (M != MLIRT) {
-            const double ze = D.sum[D.off_zeta + i] * D.inv;
-            const double lt = (double)C[e] + D.cm[j];
-            double mu = sl[j] - ze, var = sg[j];
-            if (fam_cq(M)) {
-                const double nu = qw ? D.sum[D.off_nu + (long long)e] * D.inv : 1.0;
-                mu += -th * sr[j] + D.k1 * nu;
-                var *= D.k2 * nu;
-            }
-            const double er = lt - mu;
-            ll += -0.5 * LOG_2PI - 0.5 * log(var) - 0.5 * er * er / var;
-        }
-    }
-    const double det = sS[0] * sS[3] - sS[1] * sS[2];
-    for (long long i = r0 + tid; i < r1; i += 256) {
-        const double th = D.sum[D.off_theta + i] * D.inv;
-        double xb0 = 0.0, xb1 = 0.0;
-        if (M == MLIRT || M == RTIRT || fam_lq(M)) {
-            xb0 = sbeta[0]; xb1 = sbeta[PMAX];
-            for (int f = 0; f < F; ++f) { const double x = (double)X[(size_t)i * F + f]; xb0 += x * sbeta[1 + f]; xb1 += x * sbeta[PMAX + 1 + f]; }
-        }
-        if (M == MLIRT) { const double e0 = th - xb0; ll += -0.5 * LOG_2PI - 0.5 * e0 * e0; continue; }
-        const double ze = D.sum[D.off_zeta + i] * D.inv;
-        if (fam_lq(M)) {
-            const double nu = (M == LATENTQR) ? D.sum[D.off_nu + i] * D.inv : 1.0;
-            const double mu = xb0 + th * sbeta[p] + D.k1 * nu, var = sS[3] * D.k2 * nu, er = ze - mu;
-            ll += -0.5 * LOG_2PI - 0.5 * log(var) - 0.5 * er * er / var;
-        } else {
-            const double e0 = th - (M == RTIRT ? xb0 : 0.0), e1 = ze - (M == RTIRT ? xb1 : 0.0);
-            const double quad = (sS[3] * e0 * e0 - (sS[1] + sS[2]) * e0 * e1 + sS[0] * e1 * e1) / det;
-            ll += -LOG_2PI - 0.5 * log(det) - 0.5 * quad;
-        }
-    }
-    red[tid] = ll;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
-    if (tid == 0) D.part[blockIdx.x] = red[0];
-}
-
-// checkConvergence's counts (src/SimTools.jl:427-437) from the device arrays of ess / rhat: c[0] columns with a defined ESS, c[1] of them with ESS > ess_min,
-// c[2] columns with a defined R-hat, c[3] of them with R-hat < rhat_max (integer atomics: order-independent)
-__global__ void __launch_bounds__(256) diag_count_kernel(const double* ess, const double* rhat, long long n, double ess_min, double rhat_max, unsigned long long* c)
-{
-    unsigned long long t[4] = {0ull, 0ull, 0ull, 0ull};
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
-        const double e = ess[k], r = rhat[k];
-        if (e == e) { ++t[0]; if (e > ess_min) ++t[1]; }
-        if (r == r) { ++t[2]; if (r < rhat_max) ++t[3]; }
-    }
-    for (int q = 0; q < 4; ++q) if (t[q]) atomicAdd(c + q, t[q]);
-}
-
-// n draws of the structural step's 2 x 2 inverse Wishart (erm_debug_invwishart): stream (seed, SIGP, i = k, sweep)
-__global__ void __launch_bounds__(256) invwishart_batch_kernel(uint64_t seed, uint32_t sweep, long long n, double df, double p0, double p1, double p2, double p3, double* out)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    Stream ss(seed, 0u, SITE_SIGP, (uint32_t)k, 0u, sweep);
-    double v3[3], S[4];
-    const double Psi[4] = { p0, p1, p2, p3 };
-    bartlett2_variates(ss, df, v3);
-    invwishart2(Psi, v3, S);
-    for (int e = 0; e < 4; ++e) out[4 * k + e] = S[e];
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// unit kernels for parity tests of the device samplers against the oracle
-// ---------------------------------------------------------------------------------------------------------------------
-template <typename real>
-__global__ void sample_batch_kernel(int which, uint64_t seed, uint32_t site, uint32_t sweep, long long n,
-                                    const double* par0, const double* par1, double* out, const double* pgtab)
-{
-    __shared__ double2 sh_logtab[128];
-    fm::fill_log_table(sh_logtab, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    Stream st(seed, 0u, site, (uint32_t)k, 0u, sweep);
-    double v = 0.0;
-    switch (which) {
-    case 15: v = fm::log(par0[k], sh_logtab); break;           // the table form of the cell path's logarithm
-    case 16: v = fm::cos2pi(par0[k]); break;
-    case 18: v = fm::exp_neg_ll(par0[k]); break;               // the cell log-likelihood's form of e^{-a}
-    case 19: v = fm::log_word((uint32_t)par0[k], sh_logtab); break;      // log((w + 1/2) 2^-32) of the word par0 stands for (the PG attempt's -log u1)
-    case 0: v = (double)uniform<real>(st); break;
-    case 1: v = (double)normal<real>(st); break;
-    case 2: v = (double)expo<real>(st); break;
-    case 3: v = (double)pg1<real>(st, (real)par0[k], pgtab); break;
-    case 4: v = (double)invgauss(st, (real)par0[k], (real)par1[k]); break;
-    case 5: v = truncnorm0(st, par0[k], par1[k]); break;
-    case 6: v = gamma_mt(st, par0[k]); break;
-    case 7: v = pg_tail_weight(par0[k], pgtab); break;
-    case 8: v = (double)qr_weight<real>(st, (real)par0[k], (real)par1[k]); break;
-    case 9: v = (double)ndtri((real)par0[k]); break;
-    case 17: v = qr_weight_q(st, par0[k], par1[k], par1[k] * par1[k], sh_logtab); break;      // the fp64 cell path's form of the quantile weight (parA = par0, parB = par1 at unit scale)
-    case 11: v = fm::log(par0[k]); break;           // the cell path's fp64 elementary functions (erm_rng.hpp, namespace fm)
-    case 12: v = fm::exp_neg(par0[k]); break;
-    case 13: v = fm::sqrt(par0[k]); break;
-    case 14: v = fm::div(par0[k], par1[k]); break;
-    case 10: {     // PG(1, par0) through the reference form of the attempt (every statement in fp64)
-        const double z = 0.5 * fabs(par0[k]);
-        double o = 0.0;
-        for (int tries = 0; tries < MAX_TRIES; ++tries) {
-            const uint32_t w0 = st.next(), w1 = st.next(), w2 = st.next(), w3 = st.next();
-            if (pg1_attempt_ref(z, w0, w1, w2, w3, pgtab, o)) break;
-        }
-        v = o;
-    } break;
-    }
-    out[k] = v;
-}
-
-__global__ void gig_batch_kernel(uint64_t seed, uint32_t site, uint32_t sweep, long long n, double p, double a, double b, double* out)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    Stream st(seed, 0u, site, (uint32_t)k, 0u, sweep);
-    out[k] = gig(st, p, a, b);
-}
-
 }  // namespace erm
 
+#include "erm_service_kernels.hpp"  // diagnostics, data preparation, generator, run begin / end, DIC, counters, debug samplers
 #include "erm_waic_kernels.hpp"     // WAIC: the pointwise log-likelihood pass behind every sweep and its finish

@@ -1,6 +1,6 @@
 // erm_waic_kernels.hpp -- WAIC on the device: the pointwise log-likelihood of every unit, accumulated once per post-burn-in sweep.
-// Included by erm_kernels.hpp (uses its Ctl, ll_log1pexp and the model families of erm_layout.hpp).  CellArgs, the head of this pass's kernel arguments, is shared
-// with the replicate pass (erm_predictive_kernels.hpp); the cell arithmetic of the two is not (ll_log1pexp here, exp(-|eta|) / log1p there, each pinned to its twin).
+// Included by erm_kernels.hpp (uses its Ctl, log1pexp_r and the model families of erm_layout.hpp).  CellArgs, the head of this pass's kernel arguments, is shared
+// with the replicate pass (erm_predictive_kernels.hpp); the cell arithmetic of the two is not (log1pexp_r here, exp(-|eta|) / log1p there, each pinned to its twin).
 //
 // pointwise_kernel<MODEL, real, UNIT> is ONE streaming pass over the resident data set, launched behind every sweep's own kernels (on the stream and inside
 // every captured graph): at that point theta_t, zeta_t, the item parameters of sweep t and the counters of trace row t are all resident.  It reads the
@@ -37,7 +37,7 @@ template <int MODEL>
 __device__ __forceinline__ double pw_cell(bool y, double th, double ze, double c, double nu, int j, const double* sa, int J, double k1, double k2)
 {
     const double eta = sa[j] * (th - sa[J + j]);
-    double l = (y ? eta : 0.0) - ll_log1pexp(eta);
+    double l = (y ? eta : 0.0) - log1pexp_r(eta);
     if constexpr (MODEL != MLIRT) {
         const double lt = c + sa[5 * J + j];
         double mu = sa[2 * J + j] - ze, var = sa[3 * J + j];

@@ -612,10 +612,7 @@ template <typename real> struct Engine : EngineBase {
     // One sweep = tiny step + row pass (CrossQr: two of each).  Kernel arguments never change between sweeps -- the sweep / trace-row counters and the
     // "first sweep of this call" flag live in device memory (Ctl) -- so EVERY sweep of a run is the same launch sequence and can be captured once into a
     // hipGraph and replayed.  Which graphs, single sweeps and event brackets a call consists of is decided by plan_run (erm_schedule.hpp) and nowhere else.
-#ifndef ERM_GRAPH_SWEEPS
-#define ERM_GRAPH_SWEEPS 32
-#endif
-    static constexpr int GRAPH_SWEEPS = ERM_GRAPH_SWEEPS;
+    static constexpr int GRAPH_SWEEPS = 32;
     // block[gi]: block_sweeps(gi) sweeps; full[k], tail[r]: see StepKind.  Each is built by the first call whose plan replays it.
     hipGraphExec_t graphs[NBLOCK] = {}, graphs_full[GRAPH_SWEEPS + 1] = {}, graphs_tail[GRAPH_SWEEPS + 1] = {};
     hipGraphExec_t* graph_of(const Step& s) { return s.kind == STEP_BLOCK ? &graphs[s.gi] : s.kind == STEP_FULL ? &graphs_full[s.n] : &graphs_tail[s.n]; }

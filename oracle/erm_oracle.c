@@ -904,7 +904,7 @@ void orc_step(const orc_config* c, const orc_data* d, orc_state* s, int step, ui
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Synthetic data: the five generators of /root/reference/src/SimTools.jl restated with the DEVICE's stream addressing
- * (csrc/erm_kernels.hpp gen_kernel), so that erm_simulate_data can be compared value by value.
+ * (csrc/erm_service_kernels.hpp gen_kernel), so that erm_simulate_data can be compared value by value.
  *   subject stream (DATA_SUBJ = 12, i, 0, sweep 0), consumed in this order: the nFeat covariates X[i, f] ~ N(0,1)
  *   (setDataMlIrt: X[i, 1] ~ Bernoulli(1/2) instead -- its uniform is drawn AFTER that column's unused normal), then z0, z1 ~ N(0,1),
  *   then (Latent only) the zeta noise;  cell stream (DATA_CELL = 13, i, j, sweep 0): the uniform of Y[i, j], then the logT variate(s).
