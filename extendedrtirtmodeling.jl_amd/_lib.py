@@ -64,6 +64,7 @@ EXPORTS = [
     "erm_get_dic", "erm_set_seed", "erm_farm_get_dic", "erm_farm_set_seed", "erm_abi_version", "erm_debug_invwishart", "erm_get_convergence", "erm_debug_convergence",
     "erm_set_pointwise", "erm_get_waic", "erm_pointwise_units", "erm_get_pointwise",
     "erm_set_predictive", "erm_predictive_reps", "erm_get_predictive",
+    "erm_get_rank_diagnostics", "erm_get_rank_convergence", "erm_debug_rank_diagnostics",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -192,6 +193,9 @@ def load():
     lib.erm_farm_get_dic.argtypes = [H, C.c_void_p]
     lib.erm_farm_set_seed.argtypes = [H, C.c_uint64]
     lib.erm_debug_invwishart.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]
+    lib.erm_get_rank_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_get_rank_convergence.argtypes = [H, C.c_int, C.c_void_p]
+    lib.erm_debug_rank_diagnostics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -421,6 +425,20 @@ class Engine:
         check(self._lib.erm_get_convergence(self._h, which, c.ctypes.data))
         return tuple(int(v) for v in c)
 
+    def rank_diagnostics(self, which: int):
+        """(ess_bulk, ess_tail, rhat_rank) of every column of Post.ra / rt / qr: the rank-normalised diagnostics (erm_get_rank_diagnostics), computed on the
+        device from the resident traces."""
+        w = int(self._lib.erm_trace_width(self._h, which))
+        bulk, tail, rhat = np.empty(w), np.empty(w), np.empty(w)
+        check(self._lib.erm_get_rank_diagnostics(self._h, which, bulk.ctypes.data, tail.ctypes.data, rhat.ctypes.data))
+        return bulk, tail, rhat
+
+    def rank_convergence(self, which: int):
+        """erm_get_rank_convergence: (bulk-ESS defined, bulk-ESS > 400, tail-ESS defined, tail-ESS > 400, rank R-hat defined, rank R-hat < 1.1), counted on the device."""
+        c = np.zeros(6, dtype=np.int64)
+        check(self._lib.erm_get_rank_convergence(self._h, which, c.ctypes.data))
+        return tuple(int(v) for v in c)
+
     def item_trace(self):
         w = int(self._lib.erm_item_trace_width(self._h))
         out = np.empty((self.rows_done, w), dtype=np.float64)
@@ -592,6 +610,21 @@ def debug_convergence(ess, rhat, *, device=0):
     c = np.zeros(4, dtype=np.int64)
     check(load().erm_debug_convergence(device, e.size, e.ctypes.data, r.ctypes.data, c.ctypes.data))
     return tuple(int(v) for v in c)
+
+
+def rank_diagnostics_device(x, *, precision=PREC_F64, device=0):
+    """erm_debug_rank_diagnostics: (ess_bulk, ess_tail, rhat_rank) of the columns of x[draw, column, chain] (post-burn-in draws) through the kernels
+    erm_get_rank_diagnostics runs on an engine's traces.  precision=PREC_F32 rounds x to float first, as an fp32 engine's trace does."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if x.ndim != 3:
+        raise ValueError("x must be [draw, column, chain]")
+    xf = np.asfortranarray(x)
+    n_draw, n_col, n_chain = xf.shape
+    bulk, tail, rhat = np.empty(n_col), np.empty(n_col), np.empty(n_col)
+    check(load().erm_debug_rank_diagnostics(device, precision, xf.ctypes.data, n_draw, n_col, n_chain, bulk.ctypes.data, tail.ctypes.data, rhat.ctypes.data))
+    return bulk, tail, rhat
 
 
 def debug_invwishart(nu, psi, n, *, seed=1234, sweep=1, device=0):

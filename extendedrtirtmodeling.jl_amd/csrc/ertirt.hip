@@ -19,6 +19,7 @@
 #include "ertirt.h"
 #include "erm_kernels.hpp"
 #include "erm_predictive_kernels.hpp"      // posterior predictive checks: the replicate pass behind every sweep
+#include "erm_rank_diag_kernels.hpp"       // rank-normalised convergence diagnostics: bulk / tail ESS, rank R-hat
 #include "erm_geometry.hpp"
 #include "erm_model.hpp"
 #include "erm_schedule.hpp"
@@ -129,6 +130,41 @@ static int count_converged(const DevBuf& dE, const DevBuf& dR, int64_t n, hipStr
     return 0;
 }
 
+// Rank-normalised diagnostics (erm_rank_diag_kernels.hpp): the limits every entry checks, and the one place that launches the kernels -- for the engine's traces and
+// for erm_debug_rank_diagnostics alike.
+static int rank_diag_limits(int Tn, int n_chain)
+{
+    if (Tn / 2 < 4) return fail(ERM_ERR_ARG, "too few post-burn-in iterations for split-chain diagnostics (need >= 8)");
+    if (n_chain < 1 || 2 * n_chain > DIAG_MAXSEQ) return fail(ERM_ERR_ARG, "too many chains for the diagnostics kernel");
+    const int64_t S = 2 * (int64_t)n_chain * (Tn / 2);
+    if (S > RK_MAX_DRAWS) return fail(ERM_ERR_ARG, "rank diagnostics take at most " + std::to_string(RK_MAX_DRAWS) + " used draws per column (2 * n_chain * floor((n_iter - n_burnin) / 2) = " +
+                                                   std::to_string(S) + ")");
+    return 0;
+}
+// columns [0, ncol) of the trace tr ([row = m nChain + l][ld]) -> bulk / tail / rhat[0 .. ncol), in chunks of columns whose staged draws fit the scratch budget
+// (256 MB whatever the trace width; ERM_RANK_DIAG_CHUNK: a chunk length in columns, for the tests of the chunk tails)
+template <typename T>
+static int rank_diag_run(const T* tr, int64_t ld, int64_t ncol, int nChain, int nBurnin, int Tn, hipStream_t stream, double* bulk, double* tail, double* rhat)
+{
+    const int n = Tn / 2, M = 2 * nChain, S = M * n, P = rk_pad(S);
+    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)S * (int64_t)sizeof(double)));
+    if (const char* e = getenv("ERM_RANK_DIAG_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk = std::min<int64_t>(chunk, v); }
+    chunk = std::min(chunk, ncol);
+    DevBuf scratch;
+    if (int rc = scratch.try_alloc((size_t)chunk * S * sizeof(double), "the rank diagnostics' staged draws")) return rc;
+    const size_t lds = (size_t)P * 10 + (size_t)S * 8;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (int64_t c0 = 0; c0 < ncol; c0 += chunk) {
+        const int64_t nc = std::min(chunk, ncol - c0);
+        hipLaunchKernelGGL((rank_stage_kernel<T>), dim3((unsigned)((nc + 31) / 32), (unsigned)((S + 31) / 32)), dim3(256), 0, stream, tr + c0, (long long)ld, (long long)nc, nChain, nBurnin,
+                           Tn, n, S, scratch.as<double>());
+        hipLaunchKernelGGL(rank_diag_kernel, dim3((unsigned)nc), dim3(RK_THREADS), lds, stream, scratch.as<double>(), M, n, P, bulk + c0, tail + c0, rhat + c0);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
 // A persistent launch needs all its workgroups resident at once.  Two persistent launches of ONE process on one device (a farm's chains sharing a
 // device, several engines) could each hold some compute units and wait for the other's for ever: they take turns.
 std::mutex g_persist_mu[64];
@@ -146,6 +182,8 @@ struct EngineBase {
     virtual int get_mean(erm_state*) = 0;
     virtual int get_diagnostics(int, double*, double*) = 0;
     virtual int get_convergence(int, int64_t*) = 0;
+    virtual int get_rank_diagnostics(int, double*, double*, double*) = 0;
+    virtual int get_rank_convergence(int, int64_t*) = 0;
     virtual int get_dic(double*) = 0;
     // WAIC (erm_set_pointwise / erm_get_waic / erm_pointwise_units / erm_get_pointwise)
     virtual int set_pointwise(int unit) = 0;
@@ -1495,6 +1533,66 @@ template <typename real> struct Engine : EngineBase {
         return count_converged(dE, dR, trace_width(which), stream, c4);
     }
 
+    // bulk-ESS / tail-ESS / rank-normalised R-hat of every column of trace `which` into device arrays, block by block as diag_device does (rank_diag_run); the call
+    // reads the engine only
+    int rank_diag_device(int which, DevBuf& dB, DevBuf& dT, DevBuf& dR) {
+        HIPCHK(hipSetDevice(cfg.device));
+        const int64_t wd = trace_width(which);
+        if (which == ERM_TRACE_LOGLIKE || wd <= 0) return fail(ERM_ERR_ARG, "diagnostics exist for the ra / rt / qr traces");
+        if (rows_done != rows_cap) return fail(ERM_ERR_STATE, "trace incomplete: run n_iter*n_chain sweeps first");
+        if (cfg.trace_mode != ERM_TRACE_FULL) return fail(ERM_ERR_NOTRACE, "subject-level traces need trace_mode = ERM_TRACE_FULL");
+        const int Tn = cfg.n_iter - cfg.n_burnin;
+        if (int rc = rank_diag_limits(Tn, cfg.n_chain)) return rc;
+        for (const TraceBlock& b : trace_blocks(which)) if ((b.kind == BLK_SUBJECT || b.kind == BLK_CELL) && !subj_trace(b.src).p)
+            return fail(ERM_ERR_NOTRACE, b.kind == BLK_CELL ? "the per-sweep nu trace was not recorded (erm_config.nu_trace_max_gb)" : "this trace was not recorded");
+        HIPCHK(hipStreamSynchronize(stream));
+        for (DevBuf* d : {&dB, &dT, &dR}) if (int rc = d->try_alloc((size_t)wd * sizeof(double), "the rank diagnostics")) return rc;
+        for (const TraceBlock& b : trace_blocks(which)) {
+            double* o[3] = { dB.as<double>() + b.col0, dT.as<double>() + b.col0, dR.as<double>() + b.col0 };
+            switch (b.kind) {
+            case BLK_SUBJECT: case BLK_CELL:
+                if (int rc = rank_diag_run(static_cast<const real*>(subj_trace(b.src).p), b.ncol, b.ncol, cfg.n_chain, cfg.n_burnin, Tn, stream, o[0], o[1], o[2])) return rc;
+                break;
+            case BLK_ITEM:
+                if (int rc = rank_diag_run(dTrItem.as<double>() + b.src, item_trace_width(), b.ncol, cfg.n_chain, cfg.n_burnin, Tn, stream, o[0], o[1], o[2])) return rc;
+                break;
+            case BLK_ZERO: {                    // constant columns: NaN
+                const std::vector<double> nanv((size_t)b.ncol, std::nan(""));
+                for (double* d : o) HIPCHK(hipMemcpyAsync(d, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                break;
+            }
+            }
+        }
+        return 0;
+    }
+    int get_rank_diagnostics(int which, double* bulk, double* tail, double* rhat) override {
+        DevBuf dB, dT, dR;
+        if (int rc = rank_diag_device(which, dB, dT, dR)) return rc;
+        const int64_t wd = trace_width(which);
+        const DevBuf* src[3] = { &dB, &dT, &dR };
+        double* dst[3] = { bulk, tail, rhat };
+        for (int q = 0; q < 3; ++q) {
+            if (!dst[q]) continue;
+            HIPCHK(hipMemcpy(dst[q], src[q]->p, (size_t)wd * sizeof(double), hipMemcpyDeviceToHost));
+            for (const TraceBlock& b : trace_blocks(which)) if (b.device_order()) {      // row-major N x J -> Julia's vec (column-major)
+                const std::vector<double> h(dst[q] + b.col0, dst[q] + b.col0 + b.ncol);
+                rows_to_cols(h.data(), dst[q] + b.col0, N, J);
+            }
+        }
+        return 0;
+    }
+    // { bulk defined, bulk > 400, tail defined, tail > 400, rhat defined, rhat < 1.1 }: diag_count_kernel on (bulk, rhat) and on (tail, rhat)
+    int get_rank_convergence(int which, int64_t* c6) override {
+        DevBuf dB, dT, dR;
+        if (int rc = rank_diag_device(which, dB, dT, dR)) return rc;
+        int64_t a[4], b[4];
+        if (int rc = count_converged(dB, dR, trace_width(which), stream, a)) return rc;
+        if (int rc = count_converged(dT, dR, trace_width(which), stream, b)) return rc;
+        c6[0] = a[0]; c6[1] = a[1]; c6[2] = b[0]; c6[3] = b[1]; c6[4] = a[2]; c6[5] = a[3];
+        return 0;
+    }
+
     // item-level means (an item-trace row's layout) -> the fields of Post.mean (src/GibbsRtIrt.pl.jl:249-254, 327-343; Cross :304-318; Latent :316-330)
     void unpack_items(const double* m, erm_state* out) const {
         for (int k = 0; k < item_trace_fields(cfg.model); ++k) if (double* dst = out->*FIELDS[k].member) memcpy(dst, &m[FIELDS[k].off(J)], J * sizeof(double));
@@ -1702,6 +1800,25 @@ struct erm_farm {
     }
 };
 
+// erm_debug_rank_diagnostics: caller-supplied draws through the kernels the engine runs on its traces
+template <typename T>
+static int debug_rank_diag(const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain, double* bulk, double* tail, double* rhat)
+{
+    // Julia layout x[m + n_draw (k + n_col l)] -> the engine's trace layout [row = m n_chain + l][column k] in the engine's trace type
+    std::vector<T> tr((size_t)n_draw * n_col * n_chain);
+    for (int64_t l = 0; l < n_chain; ++l) for (int64_t k = 0; k < n_col; ++k) for (int64_t m = 0; m < n_draw; ++m)
+        tr[(size_t)((m * n_chain + l) * n_col + k)] = (T)x[m + n_draw * (k + n_col * l)];
+    DevBuf dTr, dO;
+    if (int rc = dTr.try_alloc(tr.size() * sizeof(T), "the draws")) return rc;
+    if (int rc = dO.try_alloc((size_t)3 * n_col * sizeof(double), "the rank diagnostics")) return rc;
+    H2D(dTr.p, tr.data(), tr.size() * sizeof(T));
+    double* o = dO.as<double>();
+    if (int rc = rank_diag_run(dTr.as<T>(), n_col, n_col, (int)n_chain, 0, (int)n_draw, nullptr, o, o + n_col, o + 2 * n_col)) return rc;
+    double* dst[3] = { bulk, tail, rhat };
+    for (int q = 0; q < 3; ++q) if (dst[q]) HIPCHK(hipMemcpy(dst[q], o + q * n_col, (size_t)n_col * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" {
 
 int erm_create(const erm_config* cfg, erm_handle* out)
@@ -1736,6 +1853,8 @@ int erm_get_data(erm_handle h, uint8_t* Y, double* logT, double* X) { CHK_H; ret
 int erm_get_truth(erm_handle h, double* theta, double* zeta) { CHK_H; return h->e->get_truth(theta, zeta); }
 int erm_get_diagnostics(erm_handle h, int which, double* ess, double* rhat) { CHK_H; if (!ess || !rhat) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_diagnostics(which, ess, rhat); }
 int erm_get_convergence(erm_handle h, int which, int64_t* counts4) { CHK_H; if (!counts4) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_convergence(which, counts4); }
+int erm_get_rank_diagnostics(erm_handle h, int which, double* ess_bulk, double* ess_tail, double* rhat_rank) { CHK_H; return h->e->get_rank_diagnostics(which, ess_bulk, ess_tail, rhat_rank); }
+int erm_get_rank_convergence(erm_handle h, int which, int64_t* counts6) { CHK_H; if (!counts6) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_rank_convergence(which, counts6); }
 int erm_get_dic(erm_handle h, double* out4) { CHK_H; if (!out4) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_dic(out4); }
 int erm_set_pointwise(erm_handle h, int unit) { CHK_H; return h->e->set_pointwise(unit); }
 int erm_get_waic(erm_handle h, double* out_eight) { CHK_H; if (!out_eight) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_waic(out_eight); }
@@ -1985,6 +2104,18 @@ int erm_debug_convergence(int device, int64_t n, const double* ess, const double
     H2D(dE.p, ess, (size_t)n * sizeof(double));
     H2D(dR.p, rhat, (size_t)n * sizeof(double));
     return count_converged(dE, dR, n, nullptr, counts4);
+}
+
+int erm_debug_rank_diagnostics(int device, int precision, const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain, double* ess_bulk, double* ess_tail, double* rhat_rank)
+{
+    if (!x || n_draw <= 0 || n_col <= 0 || n_draw > 0x7fffffff) return fail(ERM_ERR_ARG, "bad x / n_draw / n_col");
+    if (precision != ERM_PREC_F32 && precision != ERM_PREC_F64) return fail(ERM_ERR_ARG, "unknown precision");
+    if (int rc = rank_diag_limits((int)n_draw, n_chain)) return rc;
+    const int64_t len = n_draw * n_col * n_chain;
+    for (int64_t e = 0; e < len; ++e) if (x[e] != x[e]) return fail(ERM_ERR_NONFINITE, "x holds a NaN at entry " + std::to_string(e));
+    HIPCHK(hipSetDevice(device));
+    return precision == ERM_PREC_F32 ? debug_rank_diag<float>(x, n_draw, n_col, n_chain, ess_bulk, ess_tail, rhat_rank)
+                                     : debug_rank_diag<double>(x, n_draw, n_col, n_chain, ess_bulk, ess_tail, rhat_rank);
 }
 
 int erm_debug_sample(int device, int precision, int which, uint64_t seed, uint32_t site, uint32_t sweep, int64_t n,

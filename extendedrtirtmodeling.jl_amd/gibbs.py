@@ -709,15 +709,82 @@ def ess_rhat(x: np.ndarray):
     return M * n / (-1.0 + 2.0 * total), float(np.sqrt(varp / W))
 
 
-def checkConvergence(MCMC: _GibbsBase, *, detail=True) -> dict:
+def rank_ess_rhat(x: np.ndarray):
+    """(ess_bulk, ess_tail, rhat_rank) of draws x[(iteration, chain)]: the rank-normalised diagnostics of Vehtari et al. (2021) as include/ertirt.h defines them
+    for erm_get_rank_diagnostics -- the host twin of the device kernel `rank_diag_kernel`, on numpy / scipy.  The used draws are ess_rhat's (the first and last
+    floor(T / 2) of every chain), pooled: z = ndtri((average rank - 3/8) / (S + 1/4)), ess_bulk = E(z); f = |x - med| with med the mean of the two middle order
+    statistics, rhat_rank = the larger of R(z) and R(z(f)) (R(z) alone when f is constant); with k = ceil(S / 20), ess_tail = the smaller of E([x <= x_(k)]) and
+    E([x >= x_(S+1-k)]), NaN if either indicator is constant.  E and R are ess_rhat's.  A column that never moves gets three NaN."""
+    from scipy.special import ndtri
+    from scipy.stats import rankdata
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    T, C = x.shape
+    n = T // 2
+    u = np.concatenate([x[:n], x[T - n:]], axis=0)                # the used draws [2 n, chain]: ess_rhat splits them exactly as it splits x
+    S = u.size
+    nan = float("nan")
+    if not np.any(u != u[0, 0]):
+        return nan, nan, nan
+
+    def scores(v):
+        return ndtri((rankdata(v.ravel(), method="average").reshape(v.shape) - 0.375) / (S + 0.25))
+
+    srt = np.sort(u.ravel())
+    k = (S + 19) // 20
+    ess_bulk, rz = ess_rhat(scores(u))
+    med = 0.5 * (srt[S // 2 - 1] + srt[S // 2])
+    _, rf = ess_rhat(scores(np.abs(u - med)))
+    el, _ = ess_rhat((u <= srt[k - 1]).astype(np.float64))
+    eu, _ = ess_rhat((u >= srt[S - k]).astype(np.float64))
+    ess_tail = nan if (np.isnan(el) or np.isnan(eu)) else min(el, eu)
+    return ess_bulk, ess_tail, (rf if (not np.isnan(rf) and rf > rz) else rz)
+
+
+def _check_convergence_rank(MCMC, detail):
+    eng = MCMC._engine
+    tot = np.zeros(6, dtype=np.int64)
+    out = {}
+    for name, which in (("ra", _lib.TRACE_RA), ("rt", _lib.TRACE_RT), ("qr", _lib.TRACE_QR)):
+        if which == _lib.TRACE_RT and not MCMC._traits.rt:
+            continue
+        try:
+            if detail:
+                bulk, tail, rhat = eng.rank_diagnostics(which)
+                with np.errstate(invalid="ignore"):
+                    c = (np.sum(~np.isnan(bulk)), np.sum(bulk > 400), np.sum(~np.isnan(tail)), np.sum(tail > 400), np.sum(~np.isnan(rhat)), np.sum(rhat < 1.1))
+                out[name] = (bulk, tail, rhat)
+            else:
+                c = eng.rank_convergence(which)
+        except _lib.ErmError:
+            if which != _lib.TRACE_QR:
+                raise
+            continue                                    # CrossQr without a resident nu trace
+        tot += np.asarray(c, dtype=np.int64)
+    bn, bok, tn, tok, rn, rok = (int(v) for v in tot)
+    res = dict(ess=100.0 * bok / max(bn, 1), essTail=100.0 * tok / max(tn, 1), rhat=100.0 * rok / max(rn, 1),
+               essN=f"{bok} / {bn}", essTailN=f"{tok} / {tn}", rhatN=f"{rok} / {rn}")
+    if detail:
+        res["detail"] = out
+    return res
+
+
+def checkConvergence(MCMC: _GibbsBase, *, detail=True, kind="basic") -> dict:
     """src/SimTools.jl:419-443: share of the ra / rt / qr columns with ESS > 400 and R-hat < 1.1 after burn-in.  The reference runs
-    MCMCChains' `ess_rhat` on the host; here both statistics come from the device-resident traces (erm_get_diagnostics; split-R-hat and
-    Geyer's initial-monotone-sequence ESS, not rank-normalised -- MCMCChains' version is not pinned by the reference).  Columns that
+    MCMCChains' `ess_rhat` on the host; here both statistics come from the device-resident traces.  kind="basic" (the default): erm_get_diagnostics, split-R-hat and
+    Geyer's initial-monotone-sequence ESS, not rank-normalised.  kind="rank": erm_get_rank_diagnostics, the rank-normalised estimator of Vehtari et al. (2021)
+    that MCMCChains 6 reports -- `ess` is then the share by bulk-ESS, `essTail` the share by tail-ESS, `rhat` the share by rank-normalised R-hat (with `essN`,
+    `essTailN`, `rhatN`), and with detail=True every trace carries (ess_bulk, ess_tail, rhat_rank).  Columns that
     never move (NaN) are left out of the denominators, as the reference does for qr.  detail=False also COUNTS on the device
-    (erm_get_convergence): eight integers cross the boundary instead of the N-wide ess / rhat vectors."""
+    (erm_get_convergence / erm_get_rank_convergence): eight (eighteen) integers cross the boundary instead of the N-wide vectors."""
     eng = MCMC._engine
     if eng is None:
         raise ValueError("run sample! first")
+    if kind == "rank":
+        return _check_convergence_rank(MCMC, detail)
+    if kind != "basic":
+        raise ValueError('kind must be "basic" or "rank"')
     ess_n = rhat_n = ess_ok = rhat_ok = 0
     out = {}
     for name, which in (("ra", _lib.TRACE_RA), ("rt", _lib.TRACE_RT), ("qr", _lib.TRACE_QR)):

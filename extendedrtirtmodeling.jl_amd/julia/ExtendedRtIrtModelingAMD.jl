@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -285,6 +285,33 @@ function essRhat(M::GibbsAMD, which::Integer)
 end
 
 """
+    rankEssRhat(MCMC, which) -> (essBulk, essTail, rhatRank)
+
+Bulk-ESS, tail-ESS and rank-normalised split R-hat (Vehtari et al. 2021; what MCMCChains 6 reports from `ess_rhat`) of every column of `Post.ra`,
+`Post.rt` or `Post.qr`, ranked and estimated on the device from the resident traces (`erm_get_rank_diagnostics`).  Call after `sample!`.
+"""
+function rankEssRhat(M::GibbsAMD, which::Integer)
+    M.handle == C_NULL && error("run sample! first")
+    w = ccall((:erm_trace_width, LIB[]), Int64, (Ptr{Cvoid}, Cint), M.handle, which)
+    bulk, tail, rhat = zeros(w), zeros(w), zeros(w)
+    check(ccall((:erm_get_rank_diagnostics, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), M.handle, which, bulk, tail, rhat))
+    return bulk, tail, rhat
+end
+
+"""
+    rankEssRhatDraws(x; precision=PREC_F64, device=0) -> (essBulk, essTail, rhatRank)
+
+The same kernels on a host array `x[draw, column, chain]` of post-burn-in draws (`erm_debug_rank_diagnostics`): for traces that are not resident on one device.
+"""
+function rankEssRhatDraws(x::Array{Float64,3}; precision::Integer=1, device::Integer=0)
+    nd, nc, nch = size(x)
+    bulk, tail, rhat = zeros(nc), zeros(nc), zeros(nc)
+    check(ccall((:erm_debug_rank_diagnostics, LIB[]), Cint, (Cint, Cint, Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                device, precision, x, nd, nc, nch, bulk, tail, rhat))
+    return bulk, tail, rhat
+end
+
+"""
     getDicDevice(MCMC) -> (Dbar, Dhat, pD, DIC)
 
 `getDic` (src/GibbsRtIrt.pl.jl:432-472, src/GibbsRtIrtCross.pl.jl:330-353, src/GibbsRtIrtLatent.pl.jl:342-365) from device-resident state
@@ -360,12 +387,26 @@ function getPpcDevice(M::GibbsAMD)
 end
 
 """
-    checkConvergenceDevice(MCMC) -> (ess, rhat, essN, rhatN)
+    checkConvergenceDevice(MCMC; kind=:basic) -> (ess, rhat, essN, rhatN)
+    checkConvergenceDevice(MCMC; kind=:rank)  -> (ess, essTail, rhat, essN, essTailN, rhatN)
 
 `checkConvergence` (src/SimTools.jl:419-443) with the ESS / R-hat of every column computed AND counted on the device (`erm_get_convergence`).
+`kind=:rank` counts the rank-normalised diagnostics instead (`erm_get_rank_convergence`): `ess` by bulk-ESS, `essTail` by tail-ESS, `rhat` by rank R-hat.
 """
-function checkConvergenceDevice(M::GibbsAMD)
+function checkConvergenceDevice(M::GibbsAMD; kind::Symbol=:basic)
     M.handle == C_NULL && error("run sample! first")
+    kind in (:basic, :rank) || error("kind must be :basic or :rank")
+    if kind == :rank
+        t6 = zeros(Int64, 6)
+        for which in (TRACE_RA, TRACE_RT, TRACE_QR)
+            which == TRACE_RT && M isa GibbsMlIrt && continue
+            c = zeros(Int64, 6)
+            check(ccall((:erm_get_rank_convergence, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}), M.handle, which, c))
+            t6 .+= c
+        end
+        return (ess = 100 * t6[2] / max(t6[1], 1), essTail = 100 * t6[4] / max(t6[3], 1), rhat = 100 * t6[6] / max(t6[5], 1),
+                essN = "$(t6[2]) / $(t6[1])", essTailN = "$(t6[4]) / $(t6[3])", rhatN = "$(t6[6]) / $(t6[5])")
+    end
     tot = zeros(Int64, 4)
     for which in (TRACE_RA, TRACE_RT, TRACE_QR)
         which == TRACE_RT && M isa GibbsMlIrt && continue

@@ -158,6 +158,34 @@ int erm_get_diagnostics(erm_handle h, int which, double* ess, double* rhat);
 /* checkConvergence's summary itself (src/SimTools.jl:427-437) without the N-wide vectors: counts4 = { columns with a defined ESS, of those ESS > 400, columns with a
  * defined R-hat, of those R-hat < 1.1 } for trace `which`, counted on the device. */
 int erm_get_convergence(erm_handle h, int which, int64_t* counts4);
+/* The rank-normalised diagnostics of Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021) -- what `ess_rhat` of MCMCChains 6 / MCMCDiagnosticTools 0.3 (the
+ * versions the reference's Project.toml names) reports: bulk-ESS, tail-ESS and rank-normalised split-R-hat of every column of trace `which`, computed on the
+ * device from the resident traces (the N-wide traces never cross to the host).  On the heavy-tailed columns of this model family (sig2t, Sigma_p, the quantile
+ * models' nu) the moment-based estimator above is blind to chains that differ in scale and its ESS is dominated by a few extreme draws; this one is not.
+ * Definition.  The used draws of a column are those of erm_get_diagnostics: with Tn = n_iter - n_burnin and n = floor(Tn / 2) the first n and the last n
+ * post-burn-in draws of every chain (an odd Tn drops the middle draw): M = 2 n_chain sequences, S = M n pooled draws, S even.  E(.) and R(.) are the ESS and the
+ * split-R-hat defined above, applied to a transformed column (same stop rule, same -M n case, same "never moves -> NaN" rule decided on the series).
+ *   1. ranks          r_i = the average rank of x_i among the S pooled draws; ties share the mean of their positions (-0.0 and +0.0 tie)
+ *   2. normal scores  z_i = Phi^-1((r_i - 3/8) / (S + 1/4)): one fp64 subtraction, one addition, one division, then the device's fp64 normal quantile
+ *                     (Wichura's AS 241), whatever the engine's precision
+ *   3. bulk ESS       ess_bulk = E(z)
+ *   4. folding        med = (x_(S/2) + x_(S/2+1)) / 2 with order statistics of the pooled draws, f_i = |x_i - med|, z' = the normal scores of f
+ *   5. rank R-hat     rhat_rank = max(R(z), R(z')) over those of the two that are defined (a two-valued column split evenly makes f constant: R(z') is
+ *                     undefined and rhat_rank = R(z))
+ *   6. tail ESS       k = ceil(S / 20) = (S + 19) / 20 in integers, L_i = [x_i <= x_(k)], U_i = [x_i >= x_(S+1-k)], ess_tail = min(E(L), E(U)); NaN if either
+ *                     indicator column is constant.  Order statistics, not interpolated quantiles: every decision up to the normal quantile is an ordering
+ *                     or an integer.  (Stan and ArviZ interpolate the 5 % and 95 % quantiles; the difference is below the estimator's own noise.)
+ *   7. a column that never moves: all three NaN.
+ * An fp32 engine's traces are float: the stored values are ranked, widened to double.  Any of the three output pointers may be NULL; width erm_trace_width.
+ * One workgroup sorts and ranks a column in LDS, so S is capped at 8192 used draws per column (ERM_ERR_ARG above it, the message names the cap); otherwise the
+ * limits of erm_get_diagnostics: ERM_TRACE_FULL (ERM_ERR_NOTRACE), a completed run (ERM_ERR_STATE), >= 8 post-burn-in iterations and <= 16 chains
+ * (ERM_ERR_ARG).  Device scratch is bounded (columns go through in chunks, 256 MB of staged draws at most; ERM_ERR_NOMEM if it cannot be had).  The call only
+ * reads the engine: the chain and every other read-out are unchanged by it.  All sums have a fixed order: the results are bit-reproducible from call to call
+ * and a column's result does not depend on the other columns. */
+int erm_get_rank_diagnostics(erm_handle h, int which, double* ess_bulk, double* ess_tail, double* rhat_rank);
+/* counts6 = { bulk-ESS defined, bulk-ESS > 400, tail-ESS defined, tail-ESS > 400, rank R-hat defined, rank R-hat < 1.1 } of trace `which`: the reference's
+ * thresholds, counted on the device as for erm_get_convergence. */
+int erm_get_rank_convergence(erm_handle h, int which, int64_t* counts6);
 
 /* getDic (src/GibbsRtIrt.pl.jl:432-472, src/GibbsRtIrtCross.pl.jl:330-353, src/GibbsRtIrtLatent.pl.jl:342-365) from device-resident state:
  * out = { Dbar, Dhat, pD, DIC } with Dbar = -2 mean(Post.logLike) over ALL recorded rows (burn-in included, as the reference does), Dhat = -2 logLik(Post.mean) from
@@ -303,6 +331,13 @@ int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, d
  * same thresholds ESS > 400 and R-hat < 1.1, both strict; a NaN is "not defined" and enters no count): lets a test put values ON the thresholds, where a sampler's
  * trace never lands.  counts4 as for erm_get_convergence. */
 int erm_debug_convergence(int device, int64_t n, const double* ess, const double* rhat, int64_t* counts4);
+
+/* erm_get_rank_diagnostics' kernels on caller-supplied draws x[n_draw][n_col][n_chain] (Julia layout, the draw fastest, already post-burn-in): the same staging
+ * and rank kernels, at n_iter = n_draw and n_burnin = 0.  precision ERM_PREC_F32 rounds x to float on upload (the fp32 engines' trace type); the diagnostics
+ * themselves are fp64 either way.  Any of the three output pointers (n_col doubles each) may be NULL.  Limits as for erm_get_rank_diagnostics; a NaN in x:
+ * ERM_ERR_NONFINITE.  Serves traces that are not resident on one device (erm_farm_get_trace output) and the tests. */
+int erm_debug_rank_diagnostics(int device, int precision, const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain,
+                               double* ess_bulk, double* ess_tail, double* rhat_rank);
 
 /* n draws of the generalized inverse Gaussian GIG(p, a, b) (density ~ x^(p-1) exp(-(a x + b/x)/2); the distribution type of
  * src/GenInvGaussian.jl:17-30, whose sampler :76-106 is dead code in the reference) by Devroye's (2014) sampler, fp64; element k uses
