@@ -65,6 +65,7 @@ EXPORTS = [
     "erm_set_pointwise", "erm_get_waic", "erm_pointwise_units", "erm_get_pointwise",
     "erm_set_predictive", "erm_predictive_reps", "erm_get_predictive",
     "erm_get_rank_diagnostics", "erm_get_rank_convergence", "erm_debug_rank_diagnostics",
+    "erm_farm_get_diagnostics", "erm_farm_get_convergence", "erm_farm_get_rank_diagnostics", "erm_farm_get_rank_convergence", "erm_debug_diagnostics",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -196,6 +197,11 @@ def load():
     lib.erm_get_rank_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erm_get_rank_convergence.argtypes = [H, C.c_int, C.c_void_p]
     lib.erm_debug_rank_diagnostics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_convergence.argtypes = [H, C.c_int, C.c_void_p]
+    lib.erm_farm_get_rank_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_rank_convergence.argtypes = [H, C.c_int, C.c_void_p]
+    lib.erm_debug_diagnostics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -552,6 +558,36 @@ class Farm:
         check(self._lib.erm_farm_get_dic(self._h, out.ctypes.data))
         return dict(Dbar=float(out[0]), Dhat=float(out[1]), pD=float(out[2]), DIC=float(out[3]))
 
+    # ---- joint convergence diagnostics over all chains (erm_farm_get_diagnostics and its siblings); engine(l).diagnostics(which) stays the diagnostic of chain l alone
+    def _width(self, which: int):
+        return int(self._lib.erm_trace_width(self._lib.erm_farm_engine(self._h, 0), which))
+
+    def diagnostics(self, which: int):
+        """(ess, rhat) of every column of Post.ra / rt / qr over the farm's chains jointly (M = 2 * n_chains split sequences), computed on chain 0's device."""
+        w = max(self._width(which), 0)
+        ess, rhat = np.empty(w), np.empty(w)
+        check(self._lib.erm_farm_get_diagnostics(self._h, which, ess.ctypes.data, rhat.ctypes.data))
+        return ess, rhat
+
+    def convergence(self, which: int):
+        """erm_farm_get_convergence: the four counts of Engine.convergence, of the joint diagnostics."""
+        c = np.zeros(4, dtype=np.int64)
+        check(self._lib.erm_farm_get_convergence(self._h, which, c.ctypes.data))
+        return tuple(int(v) for v in c)
+
+    def rank_diagnostics(self, which: int):
+        """(ess_bulk, ess_tail, rhat_rank) of every column over the farm's chains jointly: the rank-normalised diagnostics (erm_farm_get_rank_diagnostics)."""
+        w = max(self._width(which), 0)
+        bulk, tail, rhat = np.empty(w), np.empty(w), np.empty(w)
+        check(self._lib.erm_farm_get_rank_diagnostics(self._h, which, bulk.ctypes.data, tail.ctypes.data, rhat.ctypes.data))
+        return bulk, tail, rhat
+
+    def rank_convergence(self, which: int):
+        """erm_farm_get_rank_convergence: the six counts of Engine.rank_convergence, of the joint diagnostics."""
+        c = np.zeros(6, dtype=np.int64)
+        check(self._lib.erm_farm_get_rank_convergence(self._h, which, c.ctypes.data))
+        return tuple(int(v) for v in c)
+
     def timing(self):
         """erm_farm_get_timing: wall-clock of the last run / gather, per-chain device time, ranks of the library's RCCL communicator."""
         t = erm_farm_timing()
@@ -625,6 +661,21 @@ def rank_diagnostics_device(x, *, precision=PREC_F64, device=0):
     bulk, tail, rhat = np.empty(n_col), np.empty(n_col), np.empty(n_col)
     check(load().erm_debug_rank_diagnostics(device, precision, xf.ctypes.data, n_draw, n_col, n_chain, bulk.ctypes.data, tail.ctypes.data, rhat.ctypes.data))
     return bulk, tail, rhat
+
+
+def debug_diagnostics(x, *, precision=PREC_F64, device=0):
+    """erm_debug_diagnostics: (ess, rhat) of the columns of x[draw, column, chain] (post-burn-in draws) through the kernel erm_get_diagnostics runs on an engine's
+    traces -- the basic estimator's twin of rank_diagnostics_device.  precision=PREC_F32 rounds x to float first, as an fp32 engine's trace does."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if x.ndim != 3:
+        raise ValueError("x must be [draw, column, chain]")
+    xf = np.asfortranarray(x)
+    n_draw, n_col, n_chain = xf.shape
+    ess, rhat = np.empty(n_col), np.empty(n_col)
+    check(load().erm_debug_diagnostics(device, precision, xf.ctypes.data, n_draw, n_col, n_chain, ess.ctypes.data, rhat.ctypes.data))
+    return ess, rhat
 
 
 def debug_invwishart(nu, psi, n, *, seed=1234, sweep=1, device=0):

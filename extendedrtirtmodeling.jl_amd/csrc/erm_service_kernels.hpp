@@ -157,6 +157,31 @@ __global__ void diag_kernel(const T* tr, long long ncol, long long ld, int nIter
     ess[k] = (double)M * n / (-1.0 + 2.0 * sum);
 }
 
+// Chain farm, joint diagnostics: the post-burn-in rows of nc columns of ONE chain's trace block (src: the chunk's first column in row 0 of the
+// block, rows ld apart) into slot l of the interleaved scratch the estimator kernels read as a trace of L chains without burn-in:
+//   dst[((m - nBurnin) L + l) nc + k] = src[m ld + k],   m = nBurnin .. nBurnin + Tn - 1,  k = 0 .. nc - 1.
+// With L = 1, l = 0 the same kernel compacts the rows into the slab [Tn][nc] that crosses to chain 0's device when the chain lives elsewhere.  Rows go over
+// blockIdx.y, columns over blockIdx.x and the lanes (both grid-stride): reads and writes are coalesced along the columns, 16 bytes a lane where the chunk length,
+// the row stride and both base addresses allow (a wave-uniform choice), one element a lane otherwise.  One writer per element, no atomics.
+template <typename T>
+__global__ void __launch_bounds__(256) farm_gather_kernel(const T* src, long long ld, long long nc, int Tn, int nBurnin, int L, int l, T* dst)
+{
+    constexpr int V = 16 / (int)sizeof(T);
+    const bool wide = nc % V == 0 && ld % V == 0 && ((reinterpret_cast<unsigned long long>(src) | reinterpret_cast<unsigned long long>(dst)) & 15ull) == 0ull;
+    const long long k0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, kstep = (long long)gridDim.x * blockDim.x;
+    for (int r = (int)blockIdx.y; r < Tn; r += (int)gridDim.y) {
+        const T* s = src + (long long)(nBurnin + r) * ld;
+        T* d = dst + ((long long)r * L + l) * nc;
+        if (wide) {
+            const uint4* s4 = reinterpret_cast<const uint4*>(s);
+            uint4* d4 = reinterpret_cast<uint4*>(d);
+            for (long long k = k0; k < nc / V; k += kstep) d4[k] = s4[k];
+        } else {
+            for (long long k = k0; k < nc; k += kstep) d[k] = s[k];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Synthetic data on the device: the generators of src/SimTools.jl -- setDataRtIrt :149-178, setDataRtIrtNull
 // :117-144, setDataMlIrt :349-368, setDataRtIrtCross :220-255, setDataRtIrtLatent :304-343 -- written straight into the engine's

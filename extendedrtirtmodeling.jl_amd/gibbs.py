@@ -742,8 +742,17 @@ def rank_ess_rhat(x: np.ndarray):
     return ess_bulk, ess_tail, (rf if (not np.isnan(rf) and rf > rz) else rz)
 
 
+def _diag_source(MCMC):
+    """What checkConvergence reads: the chain farm of the last sample!(...; devices=) -- its JOINT diagnostics over all chains (erm_farm_get_diagnostics and its
+    siblings) -- else the sampler's engine, as getDic chooses."""
+    src = getattr(MCMC, "farm", None) or MCMC._engine
+    if src is None:
+        raise ValueError("run sample! first")
+    return src
+
+
 def _check_convergence_rank(MCMC, detail):
-    eng = MCMC._engine
+    eng = _diag_source(MCMC)
     tot = np.zeros(6, dtype=np.int64)
     out = {}
     for name, which in (("ra", _lib.TRACE_RA), ("rt", _lib.TRACE_RT), ("qr", _lib.TRACE_QR)):
@@ -777,10 +786,10 @@ def checkConvergence(MCMC: _GibbsBase, *, detail=True, kind="basic") -> dict:
     that MCMCChains 6 reports -- `ess` is then the share by bulk-ESS, `essTail` the share by tail-ESS, `rhat` the share by rank-normalised R-hat (with `essN`,
     `essTailN`, `rhatN`), and with detail=True every trace carries (ess_bulk, ess_tail, rhat_rank).  Columns that
     never move (NaN) are left out of the denominators, as the reference does for qr.  detail=False also COUNTS on the device
-    (erm_get_convergence / erm_get_rank_convergence): eight (eighteen) integers cross the boundary instead of the N-wide vectors."""
-    eng = MCMC._engine
-    if eng is None:
-        raise ValueError("run sample! first")
+    (erm_get_convergence / erm_get_rank_convergence): eight (eighteen) integers cross the boundary instead of the N-wide vectors.
+    After sample!(...; devices=) the statistics are the chain farm's: every estimator over the nChain independent chains jointly (erm_farm_get_diagnostics and its
+    siblings, computed on the first chain's device), which is where R-hat sees the variance between chains."""
+    eng = _diag_source(MCMC)
     if kind == "rank":
         return _check_convergence_rank(MCMC, detail)
     if kind != "basic":

@@ -70,11 +70,12 @@ for (T, model) in ((:GibbsMlIrt, MODEL_MLIRT), (:GibbsRtIrt, MODEL_RTIRT), (:Gib
             shard::Any      # nothing, or (rank, count, nSubjTotal, rowBase, uid): Cond.nSubj / Data then describe this process's subjects only
                             # (give every rank the same β / ρ / Σp start, e.g. Random.seed!(s) before the constructor and cut θ, ζ afterwards:
                             #  setInitialValues draws them from the global RNG as the reference does)
+            farm::Ptr{Cvoid}   # the chain farm of the last sample!(...; devices), kept until the next sample! (or the finalizer) for checkConvergenceDevice; else C_NULL
             function $T(Cond; Data = [], truePara = [], Para = Float64[], Post = Float64[], seed = 1234, device = 0, precision = 1, shard = nothing)
-                obj = new(Cond, Data, truePara, Para, Post, C_NULL, nothing, UInt64(seed), Int32(device), Int32(precision), shard)
+                obj = new(Cond, Data, truePara, Para, Post, C_NULL, nothing, UInt64(seed), Int32(device), Int32(precision), shard, C_NULL)
                 setInitialValues(obj)                      # always overwrites Para, as the reference's constructors do
                 obj.Post = OutputPost([], [], [], [], Float64[])
-                finalizer(o -> (o.handle != C_NULL && ccall((:erm_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), o.handle)), obj)
+                finalizer(o -> (o.handle != C_NULL && ccall((:erm_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), o.handle); releaseFarm!(o)), obj)
                 return obj
             end
         end
@@ -155,12 +156,20 @@ function state_arrays(P::InputPara)
     (dense(P.θ), dense(P.a), dense(P.b), dense(P.ζ), dense(P.λ), dense(P.σ²t), dense(vec(P.β)), dense(vec(P.Σp)), dense(P.ρ), dense(vec(P.ν)))
 end
 
+# the chain farm a sampler keeps from its last sample!(...; devices): released before the next sample! and by the finalizer
+function releaseFarm!(M)
+    M.farm != C_NULL && ccall((:erm_farm_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), M.farm)
+    M.farm = C_NULL
+    return M
+end
+
 # nChain INDEPENDENT chains, chain l on GPU devices[l] (erm_farm_*, include/ertirt.h): the library samples them concurrently (one host
 # thread per chain) and reduces Post.mean over the devices with one RCCL all-reduce.  Chain 1 starts from MCMC.Para, chain l > 1 from a
 # fresh setInitialValues draw, as nChain separately constructed samplers would.
 function sampleFarm!(M::GibbsAMD, intercept::Bool, onepl::Bool, cov2one::Bool, devices)
     C = M.Cond
     M.shard === nothing || error("a subject-sharded sampler cannot also farm chains")
+    releaseFarm!(M)
     devs = Int32[devices[mod1(l, length(devices))] for l in 1:C.nChain]
     cfg = ErmConfig(modelid(M), C.nItem, C.nSubj, C.nFeat, C.nIter, 1, C.nBurnin, intercept, onepl, cov2one, 0, 0, C.qRt,
                     M.seed, 0, M.precision, 1, 0, 0, 0, 0, 0, 0.0)
@@ -196,9 +205,11 @@ function sampleFarm!(M::GibbsAMD, intercept::Bool, onepl::Bool, cov2one::Bool, d
         bufs = (zeros(N), zeros(J), zeros(J), zeros(N), zeros(J), zeros(J), zeros(nb), zeros(4), zeros(J), zeros(nnu))
         GC.@preserve bufs check(ccall((:erm_farm_get_mean, LIB[]), Cint, (Ptr{Cvoid}, Ref{ErmState}), f[], ErmState(map(ptr, bufs)...)))
         Post.mean = InputPara(θ = bufs[1], a = bufs[2], b = bufs[3], ζ = bufs[4], λ = bufs[5], σ²t = bufs[6], β = bufs[7], Σp = bufs[8], ρ = bufs[9], ν = bufs[10])
-    finally
+    catch
         ccall((:erm_farm_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), f[])
+        rethrow()
     end
+    M.farm = f[]                                            # the traces stay resident for checkConvergenceDevice (the farm's joint diagnostics)
     return M
 end
 
@@ -224,6 +235,7 @@ function sample!(M::GibbsAMD; intercept = false, itemtype::Union{String} = "2pl"
     devices === nothing || thin == 0 || error("posterior predictive checks are not available for a chain farm (devices)")
     devices === nothing || return sampleFarm!(M, Bool(intercept), itemtype == "1pl", Bool(cov2one), collect(devices))
     C = M.Cond
+    releaseFarm!(M)                                         # an earlier farm does not describe this run
     h = engine!(M, intercept, itemtype == "1pl", cov2one)
     check(ccall((:erm_reset_trace, LIB[]), Cint, (Ptr{Cvoid},), h))
     setPointwise!(M, waic)
@@ -392,28 +404,32 @@ end
 
 `checkConvergence` (src/SimTools.jl:419-443) with the ESS / R-hat of every column computed AND counted on the device (`erm_get_convergence`).
 `kind=:rank` counts the rank-normalised diagnostics instead (`erm_get_rank_convergence`): `ess` by bulk-ESS, `essTail` by tail-ESS, `rhat` by rank R-hat.
+After `sample!(MCMC; devices=...)` the counts are the chain farm's: every estimator over the `nChain` independent chains jointly (`erm_farm_get_convergence` /
+`erm_farm_get_rank_convergence`), which is where R-hat sees the variance between chains.  The sampler keeps that farm, with its resident traces, until its next
+`sample!` for this purpose; nothing is computed before the call.
 """
 function checkConvergenceDevice(M::GibbsAMD; kind::Symbol=:basic)
-    M.handle == C_NULL && error("run sample! first")
     kind in (:basic, :rank) || error("kind must be :basic or :rank")
-    if kind == :rank
-        t6 = zeros(Int64, 6)
-        for which in (TRACE_RA, TRACE_RT, TRACE_QR)
-            which == TRACE_RT && M isa GibbsMlIrt && continue
-            c = zeros(Int64, 6)
-            check(ccall((:erm_get_rank_convergence, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}), M.handle, which, c))
-            t6 .+= c
-        end
-        return (ess = 100 * t6[2] / max(t6[1], 1), essTail = 100 * t6[4] / max(t6[3], 1), rhat = 100 * t6[6] / max(t6[5], 1),
-                essN = "$(t6[2]) / $(t6[1])", essTailN = "$(t6[4]) / $(t6[3])", rhatN = "$(t6[6]) / $(t6[5])")
-    end
-    tot = zeros(Int64, 4)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    n = kind == :rank ? 6 : 4
+    tot = zeros(Int64, n)
     for which in (TRACE_RA, TRACE_RT, TRACE_QR)
         which == TRACE_RT && M isa GibbsMlIrt && continue
-        c = zeros(Int64, 4)
-        check(ccall((:erm_get_convergence, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}), M.handle, which, c))
+        c = zeros(Int64, n)
+        if farmed && kind == :rank
+            check(ccall((:erm_farm_get_rank_convergence, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}), M.farm, which, c))
+        elseif farmed
+            check(ccall((:erm_farm_get_convergence, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}), M.farm, which, c))
+        elseif kind == :rank
+            check(ccall((:erm_get_rank_convergence, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}), M.handle, which, c))
+        else
+            check(ccall((:erm_get_convergence, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}), M.handle, which, c))
+        end
         tot .+= c
     end
+    kind == :rank && return (ess = 100 * tot[2] / max(tot[1], 1), essTail = 100 * tot[4] / max(tot[3], 1), rhat = 100 * tot[6] / max(tot[5], 1),
+                             essN = "$(tot[2]) / $(tot[1])", essTailN = "$(tot[4]) / $(tot[3])", rhatN = "$(tot[6]) / $(tot[5])")
     return (ess = 100 * tot[2] / max(tot[1], 1), rhat = 100 * tot[4] / max(tot[3], 1), essN = "$(tot[2]) / $(tot[1])", rhatN = "$(tot[4]) / $(tot[3])")
 end
 

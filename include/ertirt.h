@@ -280,7 +280,9 @@ int erm_copy(void* dst, const void* src, size_t bytes);
  * round-robin to nChain trace slabs (erm_create with n_chain > 1 reproduces that); independent chains leave Post.mean unchanged in
  * expectation and make R-hat meaningful.
  * erm_farm_get_trace fills Post.ra / rt / qr / logLike [nIter][width][nChain] with chain l in slab l.  erm_farm_engine lends chain l's
- * engine (owned by the farm) for erm_get_item_trace / erm_get_diagnostics / erm_get_timing. */
+ * engine (owned by the farm) for erm_get_item_trace / erm_get_diagnostics / erm_get_timing: erm_get_diagnostics (and erm_get_rank_diagnostics) on it remains the
+ * diagnostic of that ONE chain, M = 2 split halves, blind to the other chains.  erm_farm_get_diagnostics and its three siblings below add what several chains are
+ * run for: the estimators over all chains jointly, between-chain variance included. */
 typedef struct erm_farm* erm_farm_handle;
 int erm_farm_create(const erm_config* cfg, const int32_t* devices, int32_t n_chains, erm_farm_handle* out);
 void erm_farm_destroy(erm_farm_handle f);
@@ -295,6 +297,24 @@ int erm_farm_get_trace(erm_farm_handle f, int which, double* out);
 int erm_farm_get_mean(erm_farm_handle f, erm_state* out);
 int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Dbar over the rows of all chains, Dhat at the joint Post.mean (the same reduction as erm_farm_get_mean, evaluated on the first device) */
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed);
+/* The farm's joint convergence diagnostics: the estimators of erm_get_diagnostics / erm_get_convergence / erm_get_rank_diagnostics / erm_get_rank_convergence, as
+ * defined there, applied to the L = erm_farm_chains chains jointly -- chain l takes the place of interleaved chain l: M = 2 L sequences of
+ * n = floor((n_iter - n_burnin) / 2) draws, S = M n pooled draws for the rank estimators.  Same NaN rules, same -M n case, same stop rule, same thresholds for the
+ * counts; width erm_trace_width(erm_farm_engine(f, 0), which); output in the caller's column order (GibbsRtIrtCrossQr's nu block column-major, as erm_get_diagnostics
+ * returns it).  A farm of one chain returns what erm_get_diagnostics of its engine returns, bit for bit.
+ * Everything is computed on the device of chain 0 by the kernels the engine entries run: a gather kernel copies the post-burn-in rows of a chunk of columns of every
+ * chain into one interleaved scratch (at most 256 MB of gathered draws a chunk; the rank estimators stage as much again), and the full traces never cross to the
+ * host.  A chain on another device compacts its chunk into a slab there, which is copied to chain 0's device (hipMemcpyPeerAsync; peer access is not enabled and
+ * no device setting is touched).  The calls only read the farm.  ERM_FARM_DIAG_CHUNK (environment) caps the chunk length in columns and ERM_FARM_DIAG_REMOTE=1
+ * sends every chain but chain 0 through the slab path whatever its device: neither changes a result by a bit (tests).
+ * Limits: at most 16 chains and at least 8 post-burn-in iterations (ERM_ERR_ARG); the rank entries also S <= 8192 (ERM_ERR_ARG, the message names the cap); every
+ * chain has recorded all n_iter rows (ERM_ERR_STATE, the message names the chain); ERM_TRACE_FULL, and the nu block recorded for GibbsRtIrtCrossQr's qr
+ * (ERM_ERR_NOTRACE); `which` = ERM_TRACE_LOGLIKE or a trace the model lacks: ERM_ERR_ARG; no scratch: ERM_ERR_NOMEM.  NULL outputs as the engine entries treat
+ * them: ess, rhat, counts4 and counts6 are required, any of the three rank vectors may be NULL. */
+int erm_farm_get_diagnostics(erm_farm_handle f, int which, double* ess, double* rhat);
+int erm_farm_get_convergence(erm_farm_handle f, int which, int64_t* counts4);
+int erm_farm_get_rank_diagnostics(erm_farm_handle f, int which, double* ess_bulk, double* ess_tail, double* rhat_rank);
+int erm_farm_get_rank_convergence(erm_farm_handle f, int which, int64_t* counts6);
 int64_t erm_farm_post_count(erm_farm_handle f);
 int erm_farm_used_rccl(erm_farm_handle f);                  /* 1 if the last erm_farm_get_mean reduced over RCCL */
 /* What a multi-GPU benchmark of the farm reports: wall-clock of the last erm_farm_run (all chains, host side), the device time of each chain's
@@ -338,6 +358,11 @@ int erm_debug_convergence(int device, int64_t n, const double* ess, const double
  * ERM_ERR_NONFINITE.  Serves traces that are not resident on one device (erm_farm_get_trace output) and the tests. */
 int erm_debug_rank_diagnostics(int device, int precision, const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain,
                                double* ess_bulk, double* ess_tail, double* rhat_rank);
+
+/* The same for the basic estimator: erm_get_diagnostics' kernel (diag_kernel, at n_iter = n_draw and n_burnin = 0) on caller-supplied draws x[n_draw][n_col][n_chain],
+ * with the same layout, the same rounding to float under ERM_PREC_F32 and the same refusal of a NaN (ERM_ERR_NONFINITE).  ess and rhat (n_col doubles each) are
+ * required; at least 8 draws and at most 16 chains (ERM_ERR_ARG). */
+int erm_debug_diagnostics(int device, int precision, const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain, double* ess, double* rhat);
 
 /* n draws of the generalized inverse Gaussian GIG(p, a, b) (density ~ x^(p-1) exp(-(a x + b/x)/2); the distribution type of
  * src/GenInvGaussian.jl:17-30, whose sampler :76-106 is dead code in the reference) by Devroye's (2014) sampler, fp64; element k uses
