@@ -66,6 +66,7 @@ EXPORTS = [
     "erm_set_predictive", "erm_predictive_reps", "erm_get_predictive",
     "erm_get_rank_diagnostics", "erm_get_rank_convergence", "erm_debug_rank_diagnostics",
     "erm_farm_get_diagnostics", "erm_farm_get_convergence", "erm_farm_get_rank_diagnostics", "erm_farm_get_rank_convergence", "erm_debug_diagnostics",
+    "erm_get_marginal_waic", "erm_farm_get_marginal_waic", "erm_marginal_loglik",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -202,6 +203,10 @@ def load():
     lib.erm_farm_get_rank_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erm_farm_get_rank_convergence.argtypes = [H, C.c_int, C.c_void_p]
     lib.erm_debug_diagnostics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.erm_get_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_marginal_loglik.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -209,6 +214,41 @@ def load():
 def check(rc: int):
     if rc != 0:
         raise ErmError(f"libertirt error {rc}: {load().erm_last_error().decode()}")
+
+
+MARGINAL_MODELS = (MODEL_MLIRT, MODEL_RTIRT, MODEL_NULL, MODEL_CROSS, MODEL_LATENT)      # the models erm_get_marginal_waic serves (no quantile weights)
+MARGINAL_NODES = 61
+
+
+def marginal_nodes(nodes):
+    """The node count of the marginal WAIC's theta rule as the library accepts it: odd and in 3 .. 1025 (None or 0: the default, 61)."""
+    if nodes is None or nodes == 0:
+        return MARGINAL_NODES
+    Q = int(nodes)
+    if Q != nodes or Q < 3 or Q > 1025 or Q % 2 == 0:
+        raise ValueError("nodes must be odd and in 3 .. 1025")
+    return Q
+
+
+def item_trace_width(model, J, F):
+    """Columns of an item-trace row: a, b, lambda, sig2t [4][J], then the kernels' small part of qr (item_trace_width of csrc/erm_model.hpp)."""
+    t = MODEL_TRAITS[model]
+    Fk = kernel_feat(model, F)
+    head = J if t.rho else {"none": 0, "vec": Fk + 1, "pair": 2 * (Fk + 1), "latent": Fk + 2, "zero_pair": 2 * (Fk + 1)}[t.beta]
+    return 4 * J + head + (4 if t.rt else 0)
+
+
+def _marginal_result(out, lppd, p):
+    res = dict(elpd=float(out[0]), pWaic=float(out[1]), WAIC=float(out[2]), se=float(out[3]), lppd=float(out[4]), nUnits=int(out[5]), nRows=int(out[6]),
+               nHighVar=int(out[7]), nNodes=int(out[8]), nCoarse=int(out[9]))
+    return (res, lppd, p) if lppd is not None else res
+
+
+def _marginal_call(fn, h, nodes, n_subj, pointwise):
+    out = np.empty(10, dtype=np.float64)
+    lppd, p = (np.empty(n_subj), np.empty(n_subj)) if pointwise else (None, None)
+    check(fn(h, marginal_nodes(nodes), out.ctypes.data, None if lppd is None else lppd.ctypes.data, None if p is None else p.ctypes.data))
+    return _marginal_result(out, lppd, p)
 
 
 STATE_FIELDS = ("theta", "a", "b", "zeta", "lambda_", "sig2t", "beta", "sigp", "rho", "nu")
@@ -385,6 +425,11 @@ class Engine:
             return lppd.reshape(sh, order="F"), p.reshape(sh, order="F")
         return lppd, p
 
+    def marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_get_marginal_waic: WAIC with every subject's theta and zeta integrated out, computed on the device from the resident item trace after the run.
+        The totals (erm_get_waic's, with nNodes and nCoarse); with pointwise=True (totals, lppd_i, p_i)."""
+        return _marginal_call(self._lib.erm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
+
     # ---- posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     def set_predictive(self, on=True, thin=1):
         """Enable the replicate pass (every thin-th post-burn-in row is replicated) or turn it off; only while no trace row is recorded."""
@@ -558,6 +603,10 @@ class Farm:
         check(self._lib.erm_farm_get_dic(self._h, out.ctypes.data))
         return dict(Dbar=float(out[0]), Dhat=float(out[1]), pD=float(out[2]), DIC=float(out[3]))
 
+    def marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_farm_get_marginal_waic: Engine.marginal_waic over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
+        return _marginal_call(self._lib.erm_farm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
+
     # ---- joint convergence diagnostics over all chains (erm_farm_get_diagnostics and its siblings); engine(l).diagnostics(which) stays the diagnostic of chain l alone
     def _width(self, which: int):
         return int(self._lib.erm_trace_width(self._lib.erm_farm_engine(self._h, 0), which))
@@ -613,6 +662,35 @@ class Farm:
         out = np.empty((self.cfg.n_iter, w, self.n_chains), dtype=np.float64, order="F")
         check(self._lib.erm_farm_get_trace(self._h, which, out.ctypes.data))
         return out
+
+
+def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
+    """erm_marginal_loglik: the marginal WAIC's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
+    Engine.item_trace() returns them.  Returns a dict: l [N, R] (every l_i^(s)), and -- with want_waic, which needs R >= 2 -- totals, lppd [N], p [N]."""
+    Ya = np.asarray(Y)
+    Yf = np.asfortranarray(Ya.astype(np.uint8))
+    if Yf.ndim != 2:
+        raise ValueError("Y must be [subject, item]")
+    N, J = Yf.shape
+    lt = None if logT is None else np.asfortranarray(logT, dtype=np.float64)
+    xx = None if X is None or np.size(X) == 0 else np.asfortranarray(X, dtype=np.float64)
+    F = 0 if xx is None else xx.shape[1]
+    if (lt is not None and lt.shape != (N, J)) or (xx is not None and xx.shape[0] != N):
+        raise ValueError("logT / X do not match Y")
+    rr = np.ascontiguousarray(rows, dtype=np.float64)
+    if model in MODEL_TRAITS and (rr.ndim != 2 or rr.shape[1] != item_trace_width(model, J, F)):
+        raise ValueError(f"rows must be [row, {item_trace_width(model, J, F)}]")
+    R = rr.shape[0]
+    l = np.empty((N, R), dtype=np.float64, order="F") if want_l else None
+    out = np.empty(10, dtype=np.float64) if want_waic else None
+    lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    check(load().erm_marginal_loglik(int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, R, marginal_nodes(nodes),
+                                     ptr(l), ptr(out), ptr(lppd), ptr(p)))
+    res = dict(l=l)
+    if want_waic:
+        res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
+    return res
 
 
 def rccl_unique_id() -> bytes:

@@ -102,12 +102,15 @@ class OutputDic:
 class OutputWaic:
     """WAIC of a fit (getWaic; the reference offers DIC only): elpd = sum_u (lppd_u - p_u), pWaic = sum_u p_u, WAIC = -2 elpd, se = 2 sqrt(U Var_u(elpd_u)),
     nHighVar = number of units with p_u > 0.4; unit is "subject" or "cell", nUnits = U, nRows = the post-burn-in rows behind it.  lppd_u / p_u (pointwise=True):
-    subjects in order, cells as (nSubj, nItem)."""
+    subjects in order, cells as (nSubj, nItem).  unit "subject-marginal" (getWaicMarginal): theta_i and zeta_i integrated out; nNodes = the nodes of the theta
+    rule, nCoarse = the subjects whose posterior was too narrow for it at some row (None for the conditional WAIC)."""
 
-    def __init__(self, elpd=None, pWaic=None, WAIC=None, se=None, nHighVar=None, lppd=None, unit=None, nUnits=None, nRows=None, lppd_u=None, p_u=None):
+    def __init__(self, elpd=None, pWaic=None, WAIC=None, se=None, nHighVar=None, lppd=None, unit=None, nUnits=None, nRows=None, lppd_u=None, p_u=None,
+                 nNodes=None, nCoarse=None):
         self.elpd, self.pWaic, self.WAIC, self.se, self.nHighVar = elpd, pWaic, WAIC, se, nHighVar
         self.lppd, self.unit, self.nUnits, self.nRows = lppd, unit, nUnits, nRows
         self.lppd_u, self.p_u = lppd_u, p_u
+        self.nNodes, self.nCoarse = nNodes, nCoarse
 
     @property
     def elpd_u(self):

@@ -20,6 +20,7 @@
 #include "erm_kernels.hpp"
 #include "erm_predictive_kernels.hpp"      // posterior predictive checks: the replicate pass behind every sweep
 #include "erm_rank_diag_kernels.hpp"       // rank-normalised convergence diagnostics: bulk / tail ESS, rank R-hat
+#include "erm_marginal_kernels.hpp"        // marginal WAIC: theta and zeta integrated out, from the item trace
 #include "erm_farm_diag.hpp"               // the chain farm's joint diagnostics: chunk arithmetic
 #include "erm_geometry.hpp"
 #include "erm_model.hpp"
@@ -166,6 +167,114 @@ static int rank_diag_run(const T* tr, int64_t ld, int64_t ncol, int nChain, int 
     return 0;
 }
 
+// WAIC's totals from per-unit accumulators (erm_pointwise.hpp) on the device: the one place that launches pointwise_finish_kernel -- for erm_get_waic /
+// erm_get_pointwise (the accumulators the pass behind the sweep fills) and for the marginal WAIC (those marginal_kernel fills).
+// one launch of the finish kernel; sums[0..4]: its columns added over the workgroups in order
+static int pw_finish_on(const double2* acc_ms, const double2* acc_w, int64_t U, int64_t n, double center, double* lppd_out, double* p_out, hipStream_t stream, double* sums)
+{
+    const int nb = (int)std::min<int64_t>(1024, (U + 255) / 256);
+    DevBuf dPart;
+    if (int rc = dPart.alloc((size_t)nb * PW_FIN_COLS * sizeof(double))) return rc;
+    PwFinArgs a{};
+    a.acc_ms = acc_ms; a.acc_w = acc_w; a.U = U; a.n = n; a.center = center;
+    a.lppd_out = lppd_out; a.p_out = p_out; a.part = dPart.as<double>();
+    hipLaunchKernelGGL(pointwise_finish_kernel, dim3(nb), dim3(256), 0, stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    std::vector<double> part((size_t)nb * PW_FIN_COLS);
+    HIPCHK(hipMemcpy(part.data(), dPart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int q = 0; q < PW_FIN_COLS; ++q) { double t = 0.0; for (int b = 0; b < nb; ++b) t += part[(size_t)b * PW_FIN_COLS + q]; sums[q] = t; }
+    return 0;
+}
+// out8 of erm_get_waic: two launches (the sums, then the squared deviations of elpd_u from its mean over the units)
+static int pw_totals(const double2* acc_ms, const double2* acc_w, int64_t units, int64_t n, hipStream_t stream, double* out8)
+{
+    const double U = (double)units;
+    double s0[PW_FIN_COLS], s1[PW_FIN_COLS];
+    if (int rc = pw_finish_on(acc_ms, acc_w, units, n, 0.0, nullptr, nullptr, stream, s0)) return rc;
+    if (int rc = pw_finish_on(acc_ms, acc_w, units, n, s0[2] / U, nullptr, nullptr, stream, s1)) return rc;
+    const double var_u = U > 1.0 ? s1[3] / (U - 1.0) : 0.0;
+    out8[0] = s0[2]; out8[1] = s0[1]; out8[2] = -2.0 * s0[2]; out8[3] = 2.0 * std::sqrt(U * var_u);
+    out8[4] = s0[0]; out8[5] = U; out8[6] = (double)n; out8[7] = s0[4];
+    return 0;
+}
+
+// Marginal WAIC (erm_marginal_kernels.hpp; include/ertirt.h: erm_get_marginal_waic): the one place that launches marginal_kernel -- for an engine's resident
+// data set and item trace, for a farm's table of rows and for erm_marginal_loglik's caller-supplied data.  Everything it is given lives on the current device.
+struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; };
+static int marg_refuse_model(int model)
+{
+    if (model == ERM_MODEL_CROSSQR || model == ERM_MODEL_LATENTQR)
+        return fail(ERM_ERR_ARG, "the marginal WAIC serves the five models without quantile weights: with nu integrated out the response-time term is no longer "
+                                 "Gaussian in zeta and the zeta integral has no closed form");
+    if (!marg_served(model)) return fail(ERM_ERR_ARG, "unknown model");
+    return 0;
+}
+static int marg_nodes(int32_t n_nodes, int* Q)
+{
+    *Q = n_nodes == 0 ? MARG_NODES_DEFAULT : n_nodes;
+    if (!marg_nodes_ok(*Q)) return fail(ERM_ERR_ARG, "n_nodes must be 0 (= " + std::to_string(MARG_NODES_DEFAULT) + ") or odd and in " + std::to_string(MARG_NODES_MIN) + " .. " + std::to_string(MARG_NODES_MAX));
+    return 0;
+}
+template <typename real>
+static int marginal_run(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double* out10, double* lppd_u, double* p_u)
+{
+    const bool totals = out10 || lppd_u || p_u;
+    if (totals && n_rows < 2) return fail(ERM_ERR_STATE, "the marginal WAIC needs at least two post-burn-in rows");
+    const int64_t N = D.N, ld = item_trace_width(D.model, D.J, D.Fk);
+    DevBuf dMs, dW, dCoarse, dCnt, dL, dP;
+    const char* what = "the marginal WAIC's accumulators";
+    if (totals) {
+        if (int rc = dMs.try_alloc((size_t)N * sizeof(double2), what)) return rc;
+        if (int rc = dW.try_alloc((size_t)N * sizeof(double2), what)) return rc;
+        if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
+        if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
+        if (lppd_u) if (int rc = dL.try_alloc((size_t)N * sizeof(double), what)) return rc;
+        if (p_u) if (int rc = dP.try_alloc((size_t)N * sizeof(double), what)) return rc;
+    }
+    MargArgs a{};
+    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = ld; a.N = N; a.J = D.J; a.F = D.Fk; a.Q = Q;
+    a.l_out = l_dev; a.acc_ms = dMs.as<double2>(); a.acc_w = dW.as<double2>(); a.coarse = dCoarse.as<unsigned int>();
+    const size_t lds = (size_t)2 * marg_row_lds(ld, D.J) * sizeof(double);
+    const dim3 grid((unsigned)((N + MARG_TILE - 1) / MARG_TILE));
+    auto launch = [&](auto M) -> int {
+        constexpr int MODEL = decltype(M)::value;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&marginal_kernel<MODEL, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((marginal_kernel<MODEL, real>), grid, dim3(256), lds, stream, a);
+        return 0;
+    };
+    int rc = 0;
+    switch (D.model) {
+    case ERM_MODEL_MLIRT: rc = launch(std::integral_constant<int, MLIRT>{}); break;
+    case ERM_MODEL_RTIRT: rc = launch(std::integral_constant<int, RTIRT>{}); break;
+    case ERM_MODEL_NULL: rc = launch(std::integral_constant<int, NULLM>{}); break;
+    case ERM_MODEL_CROSS: rc = launch(std::integral_constant<int, CROSS>{}); break;
+    case ERM_MODEL_LATENT: rc = launch(std::integral_constant<int, LATENT>{}); break;
+    default: return marg_refuse_model(D.model);
+    }
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!totals) return 0;
+    double out8[8], sums[PW_FIN_COLS];
+    if (int rc2 = pw_totals(dMs.as<double2>(), dW.as<double2>(), N, n_rows, stream, out8)) return rc2;
+    if (lppd_u || p_u) {
+        if (int rc2 = pw_finish_on(dMs.as<double2>(), dW.as<double2>(), N, n_rows, 0.0, dL.as<double>(), dP.as<double>(), stream, sums)) return rc2;
+        if (lppd_u) HIPCHK(hipMemcpy(lppd_u, dL.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+        if (p_u) HIPCHK(hipMemcpy(p_u, dP.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (out10) {
+        hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        unsigned long long nc = 0;
+        HIPCHK(hipMemcpy(&nc, dCnt.p, sizeof(nc), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 8; ++k) out10[k] = out8[k];
+        out10[8] = (double)Q; out10[9] = (double)nc;
+    }
+    return 0;
+}
+
 // A persistent launch needs all its workgroups resident at once.  Two persistent launches of ONE process on one device (a farm's chains sharing a
 // device, several engines) could each hold some compute units and wait for the other's for ever: they take turns.
 std::mutex g_persist_mu[64];
@@ -191,6 +300,9 @@ struct EngineBase {
     virtual int get_waic(double* out8) = 0;
     virtual int64_t pointwise_units() const = 0;
     virtual int get_pointwise(double* lppd_u, double* p_u) = 0;
+    // marginal WAIC (erm_get_marginal_waic; the farm hands chain 0 a table of the rows of all chains on its device: rows != NULL), and the resident item trace
+    virtual int marginal_waic(int Q, const double* rows, int64_t n_rows, double* out10, double* lppd_u, double* p_u) = 0;
+    virtual const double* item_trace_dev() const = 0;
     // posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     virtual int set_predictive(int on, int32_t thin) = 0;
     virtual int64_t predictive_reps() const = 0;
@@ -751,33 +863,27 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipSetDevice(cfg.device));
         return 0;
     }
-    // one launch of the finish kernel; sums[0..4]: its columns added over the workgroups in order
     int pw_finish(double center, double* lppd_out, double* p_out, double* sums) {
-        const int64_t U = pointwise_units();
-        const int nb = (int)std::min<int64_t>(1024, (U + 255) / 256);
-        DevBuf dPart;
-        if (int rc = dPart.alloc((size_t)nb * PW_FIN_COLS * sizeof(double))) return rc;
-        PwFinArgs a{};
-        a.acc_ms = dPwMs.as<double2>(); a.acc_w = dPwW.as<double2>(); a.U = U; a.n = post_rows; a.center = center;
-        a.lppd_out = lppd_out; a.p_out = p_out; a.part = dPart.as<double>();
-        hipLaunchKernelGGL(pointwise_finish_kernel, dim3(nb), dim3(256), 0, stream, a);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
-        std::vector<double> part((size_t)nb * PW_FIN_COLS);
-        HIPCHK(hipMemcpy(part.data(), dPart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int q = 0; q < PW_FIN_COLS; ++q) { double t = 0.0; for (int b = 0; b < nb; ++b) t += part[(size_t)b * PW_FIN_COLS + q]; sums[q] = t; }
-        return 0;
+        return pw_finish_on(dPwMs.as<double2>(), dPwW.as<double2>(), pointwise_units(), post_rows, center, lppd_out, p_out, stream, sums);
     }
     int get_waic(double* out8) override {
         if (int rc = pw_ready()) return rc;
-        const double U = (double)pointwise_units();
-        double s0[PW_FIN_COLS], s1[PW_FIN_COLS];
-        if (int rc = pw_finish(0.0, nullptr, nullptr, s0)) return rc;
-        if (int rc = pw_finish(s0[2] / U, nullptr, nullptr, s1)) return rc;      // second pass: squared deviations of elpd_u from its mean over the units
-        const double var_u = U > 1.0 ? s1[3] / (U - 1.0) : 0.0;
-        out8[0] = s0[2]; out8[1] = s0[1]; out8[2] = -2.0 * s0[2]; out8[3] = 2.0 * std::sqrt(U * var_u);
-        out8[4] = s0[0]; out8[5] = U; out8[6] = (double)post_rows; out8[7] = s0[4];
-        return 0;
+        return pw_totals(dPwMs.as<double2>(), dPwW.as<double2>(), pointwise_units(), post_rows, stream, out8);
+    }
+    // ---- marginal WAIC: computed after the run from the resident data set and item-trace rows (rows == NULL: this chain's own post-burn-in rows, read in place)
+    const double* item_trace_dev() const override { return dTrItem.as<double>(); }
+    int marginal_waic(int Q, const double* rows, int64_t n_rows, double* out10, double* lppd_u, double* p_u) override {
+        if (int rc = marg_refuse_model(cfg.model)) return rc;
+        if (sharded()) return fail(ERM_ERR_STATE, "the marginal WAIC is not available on a shard (every subject's data must be resident on one device)");
+        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
+        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
+        if (!rows) {
+            if (post_rows < 2) return fail(ERM_ERR_STATE, "the marginal WAIC needs at least two post-burn-in rows");
+            rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows;
+        }
+        HIPCHK(hipSetDevice(cfg.device));
+        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
+        return marginal_run<real>(D, rows, n_rows, Q, stream, nullptr, out10, lppd_u, p_u);
     }
     int get_pointwise(double* lppd_u, double* p_u) override {
         if (int rc = pw_ready()) return rc;
@@ -2039,6 +2145,14 @@ int erm_set_pointwise(erm_handle h, int unit) { CHK_H; return h->e->set_pointwis
 int erm_get_waic(erm_handle h, double* out_eight) { CHK_H; if (!out_eight) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_waic(out_eight); }
 int64_t erm_pointwise_units(erm_handle h) { return h ? h->e->pointwise_units() : -1; }
 int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u) { CHK_H; return h->e->get_pointwise(lppd_u, p_u); }
+int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
+{
+    CHK_H;
+    if (!out10) return fail(ERM_ERR_ARG, "out is NULL");
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    return h->e->marginal_waic(Q, nullptr, 0, out10, lppd_u, p_u);
+}
 int erm_set_predictive(erm_handle h, int on, int32_t thin) { CHK_H; return h->e->set_predictive(on, thin); }
 int64_t erm_predictive_reps(erm_handle h) { return h ? h->e->predictive_reps() : -1; }
 int erm_get_predictive(erm_handle h, double* item, double* subj, double* total) { CHK_H; return h->e->get_predictive(item, subj, total); }
@@ -2248,6 +2362,36 @@ int erm_farm_get_dic(erm_farm_handle f, double* out4)
     for (auto& e : f->eng) chains.push_back(e->e.get());
     return dic_from_summary(chains.data(), chains.size(), acc[d0].as<double>(), total, out4);
 }
+// The farm's marginal WAIC: the post-burn-in item-trace rows of chain 0, chain 1, ... as ONE table on chain 0's device, whose resident data set supplies the data.
+// A chain's rows cross through the host whatever its device (item-level: a few hundred kilobytes); a farm of one chain takes the same path as several.
+int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
+{
+    CHK_F;
+    if (!out10) return fail(ERM_ERR_ARG, "out is NULL");
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
+    const int L = (int)f->eng.size();
+    EngineBase* e0 = f->eng[0]->e.get();
+    const int64_t wi = e0->item_trace_width(), rows = e0->rows_done, post = e0->post_rows;
+    for (int l = 0; l < L; ++l) {
+        const EngineBase* e = f->eng[l]->e.get();
+        if (e->rows_done != rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + std::to_string(e->rows_done) + " rows recorded where chain 0 has " + std::to_string(rows));
+        if (e->post_rows < 2) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": the marginal WAIC needs at least two post-burn-in rows");
+    }
+    std::vector<double> table((size_t)L * post * wi);
+    for (int l = 0; l < L; ++l) {
+        const EngineBase* e = f->eng[l]->e.get();
+        HIPCHK(hipSetDevice(f->dev[l]));
+        HIPCHK(hipStreamSynchronize(e->work_stream()));
+        HIPCHK(hipMemcpy(table.data() + (size_t)l * post * wi, e->item_trace_dev() + (size_t)(rows - post) * wi, (size_t)post * wi * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipSetDevice(f->dev[0]));
+    DevBuf dTab;
+    if (int rc = dTab.try_alloc(table.size() * sizeof(double), "the farm's table of item-trace rows")) return rc;
+    H2D(dTab.p, table.data(), table.size() * sizeof(double));
+    return e0->marginal_waic(Q, dTab.as<double>(), (int64_t)L * post, out10, lppd_u, p_u);
+}
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed)
 {
     CHK_F;
@@ -2299,6 +2443,65 @@ int erm_farm_get_rank_convergence(erm_farm_handle f, int which, int64_t* counts6
 const char* erm_last_error(void) { return g_err.c_str(); }
 const char* erm_version(void) { return "ertirt-amd 0.4.0 (gfx950)"; }
 int erm_abi_version(void) { return ERM_ABI_VERSION; }
+
+int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                        int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u)
+{
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    const ModelTraits mt = model_traits(model);
+    if (n_subj <= 0 || n_subj >= (1LL << 32) || n_item <= 0 || n_item > 896 || n_feat < 0 || n_feat > MARG_MAXF) return fail(ERM_ERR_ARG, "n_subj, n_item (1 .. 896) or n_feat (0 .. " + std::to_string(MARG_MAXF) + ") out of range");
+    const int64_t N = n_subj; const int J = n_item, Fk = kernel_feat(model, n_feat);
+    if (!Y || !rows) return fail(ERM_ERR_ARG, "Y / rows is NULL");
+    if (mt.rt && !logT) return fail(ERM_ERR_ARG, "logT is required for response-time models");
+    if (Fk > 0 && !X) return fail(ERM_ERR_ARG, "X is required when n_feat > 0");
+    const bool totals = out10 || lppd_u || p_u;
+    if (n_rows < 1 || (totals && n_rows < 2)) return fail(ERM_ERR_ARG, "n_rows must be at least 1 (at least 2 for the WAIC outputs)");
+    const int64_t wi = item_trace_width(model, J, Fk);
+    const size_t NJ = (size_t)N * J;
+    // ---- the inputs: a NaN anywhere, then rows outside the model's domain
+    for (size_t e = 0; e < (size_t)n_rows * wi; ++e) if (rows[e] != rows[e]) return fail(ERM_ERR_NONFINITE, "NaN in row " + std::to_string(e / (size_t)wi));
+    if (mt.rt) for (size_t e = 0; e < NJ; ++e) if (logT[e] != logT[e]) return fail(ERM_ERR_NONFINITE, "NaN in logT");
+    for (size_t e = 0; e < (size_t)N * Fk; ++e) if (X[e] != X[e]) return fail(ERM_ERR_NONFINITE, "NaN in X");
+    for (size_t e = 0; e < NJ; ++e) if (Y[e] > 1) return fail(ERM_ERR_ARG, "Y must be 0/1");
+    if (mt.rt) for (int64_t r = 0; r < n_rows; ++r) {
+        const double* row = rows + (size_t)r * wi;
+        for (int j = 0; j < J; ++j) if (!(row[3 * J + j] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": sig2t must be positive");
+        const double* S = row + 4 * J + qr_sigp_off(model, J, Fk);
+        if (!(S[0] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": Sigma_p[1,1] must be positive");
+        if (marg_law(model, 0.0, 0.0, 0.0, S).v < 0.0) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": the conditional variance of zeta given theta is negative (Sigma_p is not positive semi-definite)");
+    }
+    HIPCHK(hipSetDevice(device));
+    // ---- upload: the data set row-major in fp64, as the kernel reads an engine's
+    DevBuf dY, dC, dX, dRows, dL;
+    const char* what = "erm_marginal_loglik's inputs";
+    {
+        std::vector<uint8_t> y(NJ);
+        cols_to_rows(Y, y.data(), N, (int64_t)J);
+        if (int rc = dY.try_alloc(NJ, what)) return rc;
+        H2D(dY.p, y.data(), NJ);
+    }
+    if (mt.rt) {
+        std::vector<double> c(NJ);
+        cols_to_rows(logT, c.data(), N, (int64_t)J);
+        if (int rc = dC.try_alloc(NJ * sizeof(double), what)) return rc;
+        H2D(dC.p, c.data(), NJ * sizeof(double));
+    }
+    if (Fk > 0) {
+        std::vector<double> x((size_t)N * Fk);
+        cols_to_rows(X, x.data(), N, (int64_t)Fk);
+        if (int rc = dX.try_alloc(x.size() * sizeof(double), what)) return rc;
+        H2D(dX.p, x.data(), x.size() * sizeof(double));
+    }
+    if (int rc = dRows.try_alloc((size_t)n_rows * wi * sizeof(double), what)) return rc;
+    H2D(dRows.p, rows, (size_t)n_rows * wi * sizeof(double));
+    if (l) if (int rc = dL.try_alloc((size_t)N * n_rows * sizeof(double), "erm_marginal_loglik's output")) return rc;
+    const MargData D{dY.as<uint8_t>(), dC.p, dX.p, nullptr, N, J, Fk, model};
+    if (int rc = marginal_run<double>(D, dRows.as<double>(), n_rows, Q, nullptr, dL.as<double>(), out10, lppd_u, p_u)) return rc;
+    if (l) HIPCHK(hipMemcpy(l, dL.p, (size_t)N * n_rows * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
 
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out)
 {

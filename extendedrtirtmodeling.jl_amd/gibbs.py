@@ -550,6 +550,127 @@ def compareWaic(A, B) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Marginal WAIC (include/ertirt.h: erm_get_marginal_waic).  Unit = a subject with theta_i and zeta_i integrated out: zeta analytically, theta by a fixed
+# rule of equally spaced nodes over mu +- 6 sd of the population law.  l_i^(s) depends on row s of the item-level trace only, so it is computed after the run.
+# ------------------------------------------------------------------------------------------------------------------
+MARGINAL_UNIT = "subject-marginal"
+
+
+def _marginal_source(MCMC):
+    src = getattr(MCMC, "farm", None) or MCMC._engine
+    if src is None:
+        raise ValueError("run sample! first (getWaicMarginal reads the engine's resident item trace and data set)")
+    return src
+
+
+def _marginal_check(MCMC, nodes):
+    if MCMC._model not in _lib.MARGINAL_MODELS:
+        raise ValueError(f"getWaicMarginal is not available for {type(MCMC).__name__}: with the quantile weights integrated out the response-time term is not Gaussian in "
+                         "zeta and the zeta integral has no closed form")
+    if MCMC.shard is not None:
+        raise ValueError("getWaicMarginal is not available for a subject-sharded sampler (every subject's data must be resident on one device)")
+    return _lib.marginal_nodes(nodes)
+
+
+def getWaicMarginal(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, pointwise=False) -> OutputWaic:
+    """Marginal WAIC of the last sample! -- of one engine or of the chain farm of sample!(...; devices=), whose chains' post-burn-in rows enter as one table --
+    computed on the device from the resident item trace and data set (erm_get_marginal_waic / erm_farm_get_marginal_waic); needs no waic= at sample!.
+    unit = "subject-marginal"; nNodes = nodes, nCoarse = the subjects for which the rule was too coarse at some row (raise nodes if it is not 0).
+    pointwise=True also fetches lppd_i and p_i, which compareWaic needs."""
+    Q = _marginal_check(MCMC, nodes)
+    r = _marginal_source(MCMC).marginal_waic(Q, pointwise=pointwise)
+    w, lppd_u, p_u = r if pointwise else (r, None, None)
+    return OutputWaic(elpd=w["elpd"], pWaic=w["pWaic"], WAIC=w["WAIC"], se=w["se"], nHighVar=w["nHighVar"], lppd=w["lppd"], unit=MARGINAL_UNIT, nUnits=w["nUnits"],
+                      nRows=w["nRows"], lppd_u=lppd_u, p_u=p_u, nNodes=w["nNodes"], nCoarse=w["nCoarse"])
+
+
+def marginalLogLikHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, with_S=False) -> np.ndarray:
+    """l_i^(s) of the marginal WAIC with numpy (the test twin of marginal_kernel): an (R, N) array for the item-trace rows [R, item_trace_width] (as
+    Engine.item_trace() returns them) and the data Y, logT [N, J], X [N, F] or None.  with_S=True also returns S = sum_q exp(e_q - max_q e_q) per (row, subject):
+    S < 2 marks a posterior too narrow for the rule."""
+    from scipy.special import logsumexp
+    t = _lib.MODEL_TRAITS[model]
+    Q = _lib.marginal_nodes(nodes)
+    Y = np.asarray(Y, dtype=np.float64)
+    N, J = Y.shape
+    F = 0 if X is None or not t.sees_x else np.shape(X)[1]
+    x1 = np.ones((N, 1)) if F == 0 else np.hstack([np.ones((N, 1)), np.asarray(X, dtype=np.float64)])
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    if rows.shape[1] != _lib.item_trace_width(model, J, F):
+        raise ValueError(f"rows must have {_lib.item_trace_width(model, J, F)} columns")
+    h = 12.0 / (Q - 1)
+    z = -6.0 + h * np.arange(Q)
+    out, outS = np.empty((rows.shape[0], N)), np.empty((rows.shape[0], N))
+    zero = np.zeros(N)
+    for s, row in enumerate(rows):
+        a, b, lam, sg, q = row[:J], row[J:2 * J], row[2 * J:3 * J], row[3 * J:4 * J], row[4 * J:]
+        rho = q[:J] if t.rho else np.zeros(J)
+        if model == _lib.MODEL_MLIRT:
+            mu, s11 = x1 @ q[:F + 1], 1.0
+        else:
+            Sp = q[len(q) - 4:]
+            s11, s12, s22 = Sp[0], 0.5 * (Sp[1] + Sp[2]), Sp[3]
+            if model == _lib.MODEL_RTIRT:
+                mu = x1 @ q[:F + 1]
+                m1 = s12 / s11
+                m0, v = x1 @ q[F + 1:2 * F + 2] - m1 * mu, s22 - s12 * s12 / s11
+            elif model == _lib.MODEL_LATENT:
+                mu, m0, m1, v = zero, x1 @ q[:F + 1], q[F + 1], s22
+            else:
+                mu, m0, m1, v = zero, zero, s12 / s11, s22 - s12 * s12 / s11
+        th = mu[:, None] + np.sqrt(s11) * z[None, :]                                  # (N, Q)
+        eta = a[None, None, :] * (th[:, :, None] - b[None, None, :])                  # (N, Q, J)
+        e = np.log(h) - 0.5 * np.log(2 * np.pi) - 0.5 * z[None, :] ** 2 + np.sum(Y[:, None, :] * eta - _log1pexp(eta), axis=2)
+        if t.rt:
+            g = 1.0 / sg
+            d = lam[None, None, :] - np.asarray(logT, dtype=np.float64)[:, None, :] - rho[None, None, :] * th[:, :, None]
+            P, R, D = np.sum(g), np.sum(g * d, axis=2), np.sum(g * d * d, axis=2)
+            m = np.asarray(m0)[:, None] + m1 * th if np.ndim(m0) else m0 + m1 * th
+            e = e - 0.5 * J * np.log(2 * np.pi) - 0.5 * np.sum(np.log(sg)) - 0.5 * np.log1p(v * P) - 0.5 * (D + (P * m * m - 2 * R * m - v * R * R) / (1 + v * P))
+        out[s] = logsumexp(e, axis=1)
+        outS[s] = np.sum(np.exp(e - np.max(e, axis=1, keepdims=True)), axis=1)
+    return (out, outS) if with_S else out
+
+
+def waicFromLogLik(L, unit=MARGINAL_UNIT, **extra) -> OutputWaic:
+    """WAIC from an (|S|, U) array of pointwise log-likelihoods with scipy's logsumexp and np.var(ddof=1), as getWaicHost forms it."""
+    from scipy.special import logsumexp
+    L = np.asarray(L, dtype=np.float64)
+    S, U = L.shape
+    if S < 2:
+        raise ValueError("WAIC needs at least two post-burn-in rows")
+    lppd_u = logsumexp(L, axis=0) - np.log(S)
+    p_u = np.var(L, axis=0, ddof=1)
+    el = lppd_u - p_u
+    elpd = float(np.sum(el))
+    se = 2.0 * float(np.sqrt(U * np.var(el, ddof=1))) if U > 1 else 0.0
+    return OutputWaic(elpd=elpd, pWaic=float(np.sum(p_u)), WAIC=-2.0 * elpd, se=se, nHighVar=int(np.sum(p_u > 0.4)), lppd=float(np.sum(lppd_u)), unit=unit, nUnits=U,
+                      nRows=S, lppd_u=lppd_u, p_u=p_u, **extra)
+
+
+def marginalRows(MCMC: _GibbsBase) -> np.ndarray:
+    """The rows behind getWaicMarginal: the post-burn-in rows of the item-level trace (one engine: rows >= nBurnin * nChain; a chain farm: those of chain 0, then
+    chain 1, ...)."""
+    src, C = _marginal_source(MCMC), MCMC.Cond
+    if getattr(MCMC, "farm", None) is not None:
+        return np.concatenate([src.engine(l).item_trace()[C.nBurnin:] for l in range(src.n_chains)], axis=0)
+    return src.item_trace()[C.nBurnin * C.nChain:]
+
+
+def getWaicMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) -> OutputWaic:
+    """getWaicMarginal evaluated with numpy / scipy on the host (the test twin of the device path) from MCMC.Data and the item-level trace rows (marginalRows, or
+    `rows`)."""
+    Q = _marginal_check(MCMC, nodes)
+    D, t = MCMC.Data, MCMC._traits
+    if D is None:
+        raise ValueError("Data is required")
+    rows = marginalRows(MCMC) if rows is None else rows
+    X = np.asarray(D.X, dtype=np.float64) if t.sees_x and MCMC.Cond.nFeat > 0 else None
+    L, S = marginalLogLikHost(MCMC._model, D.Y, D.logT if t.rt else None, X, rows, Q, with_S=True)
+    return waicFromLogLik(L, nNodes=Q, nCoarse=int(np.sum(np.any(S < 2.0, axis=0))))
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Posterior predictive checks (DESIGN.md 7g).  At every replicate row the data set is drawn again from the model at the values of that row; the deviance of the
 # responses, the chi^2 of the response times and the item scores of the replicate are compared with those of the data, per subject, per item and over the data set.
 # ------------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -357,6 +357,49 @@ function getWaicDevice(M::GibbsAMD; pointwise::Bool = false)
         lppd_u, p_u = reshape(lppd_u, M.Cond.nSubj, M.Cond.nItem), reshape(p_u, M.Cond.nSubj, M.Cond.nItem)
     end
     return merge(res, (lppd_u = lppd_u, p_u = p_u))
+end
+
+"""
+    getWaicMarginal(MCMC; nodes = 61, pointwise = false) -> (elpd, pWaic, WAIC, se, lppd, nUnits, nRows, nHighVar, nNodes, nCoarse[, lppd_u, p_u])
+
+The marginal WAIC: every subject's θ and ζ integrated out (ζ in closed form, θ by a fixed rule of `nodes` equally spaced nodes), computed on the device after
+`sample!` from the resident item-level trace and data set (`erm_get_marginal_waic`).  After `sample!(MCMC; devices=...)` the post-burn-in rows of all chains
+enter as one table (`erm_farm_get_marginal_waic`).  Not for the two quantile models.  `nCoarse` counts the subjects whose posterior was too narrow for the rule
+at some row: raise `nodes` until it is 0.
+"""
+function getWaicMarginal(M::GibbsAMD; nodes::Integer = 61, pointwise::Bool = false)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    out = zeros(10)
+    lppd_u, p_u = pointwise ? (zeros(M.Cond.nSubj), zeros(M.Cond.nSubj)) : (Float64[], Float64[])
+    pl, pp = pointwise ? (pointer(lppd_u), pointer(p_u)) : (Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL))
+    GC.@preserve lppd_u p_u begin
+        if farmed
+            check(ccall((:erm_farm_get_marginal_waic, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), M.farm, nodes, out, pl, pp))
+        else
+            check(ccall((:erm_get_marginal_waic, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), M.handle, nodes, out, pl, pp))
+        end
+    end
+    res = (elpd = out[1], pWaic = out[2], WAIC = out[3], se = out[4], lppd = out[5], nUnits = Int(out[6]), nRows = Int(out[7]), nHighVar = Int(out[8]),
+           nNodes = Int(out[9]), nCoarse = Int(out[10]))
+    return pointwise ? merge(res, (lppd_u = lppd_u, p_u = p_u)) : res
+end
+
+"""
+    marginalLogLik(model, Y, logT, X, rows; nodes = 61, device = 0) -> l
+
+The same kernel on caller-supplied data (`Y` UInt8 nSubj x nItem, `logT`, `X` nSubj x nFeat) and item-trace rows (`rows` is item_trace_width x nRows: one row of
+`erm_get_item_trace` per column): `l[i, s]`, the marginal log-likelihood of subject i at row s (`erm_marginal_loglik`).  Scores new respondents against a saved
+posterior.
+"""
+function marginalLogLik(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}; nodes::Integer = 61, device::Integer = 0)
+    N, J = size(Y)
+    R = size(rows, 2)
+    l = zeros(N, R)
+    check(ccall((:erm_marginal_loglik, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                device, model, N, J, size(X, 2), Y, logT, X, rows, R, nodes, l, C_NULL, C_NULL, C_NULL))
+    return l
 end
 
 """

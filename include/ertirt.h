@@ -205,7 +205,8 @@ int erm_get_dic(erm_handle h, double* out4);
  * a subject-sharded engine: ERM_ERR_STATE; no memory for the accumulators: ERM_ERR_NOMEM, the engine stays as it was.  From then on every sweep is followed by one
  * streaming pass over the resident data set (on the stream and inside the captured graphs; burn-in rows return at once), and small data sets are run one launch per
  * sweep at the persistent schedule's geometry, as under ERM_FLAG_NO_PERSIST (erm_timing.persistent = 0): the chain itself is bit for bit the chain without WAIC.
- * In profile mode the event bracket of a timed sweep also holds the pointwise pass.  erm_reset_trace clears the accumulators.  The chain farm has no WAIC yet.
+ * In profile mode the event bracket of a timed sweep also holds the pointwise pass.  erm_reset_trace clears the accumulators.  The chain farm keeps no such accumulators:
+ * its WAIC is the marginal one below, erm_farm_get_marginal_waic.
  * erm_get_waic: out = { elpd, p_waic, waic, se_waic, lppd, n_units, n_rows, number of units with p_u > 0.4 }, finished and summed on the device (needs two
  * post-burn-in rows).  erm_get_pointwise: lppd_u / p_u of every unit (either may be NULL): subjects in order, cells column-major [nSubj][nItem]. */
 enum { ERM_POINTWISE_OFF = 0, ERM_POINTWISE_SUBJECT = 1, ERM_POINTWISE_CELL = 2 };
@@ -213,6 +214,53 @@ int erm_set_pointwise(erm_handle h, int unit);
 int erm_get_waic(erm_handle h, double* out_eight);
 int64_t erm_pointwise_units(erm_handle h);
 int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u);
+
+/* Marginal WAIC: the unit is a subject with its own theta_i and zeta_i INTEGRATED OUT.  The conditional WAIC above answers "how well would new responses of the same
+ * persons be predicted"; its effective number of parameters grows with nSubj, and it holds fixed exactly the part in which GibbsRtIrt, Null, Cross and Latent differ (how
+ * theta and zeta hang together).  For choosing between latent-variable models the marginal criterion is the one to use (Merkle, Furr and Rabe-Hesketh 2019).  Once
+ * theta_i and zeta_i are gone, a subject's log-likelihood at trace row s depends on that row's item-level and structural parameters only -- the columns of the item-level
+ * trace, which is always kept, in fp64, in both trace modes -- so everything is computed AFTER the run from resident state: no pass behind the sweep, no erm_set_pointwise,
+ * no change to any schedule, and the calls only read the engine (the chain, the traces and the accumulators of erm_get_waic are unchanged by them).
+ * Served: GibbsMlIrt, GibbsRtIrt, GibbsRtIrtNull, GibbsRtIrtCross, GibbsRtIrtLatent.  The two quantile models are refused with ERM_ERR_ARG: with nu integrated out the
+ * response-time term is no longer Gaussian in zeta and the zeta integral has no closed form.
+ * Definition, for subject i at row s; items j = 1..J, y_j in {0,1}, t_j = logT_ij, x = the subject's covariates, S = Sigma_p with S12 read as (Sigma_p[1] + Sigma_p[2]) / 2.
+ *   Population law -- the structural term of the model's own getLogLikelihood*:  theta ~ N(mu, S11'),  zeta | theta ~ N(m0 + m1 theta, v)
+ *     MlIrt         mu = beta0 + x beta, S11' = 1; no zeta, no response times
+ *     RtIrt         mu = [1 x] beta[:,1], S11' = S11;  m1 = S12 / S11, m0 = [1 x] beta[:,2] - m1 mu, v = S22 - S12^2 / S11
+ *     Null, Cross   mu = 0, S11' = S11;  m1 = S12 / S11, m0 = 0, v = S22 - S12^2 / S11
+ *     Latent        mu = 0, S11' = S11;  m0 = beta0 + x beta_x, m1 = beta_theta, v = S22.  The theta law is the prior Latent's theta draw uses (drawSubjAbilityNull,
+ *                   src/Draw.pl.jl:67-80: mean 0, variance Sigma_p[1,1]); the reference's getLogLikelihoodRtIrtLatent carries no density for theta.
+ *   Response part   B(theta) = sum_j [ y_j eta_j - log(1 + e^eta_j) ],  eta_j = a_j (theta - b_j)
+ *   Response times, zeta integrated out analytically.  g_j = 1 / sig2t_j, d_j(theta) = lambda_j - t_j - rho_j theta (rho = 0 outside Cross),
+ *     P = sum g_j,  R(theta) = sum g_j d_j = R0 - theta R1,  D(theta) = sum g_j d_j^2 = D0 - 2 theta D1 + theta^2 D2,  m = m0 + m1 theta,
+ *     T(theta) = -(J/2) log 2 pi - 1/2 sum_j log sig2t_j - 1/2 log(1 + v P) - 1/2 [ D + (P m^2 - 2 R m - v R^2) / (1 + v P) ]      (MlIrt: T = 0)
+ *     = log N(t; lambda - rho theta - m, diag(sig2t) + v 1 1').  No 1 / v: a Sigma_p of correlation +-1 after cov2one (v = 0) is an ordinary case.
+ *   theta integral: a fixed rule of Q nodes, Q odd:  z_q = -6 + q h, h = 12 / (Q - 1), theta_q = mu + sqrt(S11') z_q,
+ *     e_q = log h - 1/2 log 2 pi - 1/2 z_q^2 + B(theta_q) + T(theta_q),   l_i^(s) = log sum_q exp(e_q) = M + log S with M = max_q e_q, S = sum_q exp(e_q - M).
+ *     The rule fails when the posterior of theta is narrower than the spacing (many items).  A subject is COARSE if S < 2 at some row: the largest node carries more
+ *     than half the mass (for a Gaussian posterior: sd < 0.8 h, where the rule's relative error passes about 3e-6).  Raise Q until no unit is coarse.
+ *   WAIC: S = the post-burn-in rows, those behind Post.mean (rows >= n_burnin * n_chain; |S| = erm_post_count), applied in trace order to the accumulators of
+ *     erm_get_waic; lppd_i, p_i, elpd, p_waic, waic and se_waic are formed exactly as erm_get_waic forms them.  All fp64, whatever the engine's precision (an fp32
+ *     engine's resident logT and X are widened).
+ * A subject's result depends on its own data, the rows and Q only -- not on nSubj, the other subjects, the launch or the device: eight lanes share a subject whatever the
+ * sizes, every sum has a fixed order, and nothing is atomic.  The results are bit-reproducible from call to call and do not depend on how the sweeps were split into
+ * erm_run calls.
+ * erm_get_marginal_waic: out10 = the eight values of erm_get_waic (n_units = n_subj), then Q, then the number of coarse units.  lppd_u, p_u [n_subj] may be NULL.
+ *   n_nodes = 0 means 61; otherwise odd and in 3 .. 1025 (ERM_ERR_ARG).  Works in both trace modes; reads the item trace in place from row n_burnin * n_chain.
+ *   Refused: a quantile model (ERM_ERR_ARG), a subject-sharded engine (ERM_ERR_STATE), fewer than two post-burn-in rows, no data set or an engine whose last erm_run
+ *   failed part-way (ERM_ERR_STATE), no scratch memory (ERM_ERR_NOMEM; four doubles and a flag per subject).
+ * erm_farm_get_marginal_waic: the same over the rows of the whole farm -- the post-burn-in rows of chain 0, then chain 1, ..., as one table on chain 0's device, whose
+ *   resident data set supplies the data (n_rows = erm_farm_post_count).  The chains' item-trace rows cross through the host (item-level: a few hundred kilobytes); no
+ *   device setting is touched.  Every chain must have recorded the same number of rows, at least two of them post-burn-in (ERM_ERR_STATE, the message names the chain).
+ *   A farm of one chain returns its engine's result bit for bit.
+ * erm_marginal_loglik: the same kernel on caller-supplied data (Y, logT, X column-major as erm_set_data takes them; X is ignored by the models that see no covariates)
+ *   and caller-supplied rows [n_rows][erm_item_trace_width], exactly as erm_get_item_trace returns them.  l [n_subj][n_rows], column-major (the subject fastest),
+ *   receives every l_i^(s); out10, lppd_u, p_u as above over all n_rows rows.  Any output may be NULL; n_rows >= 1 for l, >= 2 for the WAIC outputs (ERM_ERR_ARG).
+ *   A NaN anywhere: ERM_ERR_NONFINITE.  A row with sig2t <= 0, Sigma_p[1,1] <= 0 or v < 0: ERM_ERR_ARG, the message names the row.  Serves item traces that are no
+ *   longer resident and the scoring of new respondents against a saved posterior. */
+int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);
+int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                        int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u);
 
 /* Posterior predictive checks (Gelman, Meng and Stern 1996; Sinharay 2006; Glas and Meijer 2003; Marianti et al. 2014), drawn and accumulated on the device.  The
  * reference has no counterpart.  Post-burn-in row number k = 1, 2, ... (the rows behind Post.mean) is a REPLICATE row when (k - 1) mod thin = 0.  At a replicate
@@ -296,6 +344,7 @@ int erm_farm_reset_trace(erm_farm_handle f);
 int erm_farm_get_trace(erm_farm_handle f, int which, double* out);
 int erm_farm_get_mean(erm_farm_handle f, erm_state* out);
 int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Dbar over the rows of all chains, Dhat at the joint Post.mean (the same reduction as erm_farm_get_mean, evaluated on the first device) */
+int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* the marginal WAIC over the rows of all chains: see erm_get_marginal_waic */
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed);
 /* The farm's joint convergence diagnostics: the estimators of erm_get_diagnostics / erm_get_convergence / erm_get_rank_diagnostics / erm_get_rank_convergence, as
  * defined there, applied to the L = erm_farm_chains chains jointly -- chain l takes the place of interleaved chain l: M = 2 L sequences of
