@@ -269,7 +269,46 @@ def state_struct(arrays: dict):
     return st, keep
 
 
-class Engine:
+class _Diagnostics:
+    """The four convergence queries of an Engine (erm_get_*: its own interleaved chains) and of a Farm (erm_farm_get_*: its chains jointly, M = 2 * n_chains split
+    sequences, computed on chain 0's device).  One implementation, keyed by the symbol prefix `_diag_prefix`; `_diag_width(which)` is the trace's width."""
+    _diag_prefix = "erm_get_"
+
+    def _diag_width(self, which: int):
+        return int(self._lib.erm_trace_width(self._h, which))
+
+    def _diag_vectors(self, name: str, which: int, n: int):
+        w = max(self._diag_width(which), 0)
+        out = tuple(np.empty(w) for _ in range(n))
+        check(getattr(self._lib, self._diag_prefix + name)(self._h, which, *(v.ctypes.data for v in out)))
+        return out
+
+    def _diag_counts(self, name: str, which: int, n: int):
+        c = np.zeros(n, dtype=np.int64)
+        check(getattr(self._lib, self._diag_prefix + name)(self._h, which, c.ctypes.data))
+        return tuple(int(v) for v in c)
+
+    def diagnostics(self, which: int):
+        """(ess, rhat) of every column of Post.ra / rt / qr, computed on the device from the resident traces (erm_get_diagnostics / erm_farm_get_diagnostics)."""
+        return self._diag_vectors("diagnostics", which, 2)
+
+    def convergence(self, which: int):
+        """erm_get_convergence / erm_farm_get_convergence: (columns with a defined ESS, of those ESS > 400, columns with a defined R-hat, of those R-hat < 1.1),
+        counted on the device."""
+        return self._diag_counts("convergence", which, 4)
+
+    def rank_diagnostics(self, which: int):
+        """(ess_bulk, ess_tail, rhat_rank) of every column of Post.ra / rt / qr: the rank-normalised diagnostics (erm_get_rank_diagnostics /
+        erm_farm_get_rank_diagnostics), computed on the device from the resident traces."""
+        return self._diag_vectors("rank_diagnostics", which, 3)
+
+    def rank_convergence(self, which: int):
+        """erm_get_rank_convergence / erm_farm_get_rank_convergence: (bulk-ESS defined, bulk-ESS > 400, tail-ESS defined, tail-ESS > 400, rank R-hat defined,
+        rank R-hat < 1.1), counted on the device."""
+        return self._diag_counts("rank_convergence", which, 6)
+
+
+class Engine(_Diagnostics):
     """Thin RAII wrapper over an erm_handle."""
 
     def __init__(self, **kw):
@@ -463,33 +502,6 @@ class Engine:
         check(self._lib.erm_get_trace(self._h, which, out.ctypes.data))
         return out
 
-    def diagnostics(self, which: int):
-        """(ess, rhat) of every column of Post.ra / rt / qr, computed on the device from the resident traces."""
-        w = int(self._lib.erm_trace_width(self._h, which))
-        ess, rhat = np.empty(w), np.empty(w)
-        check(self._lib.erm_get_diagnostics(self._h, which, ess.ctypes.data, rhat.ctypes.data))
-        return ess, rhat
-
-    def convergence(self, which: int):
-        """erm_get_convergence: (columns with a defined ESS, of those ESS > 400, columns with a defined R-hat, of those R-hat < 1.1), counted on the device."""
-        c = np.zeros(4, dtype=np.int64)
-        check(self._lib.erm_get_convergence(self._h, which, c.ctypes.data))
-        return tuple(int(v) for v in c)
-
-    def rank_diagnostics(self, which: int):
-        """(ess_bulk, ess_tail, rhat_rank) of every column of Post.ra / rt / qr: the rank-normalised diagnostics (erm_get_rank_diagnostics), computed on the
-        device from the resident traces."""
-        w = int(self._lib.erm_trace_width(self._h, which))
-        bulk, tail, rhat = np.empty(w), np.empty(w), np.empty(w)
-        check(self._lib.erm_get_rank_diagnostics(self._h, which, bulk.ctypes.data, tail.ctypes.data, rhat.ctypes.data))
-        return bulk, tail, rhat
-
-    def rank_convergence(self, which: int):
-        """erm_get_rank_convergence: (bulk-ESS defined, bulk-ESS > 400, tail-ESS defined, tail-ESS > 400, rank R-hat defined, rank R-hat < 1.1), counted on the device."""
-        c = np.zeros(6, dtype=np.int64)
-        check(self._lib.erm_get_rank_convergence(self._h, which, c.ctypes.data))
-        return tuple(int(v) for v in c)
-
     def item_trace(self):
         w = int(self._lib.erm_item_trace_width(self._h))
         out = np.empty((self.rows_done, w), dtype=np.float64)
@@ -513,7 +525,7 @@ class _Borrowed(Engine):
         self._h = None
 
 
-class Farm:
+class Farm(_Diagnostics):
     """erm_farm_*: nChain independent chains, chain l on device devices[l] (include/ertirt.h).  The chains sample concurrently on host
     threads of the library; get_mean() is the one collective (RCCL all-reduce over the devices)."""
 
@@ -607,35 +619,11 @@ class Farm:
         """erm_farm_get_marginal_waic: Engine.marginal_waic over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
         return _marginal_call(self._lib.erm_farm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
 
-    # ---- joint convergence diagnostics over all chains (erm_farm_get_diagnostics and its siblings); engine(l).diagnostics(which) stays the diagnostic of chain l alone
-    def _width(self, which: int):
+    # ---- joint convergence diagnostics over all chains: _Diagnostics over erm_farm_get_*; engine(l).diagnostics(which) stays the diagnostic of chain l alone
+    _diag_prefix = "erm_farm_get_"
+
+    def _diag_width(self, which: int):
         return int(self._lib.erm_trace_width(self._lib.erm_farm_engine(self._h, 0), which))
-
-    def diagnostics(self, which: int):
-        """(ess, rhat) of every column of Post.ra / rt / qr over the farm's chains jointly (M = 2 * n_chains split sequences), computed on chain 0's device."""
-        w = max(self._width(which), 0)
-        ess, rhat = np.empty(w), np.empty(w)
-        check(self._lib.erm_farm_get_diagnostics(self._h, which, ess.ctypes.data, rhat.ctypes.data))
-        return ess, rhat
-
-    def convergence(self, which: int):
-        """erm_farm_get_convergence: the four counts of Engine.convergence, of the joint diagnostics."""
-        c = np.zeros(4, dtype=np.int64)
-        check(self._lib.erm_farm_get_convergence(self._h, which, c.ctypes.data))
-        return tuple(int(v) for v in c)
-
-    def rank_diagnostics(self, which: int):
-        """(ess_bulk, ess_tail, rhat_rank) of every column over the farm's chains jointly: the rank-normalised diagnostics (erm_farm_get_rank_diagnostics)."""
-        w = max(self._width(which), 0)
-        bulk, tail, rhat = np.empty(w), np.empty(w), np.empty(w)
-        check(self._lib.erm_farm_get_rank_diagnostics(self._h, which, bulk.ctypes.data, tail.ctypes.data, rhat.ctypes.data))
-        return bulk, tail, rhat
-
-    def rank_convergence(self, which: int):
-        """erm_farm_get_rank_convergence: the six counts of Engine.rank_convergence, of the joint diagnostics."""
-        c = np.zeros(6, dtype=np.int64)
-        check(self._lib.erm_farm_get_rank_convergence(self._h, which, c.ctypes.data))
-        return tuple(int(v) for v in c)
 
     def timing(self):
         """erm_farm_get_timing: wall-clock of the last run / gather, per-chain device time, ranks of the library's RCCL communicator."""

@@ -117,7 +117,7 @@ struct DevBuf {
 };
 
 // checkConvergence's four counts (diag_count_kernel, the reference's thresholds ESS > 400 and R-hat < 1.1) of n device-resident ess / rhat values: the one place
-// that launches the kernel, for erm_get_convergence and for erm_debug_convergence
+// that launches the kernel, for the diagnostics' counts (erm_diagnostics.hpp) and for erm_debug_convergence
 static int count_converged(const DevBuf& dE, const DevBuf& dR, int64_t n, hipStream_t stream, int64_t* c4)
 {
     DevBuf dC;
@@ -132,17 +132,7 @@ static int count_converged(const DevBuf& dE, const DevBuf& dR, int64_t n, hipStr
     return 0;
 }
 
-// Rank-normalised diagnostics (erm_rank_diag_kernels.hpp): the limits every entry checks, and the one place that launches the kernels -- for the engine's traces and
-// for erm_debug_rank_diagnostics alike.
-static int rank_diag_limits(int Tn, int n_chain)
-{
-    if (Tn / 2 < 4) return fail(ERM_ERR_ARG, "too few post-burn-in iterations for split-chain diagnostics (need >= 8)");
-    if (n_chain < 1 || 2 * n_chain > DIAG_MAXSEQ) return fail(ERM_ERR_ARG, "too many chains for the diagnostics kernel");
-    const int64_t S = 2 * (int64_t)n_chain * (Tn / 2);
-    if (S > RK_MAX_DRAWS) return fail(ERM_ERR_ARG, "rank diagnostics take at most " + std::to_string(RK_MAX_DRAWS) + " used draws per column (2 * n_chain * floor((n_iter - n_burnin) / 2) = " +
-                                                   std::to_string(S) + ")");
-    return 0;
-}
+// Rank-normalised diagnostics (erm_rank_diag_kernels.hpp), the one place that launches the kernels (its caller and its limits: erm_diagnostics.hpp):
 // columns [0, ncol) of the trace tr ([row = m nChain + l][ld]) -> bulk / tail / rhat[0 .. ncol), in chunks of columns whose staged draws fit the scratch budget
 // (256 MB whatever the trace width; ERM_RANK_DIAG_CHUNK: a chunk length in columns, for the tests of the chunk tails)
 template <typename T>
@@ -290,10 +280,6 @@ struct EngineBase {
     virtual int get_trace(int, double*) = 0;
     virtual int get_item_trace(double*) = 0;
     virtual int get_mean(erm_state*) = 0;
-    virtual int get_diagnostics(int, double*, double*) = 0;
-    virtual int get_convergence(int, int64_t*) = 0;
-    virtual int get_rank_diagnostics(int, double*, double*, double*) = 0;
-    virtual int get_rank_convergence(int, int64_t*) = 0;
     virtual int get_dic(double*) = 0;
     // WAIC (erm_set_pointwise / erm_get_waic / erm_pointwise_units / erm_get_pointwise)
     virtual int set_pointwise(int unit) = 0;
@@ -322,7 +308,7 @@ struct EngineBase {
     virtual int64_t summary_len() const = 0;
     virtual int summary_add(double* acc, const erm_state* want) = 0;
     virtual int mean_from_summary(const double* dacc, double inv, erm_state* out) = 0;
-    // The chain farm's joint diagnostics (erm_farm_get_diagnostics ...) read every chain's resident trace blocks in place: the device address of row 0 of the
+    // The convergence diagnostics (erm_diagnostics.hpp) read an engine's and every farm chain's resident trace blocks in place: the device address of row 0 of the
     // block's first column, the row stride in elements and the element size (the engine's trace type for a subject-level block, double for an item-level one);
     // p = NULL: the block is not resident (ERM_TRACE_SUMMARY, CrossQr's nu block beyond its budget, BLK_ZERO).  And the stream the chain's kernels run on.
     struct BlockSrc { const void* p; int64_t ld; size_t elem; };
@@ -1594,127 +1580,6 @@ template <typename real> struct Engine : EngineBase {
     }
     hipStream_t work_stream() const override { return stream; }
 
-    // ess / rhat of every column of trace `which` into device arrays of trace_width(which) doubles, block by block (diag_kernel); a block in device order
-    // (TraceBlock::device_order) is diagnosed in that order
-    int diag_device(int which, DevBuf& dE, DevBuf& dR) {
-        HIPCHK(hipSetDevice(cfg.device));
-        const int64_t wd = trace_width(which);
-        if (which == ERM_TRACE_LOGLIKE || wd <= 0) return fail(ERM_ERR_ARG, "diagnostics exist for the ra / rt / qr traces");
-        if (rows_done != rows_cap) return fail(ERM_ERR_STATE, "trace incomplete: run n_iter*n_chain sweeps first");
-        if (cfg.trace_mode != ERM_TRACE_FULL) return fail(ERM_ERR_NOTRACE, "subject-level traces need trace_mode = ERM_TRACE_FULL");
-        const int Tn = cfg.n_iter - cfg.n_burnin;
-        if (Tn / 2 < 4) return fail(ERM_ERR_ARG, "too few post-burn-in iterations for split-chain diagnostics (need >= 8)");
-        if (2 * cfg.n_chain > DIAG_MAXSEQ) return fail(ERM_ERR_ARG, "too many chains for the diagnostics kernel");
-        HIPCHK(hipStreamSynchronize(stream));
-        if (int rc = dE.alloc((size_t)wd * sizeof(double))) return rc;
-        if (int rc = dR.alloc((size_t)wd * sizeof(double))) return rc;
-        for (const TraceBlock& b : trace_blocks(which)) {
-            double* e = dE.as<double>() + b.col0; double* r = dR.as<double>() + b.col0;
-            const dim3 grid((unsigned)((b.ncol + 255) / 256));
-            switch (b.kind) {
-            case BLK_SUBJECT: case BLK_CELL: {
-                const DevBuf& tr = subj_trace(b.src);
-                if (!tr.p) return fail(ERM_ERR_NOTRACE, b.kind == BLK_CELL ? "the per-sweep nu trace was not recorded (erm_config.nu_trace_max_gb)" : "this trace was not recorded");
-                hipLaunchKernelGGL((diag_kernel<real>), grid, dim3(256), 0, stream, tr.as<real>(), (long long)b.ncol, (long long)b.ncol, cfg.n_iter, cfg.n_chain, cfg.n_burnin, e, r);
-                break;
-            }
-            case BLK_ITEM:
-                hipLaunchKernelGGL((diag_kernel<double>), grid, dim3(256), 0, stream, dTrItem.as<double>() + b.src, (long long)b.ncol, (long long)item_trace_width(), cfg.n_iter, cfg.n_chain,
-                                   cfg.n_burnin, e, r);
-                break;
-            case BLK_ZERO: {                    // constant columns: NaN
-                const std::vector<double> nanv((size_t)b.ncol, std::nan(""));
-                HIPCHK(hipMemcpyAsync(e, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipMemcpyAsync(r, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                break;
-            }
-            }
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
-    }
-    // ess / rhat of every column of Post.ra / rt / qr in the caller's order
-    int get_diagnostics(int which, double* ess, double* rhat) override {
-        DevBuf dE, dR;
-        if (int rc = diag_device(which, dE, dR)) return rc;
-        const int64_t wd = trace_width(which);
-        HIPCHK(hipMemcpy(ess, dE.p, (size_t)wd * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(rhat, dR.p, (size_t)wd * sizeof(double), hipMemcpyDeviceToHost));
-        for (const TraceBlock& b : trace_blocks(which)) if (b.device_order()) {      // row-major N x J -> Julia's vec (column-major)
-            for (double* v : {ess, rhat}) { const std::vector<double> h(v + b.col0, v + b.col0 + b.ncol); rows_to_cols(h.data(), v + b.col0, N, J); }
-        }
-        return 0;
-    }
-    // checkConvergence's summary (src/SimTools.jl:419-443) without the N-wide vectors: counts of the columns with a defined ESS / R-hat and of those with
-    // ESS > 400 / R-hat < 1.1 (the reference's thresholds), counted on the device
-    int get_convergence(int which, int64_t* c4) override {
-        DevBuf dE, dR;
-        if (int rc = diag_device(which, dE, dR)) return rc;
-        return count_converged(dE, dR, trace_width(which), stream, c4);
-    }
-
-    // bulk-ESS / tail-ESS / rank-normalised R-hat of every column of trace `which` into device arrays, block by block as diag_device does (rank_diag_run); the call
-    // reads the engine only
-    int rank_diag_device(int which, DevBuf& dB, DevBuf& dT, DevBuf& dR) {
-        HIPCHK(hipSetDevice(cfg.device));
-        const int64_t wd = trace_width(which);
-        if (which == ERM_TRACE_LOGLIKE || wd <= 0) return fail(ERM_ERR_ARG, "diagnostics exist for the ra / rt / qr traces");
-        if (rows_done != rows_cap) return fail(ERM_ERR_STATE, "trace incomplete: run n_iter*n_chain sweeps first");
-        if (cfg.trace_mode != ERM_TRACE_FULL) return fail(ERM_ERR_NOTRACE, "subject-level traces need trace_mode = ERM_TRACE_FULL");
-        const int Tn = cfg.n_iter - cfg.n_burnin;
-        if (int rc = rank_diag_limits(Tn, cfg.n_chain)) return rc;
-        for (const TraceBlock& b : trace_blocks(which)) if ((b.kind == BLK_SUBJECT || b.kind == BLK_CELL) && !subj_trace(b.src).p)
-            return fail(ERM_ERR_NOTRACE, b.kind == BLK_CELL ? "the per-sweep nu trace was not recorded (erm_config.nu_trace_max_gb)" : "this trace was not recorded");
-        HIPCHK(hipStreamSynchronize(stream));
-        for (DevBuf* d : {&dB, &dT, &dR}) if (int rc = d->try_alloc((size_t)wd * sizeof(double), "the rank diagnostics")) return rc;
-        for (const TraceBlock& b : trace_blocks(which)) {
-            double* o[3] = { dB.as<double>() + b.col0, dT.as<double>() + b.col0, dR.as<double>() + b.col0 };
-            switch (b.kind) {
-            case BLK_SUBJECT: case BLK_CELL:
-                if (int rc = rank_diag_run(static_cast<const real*>(subj_trace(b.src).p), b.ncol, b.ncol, cfg.n_chain, cfg.n_burnin, Tn, stream, o[0], o[1], o[2])) return rc;
-                break;
-            case BLK_ITEM:
-                if (int rc = rank_diag_run(dTrItem.as<double>() + b.src, item_trace_width(), b.ncol, cfg.n_chain, cfg.n_burnin, Tn, stream, o[0], o[1], o[2])) return rc;
-                break;
-            case BLK_ZERO: {                    // constant columns: NaN
-                const std::vector<double> nanv((size_t)b.ncol, std::nan(""));
-                for (double* d : o) HIPCHK(hipMemcpyAsync(d, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                break;
-            }
-            }
-        }
-        return 0;
-    }
-    int get_rank_diagnostics(int which, double* bulk, double* tail, double* rhat) override {
-        DevBuf dB, dT, dR;
-        if (int rc = rank_diag_device(which, dB, dT, dR)) return rc;
-        const int64_t wd = trace_width(which);
-        const DevBuf* src[3] = { &dB, &dT, &dR };
-        double* dst[3] = { bulk, tail, rhat };
-        for (int q = 0; q < 3; ++q) {
-            if (!dst[q]) continue;
-            HIPCHK(hipMemcpy(dst[q], src[q]->p, (size_t)wd * sizeof(double), hipMemcpyDeviceToHost));
-            for (const TraceBlock& b : trace_blocks(which)) if (b.device_order()) {      // row-major N x J -> Julia's vec (column-major)
-                const std::vector<double> h(dst[q] + b.col0, dst[q] + b.col0 + b.ncol);
-                rows_to_cols(h.data(), dst[q] + b.col0, N, J);
-            }
-        }
-        return 0;
-    }
-    // { bulk defined, bulk > 400, tail defined, tail > 400, rhat defined, rhat < 1.1 }: diag_count_kernel on (bulk, rhat) and on (tail, rhat)
-    int get_rank_convergence(int which, int64_t* c6) override {
-        DevBuf dB, dT, dR;
-        if (int rc = rank_diag_device(which, dB, dT, dR)) return rc;
-        int64_t a[4], b[4];
-        if (int rc = count_converged(dB, dR, trace_width(which), stream, a)) return rc;
-        if (int rc = count_converged(dT, dR, trace_width(which), stream, b)) return rc;
-        c6[0] = a[0]; c6[1] = a[1]; c6[2] = b[0]; c6[3] = b[1]; c6[4] = a[2]; c6[5] = a[3];
-        return 0;
-    }
-
     // item-level means (an item-trace row's layout) -> the fields of Post.mean (src/GibbsRtIrt.pl.jl:249-254, 327-343; Cross :304-318; Latent :316-330)
     void unpack_items(const double* m, erm_state* out) const {
         for (int k = 0; k < item_trace_fields(cfg.model); ++k) if (double* dst = out->*FIELDS[k].member) memcpy(dst, &m[FIELDS[k].off(J)], J * sizeof(double));
@@ -1934,175 +1799,8 @@ static int debug_upload(const double* x, int64_t n_draw, int64_t n_col, int32_t 
     H2D(dTr.p, tr.data(), tr.size() * sizeof(T));
     return 0;
 }
-template <typename T>
-static int debug_rank_diag(const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain, double* bulk, double* tail, double* rhat)
-{
-    DevBuf dTr, dO;
-    if (int rc = debug_upload<T>(x, n_draw, n_col, n_chain, dTr)) return rc;
-    if (int rc = dO.try_alloc((size_t)3 * n_col * sizeof(double), "the rank diagnostics")) return rc;
-    double* o = dO.as<double>();
-    if (int rc = rank_diag_run(dTr.as<T>(), n_col, n_col, (int)n_chain, 0, (int)n_draw, nullptr, o, o + n_col, o + 2 * n_col)) return rc;
-    double* dst[3] = { bulk, tail, rhat };
-    for (int q = 0; q < 3; ++q) if (dst[q]) HIPCHK(hipMemcpy(dst[q], o + q * n_col, (size_t)n_col * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-// erm_debug_diagnostics: the same for the basic estimator (diag_kernel at n_iter = n_draw, n_burnin = 0)
-template <typename T>
-static int debug_diag(const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain, double* ess, double* rhat)
-{
-    DevBuf dTr, dO;
-    if (int rc = debug_upload<T>(x, n_draw, n_col, n_chain, dTr)) return rc;
-    if (int rc = dO.try_alloc((size_t)2 * n_col * sizeof(double), "the diagnostics")) return rc;
-    double* o = dO.as<double>();
-    hipLaunchKernelGGL((diag_kernel<T>), dim3((unsigned)((n_col + 255) / 256)), dim3(256), 0, nullptr, dTr.as<T>(), (long long)n_col, (long long)n_col, (int)n_draw, (int)n_chain, 0, o, o + n_col);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(ess, o, (size_t)n_col * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rhat, o + n_col, (size_t)n_col * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The chain farm's JOINT convergence diagnostics (erm_farm_get_diagnostics / _convergence / _rank_diagnostics / _rank_convergence): chain l of the
-// farm takes the place of interleaved chain l of an engine.  The estimator kernels address one buffer as [row = m nChain + l][ld]; the farm's chains keep their
-// traces apart (and possibly on other devices), so farm_gather_kernel copies the post-burn-in rows of a chunk of columns of every chain into an interleaved scratch
-// on chain 0's device, and diag_kernel / rank_diag_run read it as a trace of L chains without burn-in -- the very kernels, so a farm result is the engine's
-// arithmetic by construction.  A chain on another device (or every chain but chain 0, under ERM_FARM_DIAG_REMOTE=1) is first compacted into a slab [Tn][nc] on its
-// own device (the same kernel with L = 1), the slab crosses with hipMemcpyPeerAsync, and is gathered from there.  Device memory: the scratch (at most
-// FARM_DIAG_BUDGET = 256 MB, erm_farm_diag.hpp), a 1 / L of it twice for the slab and its landing copy, and rank_diag_run's own 256 MB of staged draws.
-// ERM_FARM_DIAG_CHUNK caps the chunk length in columns (the tests of the chunk tails).
-// ---------------------------------------------------------------------------------------------------------------------
-static dim3 farm_gather_grid(int64_t nc, int Tn, size_t elem)
-{
-    const int64_t gx = std::min<int64_t>(std::max<int64_t>(1, (nc / (int64_t)(16 / elem) + 255) / 256), 2048);
-    return dim3((unsigned)gx, (unsigned)std::min<int64_t>(Tn, std::max<int64_t>(1, 16384 / gx)));
-}
-// one block of columns whose trace element is T: o[0 .. 1] = ess, rhat (basic) or o[0 .. 2] = bulk, tail, rhat (rank), device arrays of b.ncol doubles on chain 0's device
-template <typename T>
-static int farm_diag_block(erm_farm* f, const TraceBlock& b, bool rank, int Tn, double* const* o)
-{
-    const int L = (int)f->eng.size(), dev0 = f->dev[0], nB = f->cfg.n_burnin;
-    hipStream_t s0 = f->eng[0]->e->work_stream();
-    int64_t cap = 0;
-    if (const char* e = getenv("ERM_FARM_DIAG_CHUNK")) { const long long v = atoll(e); if (v > 0) cap = v; }
-    const char* fr = getenv("ERM_FARM_DIAG_REMOTE");
-    const bool force_remote = fr && atoi(fr) == 1;
-    const FarmDiagChunks plan = farm_diag_chunks(b.ncol, Tn, L, (int64_t)sizeof(T), FARM_DIAG_BUDGET, cap);
-    // chain l goes through the slab of its device udev[via[l]]; -1: it is gathered in place (it shares chain 0's device)
-    std::vector<int> via(L, -1);
-    for (int l = 1; l < L; ++l) if (f->dev[l] != dev0 || force_remote) { int d = 0; while (f->udev[d] != f->dev[l]) ++d; via[l] = d; }
-    DevBuf scratch, land;
-    std::vector<DevBuf> slab(f->udev.size());
-    const size_t slab_bytes = (size_t)farm_diag_bytes(plan.chunk, Tn, 1, (int64_t)sizeof(T));
-    HIPCHK(hipSetDevice(dev0));
-    if (int rc = scratch.try_alloc((size_t)farm_diag_bytes(plan.chunk, Tn, L, (int64_t)sizeof(T)), "the farm diagnostics' gathered draws")) return rc;
-    for (int l = 1; l < L; ++l) if (via[l] >= 0) {
-        if (!land.p) { HIPCHK(hipSetDevice(dev0)); if (int rc = land.try_alloc(slab_bytes, "the farm diagnostics' slab")) return rc; }
-        if (!slab[via[l]].p) { HIPCHK(hipSetDevice(f->dev[l])); if (int rc = slab[via[l]].try_alloc(slab_bytes, "the farm diagnostics' slab")) return rc; }
-    }
-    for (int64_t i = 0; i < plan.count(); ++i) {
-        const FarmDiagChunk ch = plan.at(i);
-        const dim3 grid = farm_gather_grid(ch.nc, Tn, sizeof(T));
-        for (int l = 0; l < L; ++l) {
-            EngineBase* e = f->eng[l]->e.get();
-            const EngineBase::BlockSrc src = e->block_src(b);
-            const T* p = static_cast<const T*>(src.p) + ch.c0;
-            if (via[l] < 0) {
-                HIPCHK(hipSetDevice(dev0));
-                hipLaunchKernelGGL((farm_gather_kernel<T>), grid, dim3(256), 0, s0, p, (long long)src.ld, (long long)ch.nc, Tn, nB, L, l, scratch.as<T>());
-                HIPCHK(hipGetLastError());
-                continue;
-            }
-            // the owner compacts the rows, its stream drains, the slab crosses, the copy completes, chain 0's device gathers it like a local chain
-            T* own = slab[via[l]].as<T>();
-            HIPCHK(hipSetDevice(f->dev[l]));
-            hipLaunchKernelGGL((farm_gather_kernel<T>), grid, dim3(256), 0, e->work_stream(), p, (long long)src.ld, (long long)ch.nc, Tn, nB, 1, 0, own);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(e->work_stream()));
-            HIPCHK(hipSetDevice(dev0));
-            HIPCHK(hipMemcpyPeerAsync(land.p, dev0, own, f->dev[l], (size_t)farm_diag_bytes(ch.nc, Tn, 1, (int64_t)sizeof(T)), s0));
-            HIPCHK(hipStreamSynchronize(s0));
-            hipLaunchKernelGGL((farm_gather_kernel<T>), grid, dim3(256), 0, s0, land.as<T>(), (long long)ch.nc, (long long)ch.nc, Tn, 0, L, l, scratch.as<T>());
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipSetDevice(dev0));
-        if (rank) {
-            if (int rc = rank_diag_run(scratch.as<T>(), ch.nc, ch.nc, L, 0, Tn, s0, o[0] + ch.c0, o[1] + ch.c0, o[2] + ch.c0)) return rc;
-        } else {
-            hipLaunchKernelGGL((diag_kernel<T>), dim3((unsigned)((ch.nc + 255) / 256)), dim3(256), 0, s0, scratch.as<T>(), (long long)ch.nc, (long long)ch.nc, Tn, L, 0, o[0] + ch.c0, o[1] + ch.c0);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    HIPCHK(hipStreamSynchronize(s0));      // (the scratch and the slabs are released on return)
-    return 0;
-}
-// every column of trace `which` over the L chains jointly, into nout device arrays of trace_width(which) doubles on chain 0's device (device order, as
-// Engine::diag_device leaves them).  Reads the farm only.
-static int farm_diag_device_on(erm_farm* f, int which, bool rank, DevBuf* out);
-static int farm_diag_device(erm_farm* f, int which, bool rank, DevBuf* out)
-{
-    // a step that fails on another chain's device returns from there: the caller's current device is chain 0's after the call either way (what the step left in
-    // flight on the owner's stream is drained when its buffers are released)
-    const int rc = farm_diag_device_on(f, which, rank, out);
-    if (rc) (void)hipSetDevice(f->dev[0]);
-    return rc;
-}
-static int farm_diag_device_on(erm_farm* f, int which, bool rank, DevBuf* out)
-{
-    const int L = (int)f->eng.size(), nout = rank ? 3 : 2;
-    EngineBase* e0 = f->eng[0]->e.get();
-    const int64_t wd = e0->trace_width(which);
-    if (which == ERM_TRACE_LOGLIKE || wd <= 0) return fail(ERM_ERR_ARG, "diagnostics exist for the ra / rt / qr traces");
-    for (int l = 0; l < L; ++l) if (f->eng[l]->e->rows_done != (int64_t)f->cfg.n_iter)
-        return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": trace incomplete: run n_iter sweeps of every chain first");
-    if (f->cfg.trace_mode != ERM_TRACE_FULL) return fail(ERM_ERR_NOTRACE, "subject-level traces need trace_mode = ERM_TRACE_FULL");
-    const int Tn = f->cfg.n_iter - f->cfg.n_burnin;
-    if (rank) { if (int rc = rank_diag_limits(Tn, L)) return rc; }
-    else {
-        if (Tn / 2 < 4) return fail(ERM_ERR_ARG, "too few post-burn-in iterations for split-chain diagnostics (need >= 8)");
-        if (2 * L > DIAG_MAXSEQ) return fail(ERM_ERR_ARG, "too many chains for the diagnostics kernel (at most " + std::to_string(DIAG_MAXSEQ / 2) + ")");
-    }
-    const TraceBlocks blocks = e0->trace_blocks(which);
-    for (const TraceBlock& b : blocks) if (b.kind != BLK_ZERO) for (int l = 0; l < L; ++l) if (!f->eng[l]->e->block_src(b).p)
-        return fail(ERM_ERR_NOTRACE, "chain " + std::to_string(l) + (b.kind == BLK_CELL ? ": the per-sweep nu trace was not recorded (erm_config.nu_trace_max_gb)" : ": this trace was not recorded"));
-    for (int l = 0; l < L; ++l) { HIPCHK(hipSetDevice(f->dev[l])); HIPCHK(hipStreamSynchronize(f->eng[l]->e->work_stream())); }
-    HIPCHK(hipSetDevice(f->dev[0]));
-    for (int q = 0; q < nout; ++q) if (int rc = out[q].try_alloc((size_t)wd * sizeof(double), "the farm diagnostics")) return rc;
-    hipStream_t s0 = e0->work_stream();
-    for (const TraceBlock& b : blocks) {
-        double* o[3] = { out[0].as<double>() + b.col0, out[1].as<double>() + b.col0, rank ? out[2].as<double>() + b.col0 : nullptr };
-        switch (b.kind) {
-        case BLK_SUBJECT: case BLK_CELL:
-            if (int rc = f->cfg.precision == ERM_PREC_F32 ? farm_diag_block<float>(f, b, rank, Tn, o) : farm_diag_block<double>(f, b, rank, Tn, o)) return rc;
-            break;
-        case BLK_ITEM:
-            if (int rc = farm_diag_block<double>(f, b, rank, Tn, o)) return rc;
-            break;
-        case BLK_ZERO: {                    // constant columns: NaN
-            const std::vector<double> nanv((size_t)b.ncol, std::nan(""));
-            HIPCHK(hipSetDevice(f->dev[0]));
-            for (int q = 0; q < nout; ++q) HIPCHK(hipMemcpyAsync(o[q], nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, s0));
-            HIPCHK(hipStreamSynchronize(s0));
-            break;
-        }
-        }
-    }
-    HIPCHK(hipSetDevice(f->dev[0]));
-    HIPCHK(hipStreamSynchronize(s0));
-    return 0;
-}
-// a device vector of the farm's diagnostics to the caller: a block in device order (CrossQr's nu) becomes Julia's vec, as erm_get_diagnostics returns it
-static int farm_diag_fetch(erm_farm* f, int which, const DevBuf& d, double* dst)
-{
-    EngineBase* e0 = f->eng[0]->e.get();
-    const int64_t wd = e0->trace_width(which);
-    HIPCHK(hipMemcpy(dst, d.p, (size_t)wd * sizeof(double), hipMemcpyDeviceToHost));
-    for (const TraceBlock& b : e0->trace_blocks(which)) if (b.device_order()) {
-        const std::vector<double> h(dst + b.col0, dst + b.col0 + b.ncol);
-        rows_to_cols(h.data(), dst + b.col0, f->cfg.n_subj, (int64_t)f->cfg.n_item);
-    }
-    return 0;
-}
+#include "erm_diagnostics.hpp"             // the convergence diagnostics' host path: the engine's, the farm's and the debug entries'
 
 extern "C" {
 
@@ -2136,10 +1834,11 @@ int64_t erm_post_count(erm_handle h) { return h ? h->e->post_rows : -1; }
 int erm_simulate_data(erm_handle h, const erm_state* truth, uint64_t seed, int noise) { CHK_H; return h->e->simulate_data(truth, seed, noise); }
 int erm_get_data(erm_handle h, uint8_t* Y, double* logT, double* X) { CHK_H; return h->e->get_data(Y, logT, X); }
 int erm_get_truth(erm_handle h, double* theta, double* zeta) { CHK_H; return h->e->get_truth(theta, zeta); }
-int erm_get_diagnostics(erm_handle h, int which, double* ess, double* rhat) { CHK_H; if (!ess || !rhat) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_diagnostics(which, ess, rhat); }
-int erm_get_convergence(erm_handle h, int which, int64_t* counts4) { CHK_H; if (!counts4) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_convergence(which, counts4); }
-int erm_get_rank_diagnostics(erm_handle h, int which, double* ess_bulk, double* ess_tail, double* rhat_rank) { CHK_H; return h->e->get_rank_diagnostics(which, ess_bulk, ess_tail, rhat_rank); }
-int erm_get_rank_convergence(erm_handle h, int which, int64_t* counts6) { CHK_H; if (!counts6) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_rank_convergence(which, counts6); }
+// the convergence diagnostics (diag_query, erm_diagnostics.hpp): the basic entries require both vectors, the rank entries skip a NULL one
+int erm_get_diagnostics(erm_handle h, int which, double* ess, double* rhat) { CHK_H; if (!ess || !rhat) return fail(ERM_ERR_ARG, "out is NULL"); double* v[3] = { ess, rhat, nullptr }; return diag_query(h, which, false, v, nullptr); }
+int erm_get_convergence(erm_handle h, int which, int64_t* counts4) { CHK_H; if (!counts4) return fail(ERM_ERR_ARG, "out is NULL"); return diag_query(h, which, false, nullptr, counts4); }
+int erm_get_rank_diagnostics(erm_handle h, int which, double* ess_bulk, double* ess_tail, double* rhat_rank) { CHK_H; double* v[3] = { ess_bulk, ess_tail, rhat_rank }; return diag_query(h, which, true, v, nullptr); }
+int erm_get_rank_convergence(erm_handle h, int which, int64_t* counts6) { CHK_H; if (!counts6) return fail(ERM_ERR_ARG, "out is NULL"); return diag_query(h, which, true, nullptr, counts6); }
 int erm_get_dic(erm_handle h, double* out4) { CHK_H; if (!out4) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_dic(out4); }
 int erm_set_pointwise(erm_handle h, int unit) { CHK_H; return h->e->set_pointwise(unit); }
 int erm_get_waic(erm_handle h, double* out_eight) { CHK_H; if (!out_eight) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_waic(out_eight); }
@@ -2398,47 +2097,11 @@ int erm_farm_set_seed(erm_farm_handle f, uint64_t seed)
     for (auto& e : f->eng) if (int rc = e->e->set_seed(seed)) return rc;
     return 0;
 }
-// the farm's joint diagnostics (farm_diag_device above): NULL outputs as the engine entries treat them
-int erm_farm_get_diagnostics(erm_farm_handle f, int which, double* ess, double* rhat)
-{
-    CHK_F;
-    if (!ess || !rhat) return fail(ERM_ERR_ARG, "out is NULL");
-    DevBuf d[2];
-    if (int rc = farm_diag_device(f, which, false, d)) return rc;
-    if (int rc = farm_diag_fetch(f, which, d[0], ess)) return rc;
-    return farm_diag_fetch(f, which, d[1], rhat);
-}
-int erm_farm_get_convergence(erm_farm_handle f, int which, int64_t* counts4)
-{
-    CHK_F;
-    if (!counts4) return fail(ERM_ERR_ARG, "out is NULL");
-    DevBuf d[2];
-    if (int rc = farm_diag_device(f, which, false, d)) return rc;
-    return count_converged(d[0], d[1], f->eng[0]->e->trace_width(which), f->eng[0]->e->work_stream(), counts4);
-}
-int erm_farm_get_rank_diagnostics(erm_farm_handle f, int which, double* ess_bulk, double* ess_tail, double* rhat_rank)
-{
-    CHK_F;
-    DevBuf d[3];
-    if (int rc = farm_diag_device(f, which, true, d)) return rc;
-    double* dst[3] = { ess_bulk, ess_tail, rhat_rank };
-    for (int q = 0; q < 3; ++q) if (dst[q]) if (int rc = farm_diag_fetch(f, which, d[q], dst[q])) return rc;
-    return 0;
-}
-int erm_farm_get_rank_convergence(erm_farm_handle f, int which, int64_t* counts6)
-{
-    CHK_F;
-    if (!counts6) return fail(ERM_ERR_ARG, "out is NULL");
-    DevBuf d[3];
-    if (int rc = farm_diag_device(f, which, true, d)) return rc;
-    const int64_t wd = f->eng[0]->e->trace_width(which);
-    hipStream_t s0 = f->eng[0]->e->work_stream();
-    int64_t a[4], b[4];
-    if (int rc = count_converged(d[0], d[2], wd, s0, a)) return rc;
-    if (int rc = count_converged(d[1], d[2], wd, s0, b)) return rc;
-    counts6[0] = a[0]; counts6[1] = a[1]; counts6[2] = b[0]; counts6[3] = b[1]; counts6[4] = a[2]; counts6[5] = a[3];
-    return 0;
-}
+// the farm's joint diagnostics, over its chains as over an engine's interleaved ones (diag_query): NULL outputs as the engine entries treat them
+int erm_farm_get_diagnostics(erm_farm_handle f, int which, double* ess, double* rhat) { CHK_F; if (!ess || !rhat) return fail(ERM_ERR_ARG, "out is NULL"); double* v[3] = { ess, rhat, nullptr }; return diag_query(f, which, false, v, nullptr); }
+int erm_farm_get_convergence(erm_farm_handle f, int which, int64_t* counts4) { CHK_F; if (!counts4) return fail(ERM_ERR_ARG, "out is NULL"); return diag_query(f, which, false, nullptr, counts4); }
+int erm_farm_get_rank_diagnostics(erm_farm_handle f, int which, double* ess_bulk, double* ess_tail, double* rhat_rank) { CHK_F; double* v[3] = { ess_bulk, ess_tail, rhat_rank }; return diag_query(f, which, true, v, nullptr); }
+int erm_farm_get_rank_convergence(erm_farm_handle f, int which, int64_t* counts6) { CHK_F; if (!counts6) return fail(ERM_ERR_ARG, "out is NULL"); return diag_query(f, which, true, nullptr, counts6); }
 
 const char* erm_last_error(void) { return g_err.c_str(); }
 const char* erm_version(void) { return "ertirt-amd 0.4.0 (gfx950)"; }
@@ -2531,26 +2194,15 @@ int erm_debug_convergence(int device, int64_t n, const double* ess, const double
 
 int erm_debug_rank_diagnostics(int device, int precision, const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain, double* ess_bulk, double* ess_tail, double* rhat_rank)
 {
-    if (!x || n_draw <= 0 || n_col <= 0 || n_draw > 0x7fffffff) return fail(ERM_ERR_ARG, "bad x / n_draw / n_col");
-    if (precision != ERM_PREC_F32 && precision != ERM_PREC_F64) return fail(ERM_ERR_ARG, "unknown precision");
-    if (int rc = rank_diag_limits((int)n_draw, n_chain)) return rc;
-    const int64_t len = n_draw * n_col * n_chain;
-    for (int64_t e = 0; e < len; ++e) if (x[e] != x[e]) return fail(ERM_ERR_NONFINITE, "x holds a NaN at entry " + std::to_string(e));
-    HIPCHK(hipSetDevice(device));
-    return precision == ERM_PREC_F32 ? debug_rank_diag<float>(x, n_draw, n_col, n_chain, ess_bulk, ess_tail, rhat_rank)
-                                     : debug_rank_diag<double>(x, n_draw, n_col, n_chain, ess_bulk, ess_tail, rhat_rank);
+    double* v[3] = { ess_bulk, ess_tail, rhat_rank };
+    return debug_query(device, precision, x, n_draw, n_col, n_chain, true, v);
 }
 
 int erm_debug_diagnostics(int device, int precision, const double* x, int64_t n_draw, int64_t n_col, int32_t n_chain, double* ess, double* rhat)
 {
-    if (!x || !ess || !rhat || n_draw <= 0 || n_col <= 0 || n_draw > 0x7fffffff) return fail(ERM_ERR_ARG, "bad x / n_draw / n_col / out");
-    if (precision != ERM_PREC_F32 && precision != ERM_PREC_F64) return fail(ERM_ERR_ARG, "unknown precision");
-    if (n_draw / 2 < 4) return fail(ERM_ERR_ARG, "too few post-burn-in iterations for split-chain diagnostics (need >= 8)");
-    if (n_chain < 1 || 2 * n_chain > DIAG_MAXSEQ) return fail(ERM_ERR_ARG, "too many chains for the diagnostics kernel");
-    const int64_t len = n_draw * n_col * n_chain;
-    for (int64_t e = 0; e < len; ++e) if (x[e] != x[e]) return fail(ERM_ERR_NONFINITE, "x holds a NaN at entry " + std::to_string(e));
-    HIPCHK(hipSetDevice(device));
-    return precision == ERM_PREC_F32 ? debug_diag<float>(x, n_draw, n_col, n_chain, ess, rhat) : debug_diag<double>(x, n_draw, n_col, n_chain, ess, rhat);
+    if (!ess || !rhat) return fail(ERM_ERR_ARG, "out is NULL");
+    double* v[3] = { ess, rhat, nullptr };
+    return debug_query(device, precision, x, n_draw, n_col, n_chain, false, v);
 }
 
 int erm_debug_sample(int device, int precision, int which, uint64_t seed, uint32_t site, uint32_t sweep, int64_t n,

@@ -872,32 +872,10 @@ def _diag_source(MCMC):
     return src
 
 
-def _check_convergence_rank(MCMC, detail):
-    eng = _diag_source(MCMC)
-    tot = np.zeros(6, dtype=np.int64)
-    out = {}
-    for name, which in (("ra", _lib.TRACE_RA), ("rt", _lib.TRACE_RT), ("qr", _lib.TRACE_QR)):
-        if which == _lib.TRACE_RT and not MCMC._traits.rt:
-            continue
-        try:
-            if detail:
-                bulk, tail, rhat = eng.rank_diagnostics(which)
-                with np.errstate(invalid="ignore"):
-                    c = (np.sum(~np.isnan(bulk)), np.sum(bulk > 400), np.sum(~np.isnan(tail)), np.sum(tail > 400), np.sum(~np.isnan(rhat)), np.sum(rhat < 1.1))
-                out[name] = (bulk, tail, rhat)
-            else:
-                c = eng.rank_convergence(which)
-        except _lib.ErmError:
-            if which != _lib.TRACE_QR:
-                raise
-            continue                                    # CrossQr without a resident nu trace
-        tot += np.asarray(c, dtype=np.int64)
-    bn, bok, tn, tok, rn, rok = (int(v) for v in tot)
-    res = dict(ess=100.0 * bok / max(bn, 1), essTail=100.0 * tok / max(tn, 1), rhat=100.0 * rok / max(rn, 1),
-               essN=f"{bok} / {bn}", essTailN=f"{tok} / {tn}", rhatN=f"{rok} / {rn}")
-    if detail:
-        res["detail"] = out
-    return res
+# checkConvergence's two kinds: the source's (vectors, counts) method pair and the result's keys -- one (share, "ok / n") pair per (defined, converged) pair
+# of counters, in the counters' order
+_CONVERGENCE_KINDS = {"basic": ("diagnostics", "convergence", (("ess", "essN"), ("rhat", "rhatN"))),
+                      "rank": ("rank_diagnostics", "rank_convergence", (("ess", "essN"), ("essTail", "essTailN"), ("rhat", "rhatN")))}
 
 
 def checkConvergence(MCMC: _GibbsBase, *, detail=True, kind="basic") -> dict:
@@ -911,28 +889,29 @@ def checkConvergence(MCMC: _GibbsBase, *, detail=True, kind="basic") -> dict:
     After sample!(...; devices=) the statistics are the chain farm's: every estimator over the nChain independent chains jointly (erm_farm_get_diagnostics and its
     siblings, computed on the first chain's device), which is where R-hat sees the variance between chains."""
     eng = _diag_source(MCMC)
-    if kind == "rank":
-        return _check_convergence_rank(MCMC, detail)
-    if kind != "basic":
+    if kind not in _CONVERGENCE_KINDS:
         raise ValueError('kind must be "basic" or "rank"')
-    ess_n = rhat_n = ess_ok = rhat_ok = 0
+    vectors, counts, keys = _CONVERGENCE_KINDS[kind]
+    tot = np.zeros(2 * len(keys), dtype=np.int64)
     out = {}
     for name, which in (("ra", _lib.TRACE_RA), ("rt", _lib.TRACE_RT), ("qr", _lib.TRACE_QR)):
         if which == _lib.TRACE_RT and not MCMC._traits.rt:
             continue
         try:
             if detail:
-                ess, rhat = eng.diagnostics(which)
-                c = (int(np.sum(~np.isnan(ess))), int(np.sum(ess > 400)), int(np.sum(~np.isnan(rhat))), int(np.sum(rhat < 1.1)))
-                out[name] = (ess, rhat)
+                out[name] = vec = getattr(eng, vectors)(which)
+                with np.errstate(invalid="ignore"):                 # every vector is an ESS (> 400) but the last, the R-hat (< 1.1)
+                    c = [n for v in vec[:-1] for n in (np.sum(~np.isnan(v)), np.sum(v > 400))] + [np.sum(~np.isnan(vec[-1])), np.sum(vec[-1] < 1.1)]
             else:
-                c = eng.convergence(which)
+                c = getattr(eng, counts)(which)
         except _lib.ErmError:
             if which != _lib.TRACE_QR:
                 raise
             continue                                    # CrossQr without a resident nu trace
-        ess_n += c[0]; ess_ok += c[1]; rhat_n += c[2]; rhat_ok += c[3]
-    res = dict(ess=100.0 * ess_ok / max(ess_n, 1), rhat=100.0 * rhat_ok / max(rhat_n, 1), essN=f"{ess_ok} / {ess_n}", rhatN=f"{rhat_ok} / {rhat_n}")
+        tot += np.asarray(c, dtype=np.int64)
+    pairs = [(int(tot[2 * k]), int(tot[2 * k + 1])) for k in range(len(keys))]
+    res = {share: 100.0 * ok / max(n, 1) for (share, _), (n, ok) in zip(keys, pairs)}
+    res.update({label: f"{ok} / {n}" for (_, label), (n, ok) in zip(keys, pairs)})
     if detail:
         res["detail"] = out
     return res
