@@ -1,7 +1,8 @@
 // tests/geometry_check.cpp -- CPU sweep of the launch-geometry planner (extendedrtirtmodeling.jl_amd/csrc/erm_geometry.hpp).
 // Built by tests/test_geometry_planner.py with g++ -fsanitize=undefined -fno-sanitize-recover -ftrapv: any division by zero, signed overflow or
 // out-of-range shift aborts the run.  For every accepted plan it asserts the invariants the kernels rely on; prints a summary and, with
-// `case <model> <f64> <N> <J> <Fk> <bt> <gb> <W> [cus] [nofuse] [nopersist]`, one plan as key=value pairs.
+// `case <model> <f64> <N> <J> <Fk> <bt> <gb> <W> [cus] [nofuse] [nopersist] [ngx]`, one plan as key=value pairs.
+// The sweep visits Fk in {0, 1, 3, 7, 14}, and for LatentQr every one of them with ngx = 0 and with sigp_mode 1's extra statistics (153 at Fk = 14).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,6 +87,7 @@ int main(int argc, char** argv)
         if (argc > 10) g.cu_count = atoi(argv[10]);
         if (argc > 11) g.no_fuse = atoi(argv[11]) != 0;
         if (argc > 12) g.no_persist = atoi(argv[12]) != 0;
+        if (argc > 13) g.ngx = atoi(argv[13]);
         Geom o; std::string err;
         if (plan_geometry(g, o, err) != 0) { printf("error=%s\n", err.c_str()); return 0; }
         check(g);

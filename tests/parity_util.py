@@ -279,8 +279,8 @@ if pytest is not None:
         return build_geometry_check(str(tmp_path_factory.mktemp("geom") / "geometry_check"))
 
 
-def plan(exe, model, f64, N, J, Fk, bt=0, gb=0, W=0, cus=256, nofuse=0, nopersist=0):
-    r = subprocess.run([exe, "case"] + [str(v) for v in (model, f64, N, J, Fk, bt, gb, W, cus, nofuse, nopersist)], capture_output=True, text=True, timeout=60)
+def plan(exe, model, f64, N, J, Fk, bt=0, gb=0, W=0, cus=256, nofuse=0, nopersist=0, ngx=0):
+    r = subprocess.run([exe, "case"] + [str(v) for v in (model, f64, N, J, Fk, bt, gb, W, cus, nofuse, nopersist, ngx)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     out = r.stdout.strip()
     if out.startswith("error="):
@@ -293,10 +293,21 @@ def kernel_feat(model, F):
     return 0 if model in CQ_MODELS or model == "null" else F
 
 
-def engine_plan(exe, model, precision, N, J, F, cu_count, *, lanes_per_row=0, block_threads=0, grid_blocks=0, flags=0):
-    """The CPU planner's plan for an engine's (model, precision, N, J, F, overrides, schedule flags) on a card with `cu_count` compute units, as integers."""
+def extra_stats(model, F, sigp_mode=0):
+    """GeomIn.ngx: GibbsRtIrtLatentQr with sigp_mode = 1 adds the 1/nu-weighted Gram statistics of [1 X theta | u], q = F + 2 columns: the packed upper
+    triangle, the cross terms with u and the weight sum."""
+    q = F + 2
+    return q * (q + 1) // 2 + q + 1 if model == "latentqr" and sigp_mode == 1 else 0
+
+
+def engine_plan(exe, model, precision, N, J, F, cu_count, *, lanes_per_row=0, block_threads=0, grid_blocks=0, flags=0, sigp_mode=0, refusal=False):
+    """The CPU planner's plan for an engine's (model, precision, N, J, F, overrides, schedule flags) on a card with `cu_count` compute units, as integers;
+    with `refusal`, a shape the planner turns down comes back as {"error": its message}."""
     p = plan(exe, MODELS[model], int(precision == "f64"), N, J, kernel_feat(model, F), bt=block_threads, gb=grid_blocks, W=lanes_per_row, cus=cu_count,
-             nofuse=int(bool(flags & 1)), nopersist=int(bool(flags & 8)))          # ERM_FLAG_NO_FUSE = 1, ERM_FLAG_NO_PERSIST = 8 (include/ertirt.h)
+             nofuse=int(bool(flags & 1)), nopersist=int(bool(flags & 8)),          # ERM_FLAG_NO_FUSE = 1, ERM_FLAG_NO_PERSIST = 8 (include/ertirt.h)
+             ngx=extra_stats(model, F, sigp_mode))
+    if refusal and "error" in p:
+        return p
     assert "error" not in p, p
     return {k: int(v) for k, v in p.items()}
 

@@ -12,10 +12,10 @@ CLS = {"mlirt": "GibbsMlIrt", "rtirt": "GibbsRtIrt", "crossqr": "GibbsRtIrtCross
        "latent": "GibbsRtIrtLatent"}
 
 
-def _sampler(pkg, model, N, J, *, precision, nIter=20, nChain=2, seed=11):
-    Y, logT, X, init, tp = pu.make_problem(model, N, J, 3, seed=seed)
-    Cond = pkg.setCond(nSubj=N, nItem=J, nFeat=3, nIter=nIter, nChain=nChain, qRt=0.85)
-    D = pkg.InputData(Y=Y, T=np.exp(logT) if logT is not None else (), X=X if X is not None else np.zeros((N, 3)))
+def _sampler(pkg, model, N, J, *, precision, nIter=20, nChain=2, seed=11, nFeat=3):
+    Y, logT, X, init, tp = pu.make_problem(model, N, J, nFeat, seed=seed)
+    Cond = pkg.setCond(nSubj=N, nItem=J, nFeat=nFeat, nIter=nIter, nChain=nChain, qRt=0.85)
+    D = pkg.InputData(Y=Y, T=np.exp(logT) if logT is not None else (), X=X if X is not None else np.zeros((N, nFeat)))
     return getattr(pkg, CLS[model])(Cond, Data=D, precision=precision), (Y, logT, X)
 
 
@@ -53,8 +53,13 @@ def _oracle_loglik_at_mean(model, M, data, P=None):
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 @pytest.mark.parametrize("model", list(CLS))
 def test_device_dic_equals_the_host_evaluation_and_the_oracle(model, precision):
+    check_device_dic(model, precision)
+
+
+def check_device_dic(model, precision, nFeat=3):
+    """The assertions of test_device_dic_equals_the_host_evaluation_and_the_oracle at 300 x 12 with nFeat covariates (tests/test_gpu_covariate_width.py runs them at 14)."""
     pkg = pu.ge.load_package()
-    M, data = _sampler(pkg, model, 300, 12, precision=precision)
+    M, data = _sampler(pkg, model, 300, 12, precision=precision, nFeat=nFeat)
     pkg.sample_b(M)
     d = M._engine.dic()
     host = pkg.getDicHost(M)

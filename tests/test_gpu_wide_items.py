@@ -90,10 +90,10 @@ def _regime(name, p, model, precision, N, J):
     raise KeyError(name)
 
 
-def planned(exe, cu_count, regime, model, precision, N, J, **overrides):
+def planned(exe, cu_count, regime, model, precision, N, J, F=F, **overrides):
     """The CPU planner's plan for the case, checked against the case's regime and printed."""
     p = pu.engine_plan(exe, model, precision, N, J, F, cu_count, **overrides)
-    print(f"\n[{model} {precision} {N} x {J} {overrides or ''}] regime {regime or '-'}; plan {p}")
+    print(f"\n[{model} {precision} {N} x {J}{'' if F == 3 else f' F = {F}'} {overrides or ''}] regime {regime or '-'}; plan {p}")
     if regime:
         bad = [what for what, ok in _regime(regime, p, model, precision, N, J) if not ok]
         assert not bad, f"{model} {precision} {N} x {J} is not in regime '{regime}': {bad}; plan {p}"
@@ -112,7 +112,7 @@ def cu_count():
 
 
 @functools.lru_cache(maxsize=2)
-def problem(model, N, J):
+def problem(model, N, J, F=F):
     return pu.make_problem(model, N, J, F)
 
 
