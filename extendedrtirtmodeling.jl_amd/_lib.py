@@ -67,6 +67,7 @@ EXPORTS = [
     "erm_get_rank_diagnostics", "erm_get_rank_convergence", "erm_debug_rank_diagnostics",
     "erm_farm_get_diagnostics", "erm_farm_get_convergence", "erm_farm_get_rank_diagnostics", "erm_farm_get_rank_convergence", "erm_debug_diagnostics",
     "erm_get_marginal_waic", "erm_farm_get_marginal_waic", "erm_marginal_loglik",
+    "erm_get_scores", "erm_farm_get_scores", "erm_score",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -207,6 +208,10 @@ def load():
     lib.erm_farm_get_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erm_marginal_loglik.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_get_scores.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_scores.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.erm_score.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                              C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -249,6 +254,35 @@ def _marginal_call(fn, h, nodes, n_subj, pointwise):
     lppd, p = (np.empty(n_subj), np.empty(n_subj)) if pointwise else (None, None)
     check(fn(h, marginal_nodes(nodes), out.ctypes.data, None if lppd is None else lppd.ctypes.data, None if p is None else p.ctypes.data))
     return _marginal_result(out, lppd, p)
+
+
+# erm_get_scores / erm_farm_get_scores / erm_score: the columns of score [n_subj][7] (ERM_SCORE_*) and the weightings of the rows
+SCORE_COLUMNS = ("theta", "thetaSd", "zeta", "zetaSd", "cov", "rowEss", "coarse")
+SCORE_EQUAL, SCORE_LIKELIHOOD = 0, 1
+SCORE_WEIGHTINGS = {"equal": SCORE_EQUAL, "likelihood": SCORE_LIKELIHOOD}
+
+
+def score_weighting(weighting):
+    """The weighting of the rows as the library takes it: "equal" | "likelihood" (or the ERM_SCORE_* code)."""
+    if weighting in SCORE_WEIGHTINGS:
+        return SCORE_WEIGHTINGS[weighting]
+    if weighting in (SCORE_EQUAL, SCORE_LIKELIHOOD) and not isinstance(weighting, bool):
+        return int(weighting)
+    raise ValueError('weighting must be "equal" or "likelihood"')
+
+
+def _score_result(score, out):
+    """score as the library fills it, (7, n_subj) C-ordered = column-major [n_subj][7], and out4 -> a dict of the columns with nSubj, nRows, nNodes, nCoarse."""
+    res = {name: score[k] for k, name in enumerate(SCORE_COLUMNS)}
+    res["coarse"] = score[6] != 0.0
+    res.update(nSubj=int(out[0]), nRows=int(out[1]), nNodes=int(out[2]), nCoarse=int(out[3]))
+    return res
+
+
+def _score_call(fn, h, nodes, n_subj):
+    score, out = np.empty((len(SCORE_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
+    check(fn(h, marginal_nodes(nodes), score.ctypes.data, out.ctypes.data))
+    return _score_result(score, out)
 
 
 STATE_FIELDS = ("theta", "a", "b", "zeta", "lambda_", "sig2t", "beta", "sigp", "rho", "nu")
@@ -469,6 +503,11 @@ class Engine(_Diagnostics):
         The totals (erm_get_waic's, with nNodes and nCoarse); with pointwise=True (totals, lppd_i, p_i)."""
         return _marginal_call(self._lib.erm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
 
+    def scores(self, nodes=MARGINAL_NODES):
+        """erm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on the device from the
+        resident item trace after the run (equal weights).  A dict of SCORE_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
+        return _score_call(self._lib.erm_get_scores, self._h, nodes, self.cfg.n_subj)
+
     # ---- posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     def set_predictive(self, on=True, thin=1):
         """Enable the replicate pass (every thin-th post-burn-in row is replicated) or turn it off; only while no trace row is recorded."""
@@ -619,6 +658,10 @@ class Farm(_Diagnostics):
         """erm_farm_get_marginal_waic: Engine.marginal_waic over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
         return _marginal_call(self._lib.erm_farm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
 
+    def scores(self, nodes=MARGINAL_NODES):
+        """erm_farm_get_scores: Engine.scores over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
+        return _score_call(self._lib.erm_farm_get_scores, self._h, nodes, self.cfg.n_subj)
+
     # ---- joint convergence diagnostics over all chains: _Diagnostics over erm_farm_get_*; engine(l).diagnostics(which) stays the diagnostic of chain l alone
     _diag_prefix = "erm_farm_get_"
 
@@ -679,6 +722,28 @@ def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=Tru
     if want_waic:
         res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
     return res
+
+
+def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", device=0):
+    """erm_score: the scores' kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as Engine.item_trace()
+    returns them, R >= 1; weighting "equal" | "likelihood".  Returns Engine.scores' dict."""
+    Yf = np.asfortranarray(np.asarray(Y).astype(np.uint8))
+    if Yf.ndim != 2:
+        raise ValueError("Y must be [subject, item]")
+    N, J = Yf.shape
+    lt = None if logT is None else np.asfortranarray(logT, dtype=np.float64)
+    xx = None if X is None or np.size(X) == 0 else np.asfortranarray(X, dtype=np.float64)
+    F = 0 if xx is None else xx.shape[1]
+    if (lt is not None and lt.shape != (N, J)) or (xx is not None and xx.shape[0] != N):
+        raise ValueError("logT / X do not match Y")
+    rr = np.ascontiguousarray(rows, dtype=np.float64)
+    if model in MODEL_TRAITS and (rr.ndim != 2 or rr.shape[1] != item_trace_width(model, J, F)):
+        raise ValueError(f"rows must be [row, {item_trace_width(model, J, F)}]")
+    sc, out = np.empty((len(SCORE_COLUMNS), N), dtype=np.float64), np.empty(4, dtype=np.float64)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    check(load().erm_score(int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, rr.shape[0], marginal_nodes(nodes), score_weighting(weighting),
+                           sc.ctypes.data, out.ctypes.data))
+    return _score_result(sc, out)
 
 
 def rccl_unique_id() -> bytes:

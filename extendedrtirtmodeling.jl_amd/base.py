@@ -120,6 +120,36 @@ class OutputWaic:
         return f"OutputWaic(unit={self.unit!r}, elpd={self.elpd}, pWaic={self.pWaic}, WAIC={self.WAIC}, se={self.se}, nHighVar={self.nHighVar})"
 
 
+class OutputScores:
+    """Scores of the respondents (getScores / scoreRespondents; the reference has no counterpart): per subject theta, thetaSd (the posterior mean of ability and its
+    standard error), zeta, zetaSd, cov (of theta and zeta; the three are NaN for GibbsMlIrt), rowEss (the rows' effective size: nRows under equal weights) and
+    coarse (the theta rule was too coarse for the subject at some row: raise nodes); nRows, nNodes, nCoarse.  relTheta / relZeta: the EAP reliability
+    Var_i(score_i) / (Var_i(score_i) + mean_i sd_i^2)."""
+
+    def __init__(self, theta=None, thetaSd=None, zeta=None, zetaSd=None, cov=None, rowEss=None, coarse=None, nRows=None, nNodes=None, nCoarse=None, weighting="equal"):
+        self.theta, self.thetaSd, self.zeta, self.zetaSd, self.cov, self.rowEss, self.coarse = theta, thetaSd, zeta, zetaSd, cov, rowEss, coarse
+        self.nRows, self.nNodes, self.nCoarse, self.weighting = nRows, nNodes, nCoarse, weighting
+
+    @staticmethod
+    def _rel(m, sd):
+        if m is None or np.any(np.isnan(m)):
+            return float("nan")
+        between = float(np.var(m))
+        return between / (between + float(np.mean(np.square(sd))))
+
+    @property
+    def relTheta(self):
+        return self._rel(self.theta, self.thetaSd)
+
+    @property
+    def relZeta(self):
+        return self._rel(self.zeta, self.zetaSd)
+
+    def __repr__(self):
+        return (f"OutputScores(nSubj={None if self.theta is None else np.size(self.theta)}, nRows={self.nRows}, nNodes={self.nNodes}, nCoarse={self.nCoarse}, "
+                f"relTheta={self.relTheta:.4f}, relZeta={self.relZeta:.4f})")
+
+
 class OutputPpc:
     """Posterior predictive checks of a fit (getPpc / getPpcHost; the reference has no counterpart).  R = the number of replicated data sets; item (3, 4, nItem),
     subj (2, 4, nSubj), total (2, 4): components RA (response deviance), RT (response-time chi^2; NaN for GibbsMlIrt)[, SCORE (item score)] x

@@ -16,6 +16,7 @@
 //                  Each node's e_q enters the lane's (M, S); a fixed butterfly of marg_ms_merge joins the eight lanes.
 //   4. accumulate  l = M + log S goes through pw_update into the subject's PwAcc, which lives in registers from the first row to the last and is stored once.
 // The covariates of the subject stay in registers across the rows.  Plain vector loads and stores, no atomics: every output word has one writer.
+// Steps 1 to 3 are __device__ helpers (marg_stage, marg_load_x, marg_stage_law, marg_item_sums, marg_lane_nodes) that score_kernel (erm_score_kernels.hpp) calls too.
 #pragma once
 #include "erm_marginal.hpp"
 #include "erm_pointwise.hpp"
@@ -36,13 +37,107 @@ struct MargArgs {
 // doubles of LDS per half of the row buffer: the row | g [J] | log sig2t [J]
 __host__ __device__ constexpr long long marg_row_lds(long long ld, int J) { return ld + 2 * (long long)J; }
 
+// ---- the parts of a row that marginal_kernel and score_kernel (erm_score_kernels.hpp) share: one copy of the staging, the law, the item sums and the node loop
+// the subject's covariates, widened
+template <int MODEL, typename real>
+__device__ __forceinline__ void marg_load_x(const MargArgs& A, long long i, double (&x)[MARG_MAXF])
+{
+    constexpr ModelTraits MT = model_traits(MODEL);
+#pragma unroll
+    for (int f = 0; f < MARG_MAXF; ++f) x[f] = (MT.sees_x && f < A.F) ? (double)reinterpret_cast<const real*>(A.X)[(size_t)i * A.F + f] : 0.0;
+}
+// staging: a row into one half of the LDS buffer, g_j and log sig2t_j beside it
+template <int MODEL>
+__device__ __forceinline__ void marg_stage(const MargArgs& A, long long row, double* dst, int tid)
+{
+    const double* src = A.rows + row * A.ld;
+    for (long long e = tid; e < A.ld; e += 256) dst[e] = src[e];
+    if constexpr (MODEL != MLIRT) for (int j = tid; j < A.J; j += 256) { const double v = src[3 * A.J + j]; dst[A.ld + j] = 1.0 / v; dst[A.ld + A.J + j] = log(v); }
+}
+// the population law at the staged row sa (v clamped at 0)
+template <int MODEL>
+__device__ __forceinline__ MargLaw marg_stage_law(const double* sa, int J, int F, const double (&x)[MARG_MAXF])
+{
+    constexpr ModelTraits MT = model_traits(MODEL);
+    const double* q = sa + 4 * J;
+    double xb0 = 0.0, xb1 = 0.0, bth = 0.0;
+    if constexpr (MT.beta == BETA_VEC || MT.beta == BETA_LATENT || MT.beta == BETA_PAIR) {
+        xb0 = q[0];
+#pragma unroll
+        for (int f = 0; f < MARG_MAXF; ++f) if (f < F) xb0 += x[f] * q[1 + f];
+    }
+    if constexpr (MT.beta == BETA_PAIR) {
+        xb1 = q[F + 1];
+#pragma unroll
+        for (int f = 0; f < MARG_MAXF; ++f) if (f < F) xb1 += x[f] * q[F + 2 + f];
+    }
+    if constexpr (MT.beta == BETA_LATENT) bth = q[F + 1];
+    const double S1[4] = {1.0, 0.0, 0.0, 1.0};
+    MargLaw w = marg_law(MODEL, xb0, xb1, bth, MODEL != MLIRT ? q + qr_sigp_off(MODEL, J, F) : S1);
+    w.v = fmax(w.v, 0.0);
+    return w;
+}
+// item sums: lane s, items s, s + 8, ... in order; then the butterfly
+template <int MODEL, typename real>
+__device__ __forceinline__ void marg_item_sums(const MargArgs& A, const double* sa, const uint8_t* Yi, const real* Ci, int s, MargSums& ms, double& A1, double& A0)
+{
+    constexpr bool RT = MODEL != MLIRT;
+    constexpr ModelTraits MT = model_traits(MODEL);
+    const int J = A.J;
+    const double* q = sa + 4 * J;
+    ms = MargSums{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    A1 = 0.0; A0 = 0.0;
+    for (int j = s; j < J; j += MARG_LANES) {
+        if (Yi[j] != 0) { const double a = sa[j]; A1 += a; A0 += a * sa[J + j]; }
+        if constexpr (RT) {
+            const double t = (double)Ci[j] + (A.cm ? A.cm[j] : 0.0);
+            marg_sums_add(ms, sa[A.ld + j], sa[A.ld + J + j], sa[2 * J + j] - t, MT.rho ? q[j] : 0.0);
+        }
+    }
+    for (int m = 1; m < MARG_LANES; m <<= 1) {
+        A1 += __shfl_xor(A1, m, 64); A0 += __shfl_xor(A0, m, 64);
+        if constexpr (RT) {
+            ms.P += __shfl_xor(ms.P, m, 64); ms.R0 += __shfl_xor(ms.R0, m, 64); ms.D0 += __shfl_xor(ms.D0, m, 64); ms.L += __shfl_xor(ms.L, m, 64);
+            if constexpr (MT.rho) { ms.R1 += __shfl_xor(ms.R1, m, 64); ms.D1 += __shfl_xor(ms.D1, m, 64); ms.D2 += __shfl_xor(ms.D2, m, 64); }
+        }
+    }
+}
+// nodes: lane s, nodes s, s + 8, ... in chunks of MARG_CHUNK; sink(e_q, z_q) receives the lane's nodes in order
+template <int MODEL, typename Sink>
+__device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, int s, double h, double log_h, const MargLaw& w, const MargSums& ms, double A1, double A0, Sink&& sink)
+{
+    for (int q0 = s; q0 < Q; q0 += MARG_LANES * MARG_CHUNK) {
+        double th[MARG_CHUNK], lse[MARG_CHUNK];
+#pragma unroll
+        for (int c = 0; c < MARG_CHUNK; ++c) {
+            const int qq = q0 + c * MARG_LANES;
+            th[c] = w.mu + w.sd * marg_node(qq < Q ? qq : Q - 1, h);      // (a slot past the last node repeats it and is dropped below)
+            lse[c] = 0.0;
+        }
+        for (int j = 0; j < J; ++j) {
+            const double a = sa[j], b = sa[J + j];
+#pragma unroll
+            for (int c = 0; c < MARG_CHUNK; ++c) lse[c] += marg_log1pexp(a * (th[c] - b));
+        }
+#pragma unroll
+        for (int c = 0; c < MARG_CHUNK; ++c) {
+            const int qq = q0 + c * MARG_LANES;
+            if (qq < Q) {
+                const double z = marg_node(qq, h);
+                double e = marg_log_weight(z, log_h) + (th[c] * A1 - A0 - lse[c]);
+                if constexpr (MODEL != MLIRT) e += marg_T(ms, J, w, th[c]);
+                sink(e, z);
+            }
+        }
+    }
+}
+
 template <int MODEL, typename real>
 __global__ void __launch_bounds__(256) marginal_kernel(const MargArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* sh = reinterpret_cast<double*>(smem);
     constexpr bool RT = MODEL != MLIRT;
-    constexpr ModelTraits MT = model_traits(MODEL);
     const int J = A.J, F = A.F, Q = A.Q, tid = (int)threadIdx.x;
     const long long half = marg_row_lds(A.ld, J);
     const int s = tid & (MARG_LANES - 1), r = tid >> MARG_LOG_LANES;
@@ -52,83 +147,22 @@ __global__ void __launch_bounds__(256) marginal_kernel(const MargArgs A)
     const uint8_t* Yi = A.Y + (size_t)i * J;
     const real* Ci = RT ? reinterpret_cast<const real*>(A.C) + (size_t)i * J : nullptr;
     double x[MARG_MAXF];
-#pragma unroll
-    for (int f = 0; f < MARG_MAXF; ++f) x[f] = (MT.sees_x && f < F) ? (double)reinterpret_cast<const real*>(A.X)[(size_t)i * F + f] : 0.0;
-
-    auto stage = [&](long long row, double* dst) {
-        const double* src = A.rows + row * A.ld;
-        for (long long e = tid; e < A.ld; e += 256) dst[e] = src[e];
-        if constexpr (RT) for (int j = tid; j < J; j += 256) { const double v = src[3 * J + j]; dst[A.ld + j] = 1.0 / v; dst[A.ld + J + j] = log(v); }
-    };
-    stage(0, sh);
+    marg_load_x<MODEL, real>(A, i, x);
+    marg_stage<MODEL>(A, 0, sh, tid);
     __syncthreads();
 
     const double h = marg_step(Q), log_h = log(h);
-    const int soff = qr_sigp_off(MODEL, J, F);
     PwAcc acc{0.0, 0.0, 0.0, 0.0};
     bool coarse = false;
     for (long long row = 0; row < A.n_rows; ++row) {
         const double* sa = sh + (row & 1) * half;
-        if (row + 1 < A.n_rows) stage(row + 1, sh + ((row + 1) & 1) * half);
-        const double* q = sa + 4 * J;
-        // ---- the population law at this row
-        double xb0 = 0.0, xb1 = 0.0, bth = 0.0;
-        if constexpr (MT.beta == BETA_VEC || MT.beta == BETA_LATENT || MT.beta == BETA_PAIR) {
-            xb0 = q[0];
-#pragma unroll
-            for (int f = 0; f < MARG_MAXF; ++f) if (f < F) xb0 += x[f] * q[1 + f];
-        }
-        if constexpr (MT.beta == BETA_PAIR) {
-            xb1 = q[F + 1];
-#pragma unroll
-            for (int f = 0; f < MARG_MAXF; ++f) if (f < F) xb1 += x[f] * q[F + 2 + f];
-        }
-        if constexpr (MT.beta == BETA_LATENT) bth = q[F + 1];
-        const double S1[4] = {1.0, 0.0, 0.0, 1.0};
-        MargLaw w = marg_law(MODEL, xb0, xb1, bth, RT ? q + soff : S1);
-        w.v = fmax(w.v, 0.0);
-        // ---- item sums: lane s, items s, s + 8, ... in order; then the butterfly
-        MargSums ms{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        double A1 = 0.0, A0 = 0.0;
-        for (int j = s; j < J; j += MARG_LANES) {
-            if (Yi[j] != 0) { const double a = sa[j]; A1 += a; A0 += a * sa[J + j]; }
-            if constexpr (RT) {
-                const double t = (double)Ci[j] + (A.cm ? A.cm[j] : 0.0);
-                marg_sums_add(ms, sa[A.ld + j], sa[A.ld + J + j], sa[2 * J + j] - t, MT.rho ? q[j] : 0.0);
-            }
-        }
-        for (int m = 1; m < MARG_LANES; m <<= 1) {
-            A1 += __shfl_xor(A1, m, 64); A0 += __shfl_xor(A0, m, 64);
-            if constexpr (RT) {
-                ms.P += __shfl_xor(ms.P, m, 64); ms.R0 += __shfl_xor(ms.R0, m, 64); ms.D0 += __shfl_xor(ms.D0, m, 64); ms.L += __shfl_xor(ms.L, m, 64);
-                if constexpr (MT.rho) { ms.R1 += __shfl_xor(ms.R1, m, 64); ms.D1 += __shfl_xor(ms.D1, m, 64); ms.D2 += __shfl_xor(ms.D2, m, 64); }
-            }
-        }
-        // ---- nodes: lane s, nodes s, s + 8, ... in chunks of MARG_CHUNK
+        if (row + 1 < A.n_rows) marg_stage<MODEL>(A, row + 1, sh + ((row + 1) & 1) * half, tid);
+        const MargLaw w = marg_stage_law<MODEL>(sa, J, F, x);
+        MargSums ms;
+        double A1, A0;
+        marg_item_sums<MODEL, real>(A, sa, Yi, Ci, s, ms, A1, A0);
         MargMS part{0.0, 0.0};
-        for (int q0 = s; q0 < Q; q0 += MARG_LANES * MARG_CHUNK) {
-            double th[MARG_CHUNK], lse[MARG_CHUNK];
-#pragma unroll
-            for (int c = 0; c < MARG_CHUNK; ++c) {
-                const int qq = q0 + c * MARG_LANES;
-                th[c] = w.mu + w.sd * marg_node(qq < Q ? qq : Q - 1, h);      // (a slot past the last node repeats it and is dropped below)
-                lse[c] = 0.0;
-            }
-            for (int j = 0; j < J; ++j) {
-                const double a = sa[j], b = sa[J + j];
-#pragma unroll
-                for (int c = 0; c < MARG_CHUNK; ++c) lse[c] += marg_log1pexp(a * (th[c] - b));
-            }
-#pragma unroll
-            for (int c = 0; c < MARG_CHUNK; ++c) {
-                const int qq = q0 + c * MARG_LANES;
-                if (qq < Q) {
-                    double e = marg_log_weight(marg_node(qq, h), log_h) + (th[c] * A1 - A0 - lse[c]);
-                    if constexpr (RT) e += marg_T(ms, J, w, th[c]);
-                    marg_ms_add(part, e);
-                }
-            }
-        }
+        marg_lane_nodes<MODEL>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double) { marg_ms_add(part, e); });
         for (int m = 1; m < MARG_LANES; m <<= 1) {
             const MargMS o{__shfl_xor(part.M, m, 64), __shfl_xor(part.S, m, 64)};
             part = marg_ms_merge(part, o);

@@ -21,6 +21,7 @@
 #include "erm_predictive_kernels.hpp"      // posterior predictive checks: the replicate pass behind every sweep
 #include "erm_rank_diag_kernels.hpp"       // rank-normalised convergence diagnostics: bulk / tail ESS, rank R-hat
 #include "erm_marginal_kernels.hpp"        // marginal WAIC: theta and zeta integrated out, from the item trace
+#include "erm_score_kernels.hpp"           // scores of respondents: posterior moments of theta and zeta, from the item trace
 #include "erm_farm_diag.hpp"               // the chain farm's joint diagnostics: chunk arithmetic
 #include "erm_geometry.hpp"
 #include "erm_model.hpp"
@@ -265,6 +266,54 @@ static int marginal_run(const MargData& D, const double* rows, int64_t n_rows, i
     return 0;
 }
 
+// Scores of respondents (erm_score_kernels.hpp; include/ertirt.h: erm_get_scores): the one place that launches score_kernel -- for an engine's resident data set
+// and item trace, for a farm's table of rows and for erm_score's caller-supplied data.  Everything it is given lives on the current device; score [N][7] and out4
+// are the caller's host arrays.
+template <typename real>
+static int score_run(const MargData& D, const double* rows, int64_t n_rows, int Q, int weighting, hipStream_t stream, double* score, double* out4)
+{
+    if (n_rows < 1) return fail(ERM_ERR_STATE, "the scores need at least one post-burn-in row");
+    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
+    const int64_t N = D.N, ld = item_trace_width(D.model, D.J, D.Fk);
+    DevBuf dScore, dCoarse, dCnt;
+    const char* what = "the scores";
+    if (int rc = dScore.try_alloc((size_t)N * SCORE_COLS * sizeof(double), what)) return rc;
+    if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
+    if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
+    MargArgs a{};
+    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = ld; a.N = N; a.J = D.J; a.F = D.Fk; a.Q = Q;
+    a.coarse = dCoarse.as<unsigned int>();
+    const size_t lds = (size_t)2 * marg_row_lds(ld, D.J) * sizeof(double);
+    const dim3 grid((unsigned)((N + MARG_TILE - 1) / MARG_TILE));
+    auto launch = [&](auto M, auto W) -> int {
+        constexpr int MODEL = decltype(M)::value;
+        constexpr bool WEIGHTED = decltype(W)::value;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&score_kernel<MODEL, real, WEIGHTED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((score_kernel<MODEL, real, WEIGHTED>), grid, dim3(256), lds, stream, a, dScore.as<double>());
+        return 0;
+    };
+    auto pick = [&](auto M) -> int { return weighting == SCORE_LIKELIHOOD ? launch(M, std::true_type{}) : launch(M, std::false_type{}); };
+    int rc = 0;
+    switch (D.model) {
+    case ERM_MODEL_MLIRT: rc = pick(std::integral_constant<int, MLIRT>{}); break;
+    case ERM_MODEL_RTIRT: rc = pick(std::integral_constant<int, RTIRT>{}); break;
+    case ERM_MODEL_NULL: rc = pick(std::integral_constant<int, NULLM>{}); break;
+    case ERM_MODEL_CROSS: rc = pick(std::integral_constant<int, CROSS>{}); break;
+    case ERM_MODEL_LATENT: rc = pick(std::integral_constant<int, LATENT>{}); break;
+    default: return marg_refuse_model(D.model);
+    }
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    unsigned long long nc = 0;
+    HIPCHK(hipMemcpy(&nc, dCnt.p, sizeof(nc), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(score, dScore.p, (size_t)N * SCORE_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    if (out4) { out4[0] = (double)N; out4[1] = (double)n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
+    return 0;
+}
+
 // A persistent launch needs all its workgroups resident at once.  Two persistent launches of ONE process on one device (a farm's chains sharing a
 // device, several engines) could each hold some compute units and wait for the other's for ever: they take turns.
 std::mutex g_persist_mu[64];
@@ -289,6 +338,8 @@ struct EngineBase {
     // marginal WAIC (erm_get_marginal_waic; the farm hands chain 0 a table of the rows of all chains on its device: rows != NULL), and the resident item trace
     virtual int marginal_waic(int Q, const double* rows, int64_t n_rows, double* out10, double* lppd_u, double* p_u) = 0;
     virtual const double* item_trace_dev() const = 0;
+    // scores of respondents (erm_get_scores; rows as for marginal_waic), equal weights
+    virtual int scores(int Q, const double* rows, int64_t n_rows, double* score, double* out4) = 0;
     // posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     virtual int set_predictive(int on, int32_t thin) = 0;
     virtual int64_t predictive_reps() const = 0;
@@ -870,6 +921,20 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipSetDevice(cfg.device));
         const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
         return marginal_run<real>(D, rows, n_rows, Q, stream, nullptr, out10, lppd_u, p_u);
+    }
+    // ---- scores: as the marginal WAIC, from the resident data set and item-trace rows; one post-burn-in row is enough
+    int scores(int Q, const double* rows, int64_t n_rows, double* score, double* out4) override {
+        if (int rc = marg_refuse_model(cfg.model)) return rc;
+        if (sharded()) return fail(ERM_ERR_STATE, "the scores are not available on a shard (every subject's data must be resident on one device)");
+        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
+        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
+        if (!rows) {
+            if (post_rows < 1) return fail(ERM_ERR_STATE, "the scores need at least one post-burn-in row");
+            rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows;
+        }
+        HIPCHK(hipSetDevice(cfg.device));
+        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
+        return score_run<real>(D, rows, n_rows, Q, SCORE_EQUAL, stream, score, out4);
     }
     int get_pointwise(double* lppd_u, double* p_u) override {
         if (int rc = pw_ready()) return rc;
@@ -1852,6 +1917,14 @@ int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* 
     if (int rc = marg_nodes(n_nodes, &Q)) return rc;
     return h->e->marginal_waic(Q, nullptr, 0, out10, lppd_u, p_u);
 }
+int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4)
+{
+    CHK_H;
+    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    return h->e->scores(Q, nullptr, 0, score, out4);
+}
 int erm_set_predictive(erm_handle h, int on, int32_t thin) { CHK_H; return h->e->set_predictive(on, thin); }
 int64_t erm_predictive_reps(erm_handle h) { return h ? h->e->predictive_reps() : -1; }
 int erm_get_predictive(erm_handle h, double* item, double* subj, double* total) { CHK_H; return h->e->get_predictive(item, subj, total); }
@@ -2063,20 +2136,16 @@ int erm_farm_get_dic(erm_farm_handle f, double* out4)
 }
 // The farm's marginal WAIC: the post-burn-in item-trace rows of chain 0, chain 1, ... as ONE table on chain 0's device, whose resident data set supplies the data.
 // A chain's rows cross through the host whatever its device (item-level: a few hundred kilobytes); a farm of one chain takes the same path as several.
-int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
+// (the table of both farm entries: min_post = the post-burn-in rows every chain must have, need = the refusal's words; the current device is chain 0's on return)
+static int farm_row_table(erm_farm_handle f, int64_t min_post, const char* need, DevBuf& dTab, int64_t* n_rows)
 {
-    CHK_F;
-    if (!out10) return fail(ERM_ERR_ARG, "out is NULL");
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
     const int L = (int)f->eng.size();
     EngineBase* e0 = f->eng[0]->e.get();
     const int64_t wi = e0->item_trace_width(), rows = e0->rows_done, post = e0->post_rows;
     for (int l = 0; l < L; ++l) {
         const EngineBase* e = f->eng[l]->e.get();
         if (e->rows_done != rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + std::to_string(e->rows_done) + " rows recorded where chain 0 has " + std::to_string(rows));
-        if (e->post_rows < 2) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": the marginal WAIC needs at least two post-burn-in rows");
+        if (e->post_rows < min_post) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + need);
     }
     std::vector<double> table((size_t)L * post * wi);
     for (int l = 0; l < L; ++l) {
@@ -2086,10 +2155,35 @@ int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10
         HIPCHK(hipMemcpy(table.data() + (size_t)l * post * wi, e->item_trace_dev() + (size_t)(rows - post) * wi, (size_t)post * wi * sizeof(double), hipMemcpyDeviceToHost));
     }
     HIPCHK(hipSetDevice(f->dev[0]));
-    DevBuf dTab;
     if (int rc = dTab.try_alloc(table.size() * sizeof(double), "the farm's table of item-trace rows")) return rc;
     H2D(dTab.p, table.data(), table.size() * sizeof(double));
-    return e0->marginal_waic(Q, dTab.as<double>(), (int64_t)L * post, out10, lppd_u, p_u);
+    *n_rows = (int64_t)L * post;
+    return 0;
+}
+int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
+{
+    CHK_F;
+    if (!out10) return fail(ERM_ERR_ARG, "out is NULL");
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
+    DevBuf dTab;
+    int64_t n_rows = 0;
+    if (int rc = farm_row_table(f, 2, "the marginal WAIC needs at least two post-burn-in rows", dTab, &n_rows)) return rc;
+    return f->eng[0]->e->marginal_waic(Q, dTab.as<double>(), n_rows, out10, lppd_u, p_u);
+}
+// The farm's scores: the same table, the same device, equal weights.
+int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4)
+{
+    CHK_F;
+    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
+    DevBuf dTab;
+    int64_t n_rows = 0;
+    if (int rc = farm_row_table(f, 1, "the scores need at least one post-burn-in row", dTab, &n_rows)) return rc;
+    return f->eng[0]->e->scores(Q, dTab.as<double>(), n_rows, score, out4);
 }
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed)
 {
@@ -2107,20 +2201,19 @@ const char* erm_last_error(void) { return g_err.c_str(); }
 const char* erm_version(void) { return "ertirt-amd 0.4.0 (gfx950)"; }
 int erm_abi_version(void) { return ERM_ABI_VERSION; }
 
-int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
-                        int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u)
+// Caller-supplied data and rows for marginal_run / score_run (erm_marginal_loglik, erm_score): validated on the host, then uploaded to `device` row-major in fp64,
+// as the kernels read an engine's.  min_rows / rows_msg: the fewest rows the caller's outputs need.
+struct MargUpload { DevBuf dY, dC, dX, dRows; MargData D; };
+static int marg_upload(const char* what, int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
+                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, MargUpload& U)
 {
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
     const ModelTraits mt = model_traits(model);
     if (n_subj <= 0 || n_subj >= (1LL << 32) || n_item <= 0 || n_item > 896 || n_feat < 0 || n_feat > MARG_MAXF) return fail(ERM_ERR_ARG, "n_subj, n_item (1 .. 896) or n_feat (0 .. " + std::to_string(MARG_MAXF) + ") out of range");
     const int64_t N = n_subj; const int J = n_item, Fk = kernel_feat(model, n_feat);
     if (!Y || !rows) return fail(ERM_ERR_ARG, "Y / rows is NULL");
     if (mt.rt && !logT) return fail(ERM_ERR_ARG, "logT is required for response-time models");
     if (Fk > 0 && !X) return fail(ERM_ERR_ARG, "X is required when n_feat > 0");
-    const bool totals = out10 || lppd_u || p_u;
-    if (n_rows < 1 || (totals && n_rows < 2)) return fail(ERM_ERR_ARG, "n_rows must be at least 1 (at least 2 for the WAIC outputs)");
+    if (n_rows < min_rows) return fail(ERM_ERR_ARG, rows_msg);
     const int64_t wi = item_trace_width(model, J, Fk);
     const size_t NJ = (size_t)N * J;
     // ---- the inputs: a NaN anywhere, then rows outside the model's domain
@@ -2137,33 +2230,58 @@ int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, i
     }
     HIPCHK(hipSetDevice(device));
     // ---- upload: the data set row-major in fp64, as the kernel reads an engine's
-    DevBuf dY, dC, dX, dRows, dL;
-    const char* what = "erm_marginal_loglik's inputs";
     {
         std::vector<uint8_t> y(NJ);
         cols_to_rows(Y, y.data(), N, (int64_t)J);
-        if (int rc = dY.try_alloc(NJ, what)) return rc;
-        H2D(dY.p, y.data(), NJ);
+        if (int rc = U.dY.try_alloc(NJ, what)) return rc;
+        H2D(U.dY.p, y.data(), NJ);
     }
     if (mt.rt) {
         std::vector<double> c(NJ);
         cols_to_rows(logT, c.data(), N, (int64_t)J);
-        if (int rc = dC.try_alloc(NJ * sizeof(double), what)) return rc;
-        H2D(dC.p, c.data(), NJ * sizeof(double));
+        if (int rc = U.dC.try_alloc(NJ * sizeof(double), what)) return rc;
+        H2D(U.dC.p, c.data(), NJ * sizeof(double));
     }
     if (Fk > 0) {
         std::vector<double> x((size_t)N * Fk);
         cols_to_rows(X, x.data(), N, (int64_t)Fk);
-        if (int rc = dX.try_alloc(x.size() * sizeof(double), what)) return rc;
-        H2D(dX.p, x.data(), x.size() * sizeof(double));
+        if (int rc = U.dX.try_alloc(x.size() * sizeof(double), what)) return rc;
+        H2D(U.dX.p, x.data(), x.size() * sizeof(double));
     }
-    if (int rc = dRows.try_alloc((size_t)n_rows * wi * sizeof(double), what)) return rc;
-    H2D(dRows.p, rows, (size_t)n_rows * wi * sizeof(double));
-    if (l) if (int rc = dL.try_alloc((size_t)N * n_rows * sizeof(double), "erm_marginal_loglik's output")) return rc;
-    const MargData D{dY.as<uint8_t>(), dC.p, dX.p, nullptr, N, J, Fk, model};
-    if (int rc = marginal_run<double>(D, dRows.as<double>(), n_rows, Q, nullptr, dL.as<double>(), out10, lppd_u, p_u)) return rc;
-    if (l) HIPCHK(hipMemcpy(l, dL.p, (size_t)N * n_rows * sizeof(double), hipMemcpyDeviceToHost));
+    if (int rc = U.dRows.try_alloc((size_t)n_rows * wi * sizeof(double), what)) return rc;
+    H2D(U.dRows.p, rows, (size_t)n_rows * wi * sizeof(double));
+    U.D = MargData{U.dY.as<uint8_t>(), U.dC.p, U.dX.p, nullptr, N, J, Fk, model};
     return 0;
+}
+
+int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                        int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u)
+{
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    const bool totals = out10 || lppd_u || p_u;
+    MargUpload U;
+    if (int rc = marg_upload("erm_marginal_loglik's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, totals ? 2 : 1,
+                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", U)) return rc;
+    DevBuf dL;
+    if (l) if (int rc = dL.try_alloc((size_t)n_subj * n_rows * sizeof(double), "erm_marginal_loglik's output")) return rc;
+    if (int rc = marginal_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, nullptr, dL.as<double>(), out10, lppd_u, p_u)) return rc;
+    if (l) HIPCHK(hipMemcpy(l, dL.p, (size_t)n_subj * n_rows * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int erm_score(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+              int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4)
+{
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
+    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
+    MargUpload U;
+    if (int rc = marg_upload("erm_score's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", U)) return rc;
+    return score_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, weighting, nullptr, score, out4);
 }
 
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out)

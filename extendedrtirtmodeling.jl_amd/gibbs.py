@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import InputPara, OutputDic, OutputPpc, OutputWaic, SimConditions
+from .base import InputPara, OutputDic, OutputPpc, OutputScores, OutputWaic, SimConditions
 
 _PREC = {"f32": _lib.PREC_F32, "f64": _lib.PREC_F64}
 _TRACE = {"summary": _lib.TRACE_SUMMARY, "full": _lib.TRACE_FULL}
@@ -556,19 +556,19 @@ def compareWaic(A, B) -> dict:
 MARGINAL_UNIT = "subject-marginal"
 
 
-def _marginal_source(MCMC):
+def _marginal_source(MCMC, who="getWaicMarginal"):
     src = getattr(MCMC, "farm", None) or MCMC._engine
     if src is None:
-        raise ValueError("run sample! first (getWaicMarginal reads the engine's resident item trace and data set)")
+        raise ValueError(f"run sample! first ({who} reads the engine's resident item trace and data set)")
     return src
 
 
-def _marginal_check(MCMC, nodes):
+def _marginal_check(MCMC, nodes, who="getWaicMarginal"):
     if MCMC._model not in _lib.MARGINAL_MODELS:
-        raise ValueError(f"getWaicMarginal is not available for {type(MCMC).__name__}: with the quantile weights integrated out the response-time term is not Gaussian in "
+        raise ValueError(f"{who} is not available for {type(MCMC).__name__}: with the quantile weights integrated out the response-time term is not Gaussian in "
                          "zeta and the zeta integral has no closed form")
     if MCMC.shard is not None:
-        raise ValueError("getWaicMarginal is not available for a subject-sharded sampler (every subject's data must be resident on one device)")
+        raise ValueError(f"{who} is not available for a subject-sharded sampler (every subject's data must be resident on one device)")
     return _lib.marginal_nodes(nodes)
 
 
@@ -584,13 +584,10 @@ def getWaicMarginal(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, pointwise=False
                       nRows=w["nRows"], lppd_u=lppd_u, p_u=p_u, nNodes=w["nNodes"], nCoarse=w["nCoarse"])
 
 
-def marginalLogLikHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, with_S=False) -> np.ndarray:
-    """l_i^(s) of the marginal WAIC with numpy (the test twin of marginal_kernel): an (R, N) array for the item-trace rows [R, item_trace_width] (as
-    Engine.item_trace() returns them) and the data Y, logT [N, J], X [N, F] or None.  with_S=True also returns S = sum_q exp(e_q - max_q e_q) per (row, subject):
-    S < 2 marks a posterior too narrow for the rule."""
-    from scipy.special import logsumexp
+def _marginal_rows_host(model, Y, logT, X, rows, Q):
+    """The rule at every row for marginalLogLikHost and scoresHost: yields (e (N, Q), z (Q,), law, sums) with law = (mu (N,), sd, m0, m1, v) and
+    sums = (P, R0 (N,), R1) of include/ertirt.h's definition (None for GibbsMlIrt)."""
     t = _lib.MODEL_TRAITS[model]
-    Q = _lib.marginal_nodes(nodes)
     Y = np.asarray(Y, dtype=np.float64)
     N, J = Y.shape
     F = 0 if X is None or not t.sees_x else np.shape(X)[1]
@@ -600,11 +597,11 @@ def marginalLogLikHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, with_
         raise ValueError(f"rows must have {_lib.item_trace_width(model, J, F)} columns")
     h = 12.0 / (Q - 1)
     z = -6.0 + h * np.arange(Q)
-    out, outS = np.empty((rows.shape[0], N)), np.empty((rows.shape[0], N))
     zero = np.zeros(N)
-    for s, row in enumerate(rows):
+    for row in rows:
         a, b, lam, sg, q = row[:J], row[J:2 * J], row[2 * J:3 * J], row[3 * J:4 * J], row[4 * J:]
         rho = q[:J] if t.rho else np.zeros(J)
+        m0, m1, v = zero, 0.0, 0.0
         if model == _lib.MODEL_MLIRT:
             mu, s11 = x1 @ q[:F + 1], 1.0
         else:
@@ -621,14 +618,26 @@ def marginalLogLikHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, with_
         th = mu[:, None] + np.sqrt(s11) * z[None, :]                                  # (N, Q)
         eta = a[None, None, :] * (th[:, :, None] - b[None, None, :])                  # (N, Q, J)
         e = np.log(h) - 0.5 * np.log(2 * np.pi) - 0.5 * z[None, :] ** 2 + np.sum(Y[:, None, :] * eta - _log1pexp(eta), axis=2)
+        sums = None
         if t.rt:
             g = 1.0 / sg
-            d = lam[None, None, :] - np.asarray(logT, dtype=np.float64)[:, None, :] - rho[None, None, :] * th[:, :, None]
+            lt = np.asarray(logT, dtype=np.float64)
+            d = lam[None, None, :] - lt[:, None, :] - rho[None, None, :] * th[:, :, None]
             P, R, D = np.sum(g), np.sum(g * d, axis=2), np.sum(g * d * d, axis=2)
             m = np.asarray(m0)[:, None] + m1 * th if np.ndim(m0) else m0 + m1 * th
             e = e - 0.5 * J * np.log(2 * np.pi) - 0.5 * np.sum(np.log(sg)) - 0.5 * np.log1p(v * P) - 0.5 * (D + (P * m * m - 2 * R * m - v * R * R) / (1 + v * P))
-        out[s] = logsumexp(e, axis=1)
-        outS[s] = np.sum(np.exp(e - np.max(e, axis=1, keepdims=True)), axis=1)
+            sums = (P, np.sum(g[None, :] * (lam[None, :] - lt), axis=1), np.sum(g * rho))
+        yield e, z, (mu, np.sqrt(s11), m0, m1, v), sums
+
+
+def marginalLogLikHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, with_S=False) -> np.ndarray:
+    """l_i^(s) of the marginal WAIC with numpy (the test twin of marginal_kernel): an (R, N) array for the item-trace rows [R, item_trace_width] (as
+    Engine.item_trace() returns them) and the data Y, logT [N, J], X [N, F] or None.  with_S=True also returns S = sum_q exp(e_q - max_q e_q) per (row, subject):
+    S < 2 marks a posterior too narrow for the rule."""
+    from scipy.special import logsumexp
+    Q = _lib.marginal_nodes(nodes)
+    per = [(logsumexp(e, axis=1), np.sum(np.exp(e - np.max(e, axis=1, keepdims=True)), axis=1)) for e, _, _, _ in _marginal_rows_host(model, Y, logT, X, rows, Q)]
+    out, outS = np.array([p[0] for p in per]), np.array([p[1] for p in per])
     return (out, outS) if with_S else out
 
 
@@ -668,6 +677,68 @@ def getWaicMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) 
     X = np.asarray(D.X, dtype=np.float64) if t.sees_x and MCMC.Cond.nFeat > 0 else None
     L, S = marginalLogLikHost(MCMC._model, D.Y, D.logT if t.rt else None, X, rows, Q, with_S=True)
     return waicFromLogLik(L, nNodes=Q, nCoarse=int(np.sum(np.any(S < 2.0, axis=0))))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Scores of respondents (include/ertirt.h: erm_get_scores).  Posterior mean and sd of every subject's theta and zeta from the item-level trace: the
+# posterior of theta on the marginal WAIC's rule at every row, zeta given theta Gaussian in closed form, the rows joined by the law of total variance.
+# ------------------------------------------------------------------------------------------------------------------
+def _scores_output(r, weighting="equal") -> OutputScores:
+    return OutputScores(theta=r["theta"], thetaSd=r["thetaSd"], zeta=r["zeta"], zetaSd=r["zetaSd"], cov=r["cov"], rowEss=r["rowEss"], coarse=r["coarse"],
+                        nRows=r["nRows"], nNodes=r["nNodes"], nCoarse=r["nCoarse"], weighting=weighting)
+
+
+def getScores(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES) -> OutputScores:
+    """Scores of the subjects of the last sample! -- of one engine or of the chain farm of sample!(...; devices=) -- computed on the device from the resident item
+    trace and data set (erm_get_scores / erm_farm_get_scores), in either trace mode: theta, thetaSd, zeta, zetaSd, cov, rowEss, coarse per subject; relTheta,
+    relZeta.  The scores are posterior under the population law of getWaicMarginal: for the response-time models theta borrows strength from the response times, so
+    they differ from Post.mean by design (the sampler's theta and zeta draws each use the marginal prior); for GibbsMlIrt the two agree."""
+    Q = _marginal_check(MCMC, nodes, "getScores")
+    return _scores_output(_marginal_source(MCMC, "getScores").scores(Q))
+
+
+def scoreRespondents(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal", device=0) -> OutputScores:
+    """Scores of respondents -- new ones, or those of a run that is no longer resident -- against saved item-trace rows [R, item_trace_width] (Engine.item_trace()),
+    on the device (erm_score).  model: the model code (_lib.MODEL_*); Y, logT [N, J], X [N, F] or None.  weighting "equal": every row counts once, the usual
+    operational scoring; "likelihood": row s counts exp(l_s), the posterior of a new respondent given their own data and the saved item posterior."""
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("scoreRespondents serves the five models without quantile weights")
+    w = _lib.score_weighting(weighting)
+    return _scores_output(_lib.score(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), weighting=w, device=device), "likelihood" if w else "equal")
+
+
+def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal") -> OutputScores:
+    """scoreRespondents with numpy (the test twin of score_kernel), written beside marginalLogLikHost: the rule's weights at every row, the moments of theta, the
+    zeta conditional, and the rows joined in two passes (the means, then the deviations from them)."""
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("scoresHost serves the five models without quantile weights")
+    Q, wt = _lib.marginal_nodes(nodes), _lib.score_weighting(weighting)
+    rt = _lib.MODEL_TRAITS[model].rt
+    E, V, Ez, Vz, Cz, l, S = ([] for _ in range(7))
+    for e, z, (mu, sd, m0, m1, v), sums in _marginal_rows_host(model, Y, logT, X, rows, Q):
+        M = np.max(e, axis=1, keepdims=True)
+        p = np.exp(e - M)
+        s = np.sum(p, axis=1)
+        w = p / s[:, None]
+        Z1, Z2 = w @ z, w @ (z * z)
+        Es, Vs = mu + sd * Z1, np.maximum(sd * sd * (Z2 - Z1 * Z1), 0.0)
+        c0, c1, u = 0.0, 0.0, 0.0
+        if rt:
+            P, R0, R1 = sums
+            c0, c1, u = (m0 + v * R0) / (1 + v * P), (m1 - v * R1) / (1 + v * P), v / (1 + v * P)
+        for lst, val in zip((E, V, Ez, Vz, Cz, l, S), (Es, Vs, c0 + c1 * Es, u + c1 * c1 * Vs, c1 * Vs, M[:, 0] + np.log(s), s)):
+            lst.append(val)
+    E, V, Ez, Vz, Cz, l, S = (np.array(a) for a in (E, V, Ez, Vz, Cz, l, S))             # (R, N)
+    om = np.exp(l - np.max(l, axis=0, keepdims=True)) if wt == _lib.SCORE_LIKELIHOOD else np.ones_like(l)
+    W = np.sum(om, axis=0)
+    mean = lambda a: np.sum(om * a, axis=0) / W
+    th, ze = mean(E), mean(Ez)
+    nan = np.full(E.shape[1], np.nan)
+    coarse = np.any(S < 2.0, axis=0)
+    return OutputScores(theta=th, thetaSd=np.sqrt(np.maximum(mean(V) + mean((E - th) ** 2), 0.0)), zeta=ze if rt else nan,
+                        zetaSd=np.sqrt(np.maximum(mean(Vz) + mean((Ez - ze) ** 2), 0.0)) if rt else nan, cov=mean(Cz) + mean((E - th) * (Ez - ze)) if rt else nan,
+                        rowEss=W * W / np.sum(om * om, axis=0), coarse=coarse, nRows=E.shape[0], nNodes=Q, nCoarse=int(np.sum(coarse)),
+                        weighting="likelihood" if wt else "equal")
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getScores, scoreRespondents, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -400,6 +400,53 @@ function marginalLogLik(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64},
                 (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                 device, model, N, J, size(X, 2), Y, logT, X, rows, R, nodes, l, C_NULL, C_NULL, C_NULL))
     return l
+end
+
+# score as erm_get_scores fills it (column-major [nSubj][7], the ERM_SCORE_* columns) and out4 -> a named tuple with the EAP reliabilities
+function scoresTuple(score::Matrix{Float64}, out::Vector{Float64})
+    mean(v) = sum(v) / length(v)
+    rel(m, sd) = any(isnan, m) ? NaN : (b = mean((m .- mean(m)) .^ 2); b / (b + mean(sd .^ 2)))
+    return (theta = score[:, 1], thetaSd = score[:, 2], zeta = score[:, 3], zetaSd = score[:, 4], cov = score[:, 5], rowEss = score[:, 6], coarse = score[:, 7] .!= 0.0,
+            nRows = Int(out[2]), nNodes = Int(out[3]), nCoarse = Int(out[4]), relTheta = rel(score[:, 1], score[:, 2]), relZeta = rel(score[:, 3], score[:, 4]))
+end
+
+"""
+    getScores(MCMC; nodes = 61) -> (theta, thetaSd, zeta, zetaSd, cov, rowEss, coarse, nRows, nNodes, nCoarse, relTheta, relZeta)
+
+Scores of the subjects of the last `sample!`: the posterior mean and standard deviation of every θ_i and ζ_i and their covariance, computed on the device from the
+resident item-level trace and data set in either trace mode (`erm_get_scores`; after `sample!(MCMC; devices=...)` over the rows of all chains,
+`erm_farm_get_scores`), with the EAP reliabilities.  Posterior under the population law of `getWaicMarginal`: for the response-time models θ borrows strength from
+the response times, so the scores differ from `Post.mean` by design; for GibbsMlIrt the two agree.  ζ, its sd and the covariance are NaN for GibbsMlIrt.  Not for
+the two quantile models.
+"""
+function getScores(M::GibbsAMD; nodes::Integer = 61)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    score, out = zeros(M.Cond.nSubj, 7), zeros(4)
+    if farmed
+        check(ccall((:erm_farm_get_scores, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.farm, nodes, score, out))
+    else
+        check(ccall((:erm_get_scores, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.handle, nodes, score, out))
+    end
+    return scoresTuple(score, out)
+end
+
+"""
+    scoreRespondents(model, Y, logT, X, rows; nodes = 61, weighting = :equal, device = 0)
+
+`getScores` for caller-supplied respondents (`Y` UInt8 nSubj x nItem, `logT`, `X` nSubj x nFeat) against saved item-trace rows (`rows` is item_trace_width x nRows,
+as `marginalLogLik` takes them), on the device (`erm_score`).  `weighting = :equal`: every row counts once, the usual operational scoring; `:likelihood`: row s
+counts exp(l_s), the posterior of a new respondent given their own data and the saved item posterior.
+"""
+function scoreRespondents(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}; nodes::Integer = 61,
+                          weighting::Symbol = :equal, device::Integer = 0)
+    N, J = size(Y)
+    w = weighting == :equal ? 0 : weighting == :likelihood ? 1 : error("weighting must be :equal or :likelihood")
+    score, out = zeros(N, 7), zeros(4)
+    check(ccall((:erm_score, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, w, score, out))
+    return scoresTuple(score, out)
 end
 
 """

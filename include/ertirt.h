@@ -262,6 +262,47 @@ int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* 
 int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                         int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u);
 
+/* Scores of respondents: the posterior mean and standard deviation of every subject's theta_i and zeta_i, their covariance, and what the rows were worth -- the
+ * standard errors and reliabilities an IRT model is fitted for -- from the item-level trace alone.  Given a row of the item-level trace, a subject's (theta, zeta)
+ * depends on nothing but its own data, so no trace of theta is needed: the row-wise posterior moments, averaged over the rows, are the Rao-Blackwell estimators of
+ * E[theta_i | data] and Var[theta_i | data] with the item and structural uncertainty integrated.  Computed AFTER the run from resident state, in ERM_TRACE_SUMMARY as in
+ * ERM_TRACE_FULL; the calls only read the engine.  Served: the five models of erm_get_marginal_waic; the two quantile models are refused with ERM_ERR_ARG for its reason.
+ * Definition, for subject i at row s.  The population law (mu, sd = sqrt(S11'), m0, m1, v), the node rule (z_q, theta_q, e_q, M, S) and the item sums (P, R0, R1, ...)
+ * are exactly those of erm_get_marginal_waic above; l_s = M + log S.
+ *   theta at the row   w_q = exp(e_q - M) / S,  Z1 = sum w_q z_q,  Z2 = sum w_q z_q^2;   E_s = mu + sd Z1,  V_s = sd^2 (Z2 - Z1^2), clamped at 0.
+ *                      The three sums S, sum exp(e_q - M) z_q, sum exp(e_q - M) z_q^2 stream and merge under the same running maximum as M and S do there.
+ *   zeta at the row    given theta and the response times, zeta ~ N(c0 + c1 theta, u):  u = v / (1 + v P),  c0 = (m0 + v R0) / (1 + v P),  c1 = (m1 - v R1) / (1 + v P).
+ *                      No 1 / v: v = 0 is an ordinary case.  Hence Ez_s = c0 + c1 E_s,  Vz_s = u + c1^2 V_s,  C_s = c1 V_s.  MlIrt has no zeta: its zeta columns and
+ *                      its covariance are NaN.
+ *   across the rows    in trace order, with weight omega_s:
+ *                        ERM_SCORE_EQUAL       omega_s = 1: right for the subjects of the data set the chain was fitted to, and the usual operational scoring, in
+ *                                              which a new respondent does not update the item posterior;
+ *                        ERM_SCORE_LIKELIHOOD  omega_s = exp(l_s - Lambda), Lambda the running maximum of l_s (what is held is rescaled when Lambda rises): the
+ *                                              posterior of a new respondent given their own data and the saved item posterior.
+ *                      West's weighted Welford on the pair (E_s, Ez_s) with its co-moment, the weighted means of V_s, Vz_s and C_s, sum omega and sum omega^2: eleven
+ *                      doubles per subject, held in registers from the first row to the last.
+ *   results            the law of total variance, W = sum omega:  theta = mean E,  theta_sd^2 = mean V + M2_E / W,  cov = mean C + C_EEz / W,  zeta and zeta_sd
+ *                      likewise,  row_ess = W^2 / sum omega^2 (= n_rows under equal weights).
+ * Population law, not the sampler's conditionals.  The scores are posterior under the law erm_get_marginal_waic defines: theta borrows strength from the response
+ * times through S12 (RtIrt, Null, Cross) or beta_theta (Latent) and rho (Cross).  The reference's sampler is not the Gibbs sampler of that joint model for the
+ * response-time models -- drawSubjAbility (src/Draw.pl.jl:49-62) and drawSubjSpeed (:132-141) each use the marginal prior and ignore Sigma_p[1,2]; Latent's theta draw
+ * ignores zeta's regression on theta -- so for those models the scores differ from Post.mean BY DESIGN.  Only for GibbsMlIrt is the sampler's theta conditional the
+ * model's own, and there the two agree (tests/test_score_host.py, tests/test_gpu_scores.py).
+ * Output: score, column-major [n_subj][7], column ERM_SCORE_*; COARSE is 1.0 if S < 2 at some row (the marginal WAIC's rule) and 0.0 otherwise.
+ *   out4 (may be NULL) = { n_subj, n_rows, Q, number of coarse subjects }.  Everything is fp64 whatever the engine's precision; every sum has a fixed order and nothing
+ *   is atomic; a subject's result depends on its own data, the rows, Q and the weighting only; results are bit-reproducible from call to call and do not depend on
+ *   how the sweeps were split into erm_run calls.
+ * erm_get_scores: the post-burn-in rows of the resident item trace, read in place, equal weights.  n_nodes and the refusals as erm_get_marginal_waic's, except that
+ *   ONE post-burn-in row is enough.  erm_farm_get_scores (below): the same over the chain-major table of erm_farm_get_marginal_waic on chain 0's device; a farm of one
+ *   chain returns its engine's result bit for bit.
+ * erm_score: the same kernel on caller-supplied data and rows, validated as erm_marginal_loglik validates them (a NaN: ERM_ERR_NONFINITE; a bad row: ERM_ERR_ARG,
+ *   the message names the row); n_rows >= 1; an unknown weighting: ERM_ERR_ARG. */
+enum { ERM_SCORE_EQUAL = 0, ERM_SCORE_LIKELIHOOD = 1 };
+enum { ERM_SCORE_THETA = 0, ERM_SCORE_THETA_SD = 1, ERM_SCORE_ZETA = 2, ERM_SCORE_ZETA_SD = 3, ERM_SCORE_COV = 4, ERM_SCORE_ROW_ESS = 5, ERM_SCORE_COARSE = 6, ERM_SCORE_COLS = 7 };
+int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4);
+int erm_score(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+              int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4);
+
 /* Posterior predictive checks (Gelman, Meng and Stern 1996; Sinharay 2006; Glas and Meijer 2003; Marianti et al. 2014), drawn and accumulated on the device.  The
  * reference has no counterpart.  Post-burn-in row number k = 1, 2, ... (the rows behind Post.mean) is a REPLICATE row when (k - 1) mod thin = 0.  At a replicate
  * row the whole data set is drawn again from the model at the values of that row -- the law whose log-density is WAIC's cell term: y_rep ~ Bernoulli(p),
@@ -345,6 +386,7 @@ int erm_farm_get_trace(erm_farm_handle f, int which, double* out);
 int erm_farm_get_mean(erm_farm_handle f, erm_state* out);
 int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Dbar over the rows of all chains, Dhat at the joint Post.mean (the same reduction as erm_farm_get_mean, evaluated on the first device) */
 int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* the marginal WAIC over the rows of all chains: see erm_get_marginal_waic */
+int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4);                          /* the scores over the rows of all chains: see erm_get_scores */
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed);
 /* The farm's joint convergence diagnostics: the estimators of erm_get_diagnostics / erm_get_convergence / erm_get_rank_diagnostics / erm_get_rank_convergence, as
  * defined there, applied to the L = erm_farm_chains chains jointly -- chain l takes the place of interleaved chain l: M = 2 L sequences of
