@@ -68,6 +68,7 @@ EXPORTS = [
     "erm_farm_get_diagnostics", "erm_farm_get_convergence", "erm_farm_get_rank_diagnostics", "erm_farm_get_rank_convergence", "erm_debug_diagnostics",
     "erm_get_marginal_waic", "erm_farm_get_marginal_waic", "erm_marginal_loglik",
     "erm_get_scores", "erm_farm_get_scores", "erm_score",
+    "erm_get_marginal_loo", "erm_farm_get_marginal_loo", "erm_psis_loo",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -212,6 +213,9 @@ def load():
     lib.erm_farm_get_scores.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
     lib.erm_score.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_void_p]
+    lib.erm_get_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.erm_psis_loo.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -283,6 +287,35 @@ def _score_call(fn, h, nodes, n_subj):
     score, out = np.empty((len(SCORE_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
     check(fn(h, marginal_nodes(nodes), score.ctypes.data, out.ctypes.data))
     return _score_result(score, out)
+
+
+# erm_get_marginal_loo / erm_farm_get_marginal_loo / erm_psis_loo: the columns of pw [n_subj][4] (ERM_LOO_*) and the limits of the rows per unit
+LOO_COLUMNS = ("elpd_u", "p_u", "khat", "nEff")
+PSIS_MIN_ROWS, PSIS_MAX_ROWS, PSIS_K_BAD = 25, 8192, 0.7
+
+
+def psis_rows(S):
+    """The rows per unit as PSIS-LOO takes them: 25 .. 8192."""
+    S = int(S)
+    if S < PSIS_MIN_ROWS or S > PSIS_MAX_ROWS:
+        raise ValueError(f"PSIS-LOO needs {PSIS_MIN_ROWS} .. {PSIS_MAX_ROWS} rows per unit ({S} given)")
+    return S
+
+
+def _loo_result(out, pw):
+    """out12 and pw as the library fills it, (4, n_subj) C-ordered = column-major [n_subj][4], -> a dict of the totals, with the pointwise columns if pw is given."""
+    res = dict(elpd=float(out[0]), pLoo=float(out[1]), LOOIC=float(out[2]), se=float(out[3]), lppd=float(out[4]), nUnits=int(out[5]), nRows=int(out[6]),
+               nBadK=int(out[7]), nHighK=int(out[8]), tailLen=int(out[9]), nNodes=int(out[10]), nCoarse=int(out[11]))
+    if pw is not None:
+        res.update({name: pw[k] for k, name in enumerate(LOO_COLUMNS)})
+    return res
+
+
+def _loo_call(fn, h, nodes, n_subj, pointwise):
+    out = np.empty(12, dtype=np.float64)
+    pw = np.empty((len(LOO_COLUMNS), n_subj), dtype=np.float64) if pointwise else None
+    check(fn(h, marginal_nodes(nodes), out.ctypes.data, None if pw is None else pw.ctypes.data))
+    return _loo_result(out, pw)
 
 
 STATE_FIELDS = ("theta", "a", "b", "zeta", "lambda_", "sig2t", "beta", "sigp", "rho", "nu")
@@ -503,6 +536,11 @@ class Engine(_Diagnostics):
         The totals (erm_get_waic's, with nNodes and nCoarse); with pointwise=True (totals, lppd_i, p_i)."""
         return _marginal_call(self._lib.erm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
 
+    def marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_get_marginal_loo: Pareto-smoothed leave-one-subject-out on the marginal log-likelihoods, computed on the device from the resident item trace after the
+        run.  Returns a dict of out12; pointwise=True adds elpd_u, p_u, khat, nEff [n_subj]."""
+        return _loo_call(self._lib.erm_get_marginal_loo, self._h, nodes, self.cfg.n_subj, pointwise)
+
     def scores(self, nodes=MARGINAL_NODES):
         """erm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on the device from the
         resident item trace after the run (equal weights).  A dict of SCORE_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
@@ -658,6 +696,10 @@ class Farm(_Diagnostics):
         """erm_farm_get_marginal_waic: Engine.marginal_waic over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
         return _marginal_call(self._lib.erm_farm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
 
+    def marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_farm_get_marginal_loo: Engine.marginal_loo over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
+        return _loo_call(self._lib.erm_farm_get_marginal_loo, self._h, nodes, self.cfg.n_subj, pointwise)
+
     def scores(self, nodes=MARGINAL_NODES):
         """erm_farm_get_scores: Engine.scores over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
         return _score_call(self._lib.erm_farm_get_scores, self._h, nodes, self.cfg.n_subj)
@@ -744,6 +786,22 @@ def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", d
     check(load().erm_score(int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, rr.shape[0], marginal_nodes(nodes), score_weighting(weighting),
                            sc.ctypes.data, out.ctypes.data))
     return _score_result(sc, out)
+
+
+def psis_loo(l, *, want_lw=False, device=0):
+    """erm_psis_loo: the PSIS-LOO kernel on a caller-supplied table l [N, S] of log-likelihoods (unit, row), as marginal_loglik returns it, 25 <= S <= 8192.
+    Returns Engine.marginal_loo's pointwise dict (nNodes = nCoarse = 0), with lw [N, S] -- the smoothed, normalised log-weights -- if want_lw."""
+    ll = np.asfortranarray(l, dtype=np.float64)
+    if ll.ndim != 2:
+        raise ValueError("l must be [unit, row]")
+    N, S = ll.shape
+    out, pw = np.empty(12, dtype=np.float64), np.empty((len(LOO_COLUMNS), N), dtype=np.float64)
+    lw = np.empty((N, S), dtype=np.float64, order="F") if want_lw else None
+    check(load().erm_psis_loo(int(device), ll.ctypes.data, N, S, out.ctypes.data, pw.ctypes.data, None if lw is None else lw.ctypes.data))
+    res = _loo_result(out, pw)
+    if want_lw:
+        res["lw"] = lw
+    return res
 
 
 def rccl_unique_id() -> bytes:

@@ -120,6 +120,28 @@ class OutputWaic:
         return f"OutputWaic(unit={self.unit!r}, elpd={self.elpd}, pWaic={self.pWaic}, WAIC={self.WAIC}, se={self.se}, nHighVar={self.nHighVar})"
 
 
+class OutputLoo:
+    """Marginal PSIS-LOO of a fit (getLooMarginal / psisLoo; the reference offers DIC only): elpd = sum_u elpd_u, pLoo = sum_u p_u, LOOIC = -2 elpd,
+    se = 2 sqrt(U Var_u(elpd_u)), lppd; nBadK = the units with khat > 0.7 (Inf included), nHighK = those above the sample-size dependent threshold
+    min(1 - 1 / log10(nRows), 0.7); tailLen = M, the values the generalised Pareto law is fitted to; nNodes, nCoarse as OutputWaic's.  Pointwise (subjects in
+    order): elpd_u, p_u, khat (the Pareto shape of the subject's importance ratios: above the threshold the posterior would move if the subject were left out --
+    an aberrant or influential respondent -- and elpd_u is optimistic; +Inf: the tail could not be fitted), nEff (the effective number of rows behind elpd_u)."""
+
+    def __init__(self, elpd=None, pLoo=None, LOOIC=None, se=None, lppd=None, unit=None, nUnits=None, nRows=None, nBadK=None, nHighK=None, tailLen=None,
+                 elpd_u=None, p_u=None, khat=None, nEff=None, nNodes=None, nCoarse=None):
+        self.elpd, self.pLoo, self.LOOIC, self.se, self.lppd = elpd, pLoo, LOOIC, se, lppd
+        self.unit, self.nUnits, self.nRows, self.nBadK, self.nHighK, self.tailLen = unit, nUnits, nRows, nBadK, nHighK, tailLen
+        self.elpd_u, self.p_u, self.khat, self.nEff = elpd_u, p_u, khat, nEff
+        self.nNodes, self.nCoarse = nNodes, nCoarse
+
+    @property
+    def lppd_u(self):
+        return None if self.elpd_u is None else self.elpd_u + self.p_u
+
+    def __repr__(self):
+        return f"OutputLoo(unit={self.unit!r}, elpd={self.elpd}, pLoo={self.pLoo}, LOOIC={self.LOOIC}, se={self.se}, nBadK={self.nBadK}, nHighK={self.nHighK})"
+
+
 class OutputScores:
     """Scores of the respondents (getScores / scoreRespondents; the reference has no counterpart): per subject theta, thetaSd (the posterior mean of ability and its
     standard error), zeta, zetaSd, cov (of theta and zeta; the three are NaN for GibbsMlIrt), rowEss (the rows' effective size: nRows under equal weights) and

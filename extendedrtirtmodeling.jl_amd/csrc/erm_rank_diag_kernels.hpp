@@ -76,14 +76,15 @@ __device__ __forceinline__ void rk_block_sum2(double& a, double& b, RkShared& sh
 }
 
 // bitonic network on the P (key, position) pairs, ascending by (key, position): the position breaks ties, so the padding (key ~0, positions >= S) stays behind
-// every draw whatever its key
-__device__ inline void rk_sort(uint64_t* key, uint16_t* pos, int P)
+// every draw whatever its key.  THREADS threads, numbered tid = 0 .. THREADS - 1, share the P pairs; the barriers are the workgroup's, so every thread of the
+// workgroup calls it with the same P (psis_kernel, erm_psis_kernels.hpp: several groups of a workgroup, each on its own pairs)
+template <int THREADS>
+__device__ inline void rk_sort_n(uint64_t* key, uint16_t* pos, int P, int tid)
 {
-    const int tid = (int)threadIdx.x;
     for (int k = 2; k <= P; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
 #pragma unroll 1
-            for (int t = tid; t < (P >> 1); t += RK_THREADS) {
+            for (int t = tid; t < (P >> 1); t += THREADS) {
                 const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
                 const uint64_t ka = key[lo], kb = key[hi];
                 const uint16_t pa = pos[lo], pb = pos[hi];
@@ -94,6 +95,7 @@ __device__ inline void rk_sort(uint64_t* key, uint16_t* pos, int P)
         }
     }
 }
+__device__ inline void rk_sort(uint64_t* key, uint16_t* pos, int P) { rk_sort_n<RK_THREADS>(key, pos, P, (int)threadIdx.x); }
 
 // the normal score of an average rank, as a REAL call: inlined, the 48 fp64 coefficients of AS 241 are hoisted out of the loop over the draws and held in
 // registers across it

@@ -21,6 +21,7 @@
 #include "erm_predictive_kernels.hpp"      // posterior predictive checks: the replicate pass behind every sweep
 #include "erm_rank_diag_kernels.hpp"       // rank-normalised convergence diagnostics: bulk / tail ESS, rank R-hat
 #include "erm_marginal_kernels.hpp"        // marginal WAIC: theta and zeta integrated out, from the item trace
+#include "erm_psis_kernels.hpp"            // marginal PSIS-LOO: Pareto-smoothed leave-one-subject-out from marginal_kernel's l
 #include "erm_score_kernels.hpp"           // scores of respondents: posterior moments of theta and zeta, from the item trace
 #include "erm_farm_diag.hpp"               // the chain farm's joint diagnostics: chunk arithmetic
 #include "erm_geometry.hpp"
@@ -190,8 +191,9 @@ static int pw_totals(const double2* acc_ms, const double2* acc_w, int64_t units,
     return 0;
 }
 
-// Marginal WAIC (erm_marginal_kernels.hpp; include/ertirt.h: erm_get_marginal_waic): the one place that launches marginal_kernel -- for an engine's resident
-// data set and item trace, for a farm's table of rows and for erm_marginal_loglik's caller-supplied data.  Everything it is given lives on the current device.
+// Marginal WAIC (erm_marginal_kernels.hpp; include/ertirt.h: erm_get_marginal_waic): marginal_launch is the one place that launches marginal_kernel -- for
+// marginal_run (an engine's resident data set and item trace, a farm's table of rows, erm_marginal_loglik's caller-supplied data) and for the chunks of the
+// marginal PSIS-LOO (marginal_loo_run).  Everything they are given lives on the current device.
 struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; };
 static int marg_refuse_model(int model)
 {
@@ -207,25 +209,14 @@ static int marg_nodes(int32_t n_nodes, int* Q)
     if (!marg_nodes_ok(*Q)) return fail(ERM_ERR_ARG, "n_nodes must be 0 (= " + std::to_string(MARG_NODES_DEFAULT) + ") or odd and in " + std::to_string(MARG_NODES_MIN) + " .. " + std::to_string(MARG_NODES_MAX));
     return 0;
 }
+// one launch of marginal_kernel over the subjects of D and the table of rows, waited for: l_dev [n_rows][D.N], the accumulators and the flags [D.N], any of them NULL
 template <typename real>
-static int marginal_run(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double* out10, double* lppd_u, double* p_u)
+static int marginal_launch(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double2* acc_ms, double2* acc_w, unsigned int* coarse)
 {
-    const bool totals = out10 || lppd_u || p_u;
-    if (totals && n_rows < 2) return fail(ERM_ERR_STATE, "the marginal WAIC needs at least two post-burn-in rows");
     const int64_t N = D.N, ld = item_trace_width(D.model, D.J, D.Fk);
-    DevBuf dMs, dW, dCoarse, dCnt, dL, dP;
-    const char* what = "the marginal WAIC's accumulators";
-    if (totals) {
-        if (int rc = dMs.try_alloc((size_t)N * sizeof(double2), what)) return rc;
-        if (int rc = dW.try_alloc((size_t)N * sizeof(double2), what)) return rc;
-        if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
-        if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
-        if (lppd_u) if (int rc = dL.try_alloc((size_t)N * sizeof(double), what)) return rc;
-        if (p_u) if (int rc = dP.try_alloc((size_t)N * sizeof(double), what)) return rc;
-    }
     MargArgs a{};
     a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = ld; a.N = N; a.J = D.J; a.F = D.Fk; a.Q = Q;
-    a.l_out = l_dev; a.acc_ms = dMs.as<double2>(); a.acc_w = dW.as<double2>(); a.coarse = dCoarse.as<unsigned int>();
+    a.l_out = l_dev; a.acc_ms = acc_ms; a.acc_w = acc_w; a.coarse = coarse;
     const size_t lds = (size_t)2 * marg_row_lds(ld, D.J) * sizeof(double);
     const dim3 grid((unsigned)((N + MARG_TILE - 1) / MARG_TILE));
     auto launch = [&](auto M) -> int {
@@ -246,6 +237,25 @@ static int marginal_run(const MargData& D, const double* rows, int64_t n_rows, i
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+template <typename real>
+static int marginal_run(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double* out10, double* lppd_u, double* p_u)
+{
+    const bool totals = out10 || lppd_u || p_u;
+    if (totals && n_rows < 2) return fail(ERM_ERR_STATE, "the marginal WAIC needs at least two post-burn-in rows");
+    const int64_t N = D.N;
+    DevBuf dMs, dW, dCoarse, dCnt, dL, dP;
+    const char* what = "the marginal WAIC's accumulators";
+    if (totals) {
+        if (int rc = dMs.try_alloc((size_t)N * sizeof(double2), what)) return rc;
+        if (int rc = dW.try_alloc((size_t)N * sizeof(double2), what)) return rc;
+        if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
+        if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
+        if (lppd_u) if (int rc = dL.try_alloc((size_t)N * sizeof(double), what)) return rc;
+        if (p_u) if (int rc = dP.try_alloc((size_t)N * sizeof(double), what)) return rc;
+    }
+    if (int rc = marginal_launch<real>(D, rows, n_rows, Q, stream, l_dev, dMs.as<double2>(), dW.as<double2>(), dCoarse.as<unsigned int>())) return rc;
     if (!totals) return 0;
     double out8[8], sums[PW_FIN_COLS];
     if (int rc2 = pw_totals(dMs.as<double2>(), dW.as<double2>(), N, n_rows, stream, out8)) return rc2;
@@ -314,6 +324,89 @@ static int score_run(const MargData& D, const double* rows, int64_t n_rows, int 
     return 0;
 }
 
+// Marginal PSIS-LOO (erm_psis_kernels.hpp; include/ertirt.h: erm_get_marginal_loo): the one place that launches psis_kernel -- for an engine's or a farm's l, which
+// marginal_kernel writes chunk by chunk, and for erm_psis_loo's caller-supplied table.  The subjects go through in chunks whose staged l fits 256 MB whatever S
+// (ERM_PSIS_CHUNK: a chunk length in subjects, for the tests of the chunk tails); fill(c0, nc, dst) puts l of the subjects [c0, c0 + nc) into dst as [S][nc], and
+// take(c0, nc, src), if given, receives their smoothed log-weights in the same layout.
+static int psis_rows_ok(int64_t S)
+{
+    if (S < PSIS_MIN_ROWS) return fail(ERM_ERR_ARG, "PSIS-LOO needs at least " + std::to_string(PSIS_MIN_ROWS) + " rows per unit (" + std::to_string(S) + " given): fewer leave a tail of less than 5 values");
+    if (S > PSIS_MAX_ROWS) return fail(ERM_ERR_ARG, "PSIS-LOO takes at most " + std::to_string(PSIS_MAX_ROWS) + " rows per unit (" + std::to_string(S) + " given): a unit's rows are sorted in LDS");
+    return 0;
+}
+template <typename Fill, typename Take>
+static int psis_run(int64_t N, int64_t S, hipStream_t stream, Fill&& fill, Take&& take, bool want_lw, double* out8, double* pw)
+{
+    const int P = rk_pad((int)S);
+    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / (S * (int64_t)sizeof(double)));
+    if (const char* e = getenv("ERM_PSIS_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk = std::min<int64_t>(chunk, v); }
+    chunk = std::min(chunk, N);
+    DevBuf dL, dXs, dPw, dOut;
+    if (int rc = dL.try_alloc((size_t)chunk * S * sizeof(double), "PSIS-LOO's log-likelihoods")) return rc;
+    if (int rc = dXs.try_alloc((size_t)chunk * S * sizeof(double), "PSIS-LOO's staged log-likelihoods")) return rc;
+    if (int rc = dPw.try_alloc((size_t)N * PSIS_DEV_COLS * sizeof(double), "PSIS-LOO's pointwise table")) return rc;
+    if (int rc = dOut.try_alloc(8 * sizeof(double), "PSIS-LOO's totals")) return rc;
+    const int tps = P <= 2048 ? 64 : P <= 4096 ? 128 : 256, ns = 256 / tps;
+    const size_t lds = (size_t)ns * P * 10;
+    const void* kern = tps == 64 ? reinterpret_cast<const void*>(&psis_kernel<64>) : tps == 128 ? reinterpret_cast<const void*>(&psis_kernel<128>) : reinterpret_cast<const void*>(&psis_kernel<256>);
+    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+        const int64_t nc = std::min(chunk, N - c0);
+        if (int rc = fill(c0, nc, dL.as<double>())) return rc;
+        hipLaunchKernelGGL(psis_transpose_kernel, dim3((unsigned)((nc + 31) / 32), (unsigned)((S + 31) / 32)), dim3(256), 0, stream, dL.as<double>(), (long long)S, (long long)nc, dXs.as<double>());
+        PsisArgs a{};
+        a.xs = dXs.as<double>(); a.n = nc; a.S = (int)S; a.P = P; a.pw = dPw.as<double>(); a.n_all = N; a.c0 = c0; a.want_lw = want_lw ? 1 : 0;
+        const dim3 grid((unsigned)((nc + ns - 1) / ns));
+        if (tps == 64) hipLaunchKernelGGL(psis_kernel<64>, grid, dim3(256), lds, stream, a);
+        else if (tps == 128) hipLaunchKernelGGL(psis_kernel<128>, grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL(psis_kernel<256>, grid, dim3(256), lds, stream, a);
+        if (want_lw) hipLaunchKernelGGL(psis_transpose_kernel, dim3((unsigned)((S + 31) / 32), (unsigned)((nc + 31) / 32)), dim3(256), 0, stream, dXs.as<double>(), (long long)nc, (long long)S, dL.as<double>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        if (want_lw) if (int rc = take(c0, nc, dL.as<double>())) return rc;
+    }
+    hipLaunchKernelGGL(psis_totals_kernel, dim3(1), dim3(256), 0, stream, dPw.as<double>(), (long long)N, psis_k_threshold(S), dOut.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(out8, dOut.p, 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (pw) HIPCHK(hipMemcpy(pw, dPw.p, (size_t)N * PSIS_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+// out12 from psis_totals_kernel's sums
+static void psis_out12(const double* s8, int64_t N, int64_t S, int Q, int64_t n_coarse, double* out12)
+{
+    const double U = (double)N, var_u = N > 1 ? s8[3] / (U - 1.0) : 0.0;
+    out12[0] = s8[0]; out12[1] = s8[1]; out12[2] = -2.0 * s8[0]; out12[3] = 2.0 * std::sqrt(U * var_u); out12[4] = s8[2]; out12[5] = U; out12[6] = (double)S;
+    out12[7] = s8[4]; out12[8] = s8[5]; out12[9] = (double)psis_tail_len(S); out12[10] = (double)Q; out12[11] = (double)n_coarse;
+}
+// an engine's or a farm's: l of every chunk from marginal_kernel, on the data set D and the table of rows (both on the current device)
+template <typename real>
+static int marginal_loo_run(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* out12, double* pw)
+{
+    if (int rc = psis_rows_ok(n_rows)) return rc;
+    const int64_t N = D.N;
+    DevBuf dCoarse, dCnt;
+    if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), "the marginal LOO's flags")) return rc;
+    if (int rc = dCnt.try_alloc(sizeof(unsigned long long), "the marginal LOO's flags")) return rc;
+    auto fill = [&](int64_t c0, int64_t nc, double* dst) -> int {
+        MargData Dc = D;
+        Dc.Y = D.Y + (size_t)c0 * D.J;
+        Dc.C = D.C ? static_cast<const char*>(D.C) + (size_t)c0 * D.J * sizeof(real) : nullptr;
+        Dc.X = D.X ? static_cast<const char*>(D.X) + (size_t)c0 * D.Fk * sizeof(real) : nullptr;
+        Dc.N = nc;
+        return marginal_launch<real>(Dc, rows, n_rows, Q, stream, dst, nullptr, nullptr, dCoarse.as<unsigned int>() + c0);
+    };
+    double s8[8];
+    if (int rc = psis_run(N, n_rows, stream, fill, [](int64_t, int64_t, const double*) { return 0; }, false, s8, pw)) return rc;
+    hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    unsigned long long nc = 0;
+    HIPCHK(hipMemcpy(&nc, dCnt.p, sizeof(nc), hipMemcpyDeviceToHost));
+    psis_out12(s8, N, n_rows, Q, (int64_t)nc, out12);
+    return 0;
+}
+
 // A persistent launch needs all its workgroups resident at once.  Two persistent launches of ONE process on one device (a farm's chains sharing a
 // device, several engines) could each hold some compute units and wait for the other's for ever: they take turns.
 std::mutex g_persist_mu[64];
@@ -338,6 +431,8 @@ struct EngineBase {
     // marginal WAIC (erm_get_marginal_waic; the farm hands chain 0 a table of the rows of all chains on its device: rows != NULL), and the resident item trace
     virtual int marginal_waic(int Q, const double* rows, int64_t n_rows, double* out10, double* lppd_u, double* p_u) = 0;
     virtual const double* item_trace_dev() const = 0;
+    // marginal PSIS-LOO (erm_get_marginal_loo; rows as for marginal_waic)
+    virtual int marginal_loo(int Q, const double* rows, int64_t n_rows, double* out12, double* pw) = 0;
     // scores of respondents (erm_get_scores; rows as for marginal_waic), equal weights
     virtual int scores(int Q, const double* rows, int64_t n_rows, double* score, double* out4) = 0;
     // posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
@@ -921,6 +1016,17 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipSetDevice(cfg.device));
         const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
         return marginal_run<real>(D, rows, n_rows, Q, stream, nullptr, out10, lppd_u, p_u);
+    }
+    // ---- marginal PSIS-LOO: as the marginal WAIC, from the resident data set and item-trace rows; 25 .. 8192 of them
+    int marginal_loo(int Q, const double* rows, int64_t n_rows, double* out12, double* pw) override {
+        if (int rc = marg_refuse_model(cfg.model)) return rc;
+        if (sharded()) return fail(ERM_ERR_STATE, "the marginal LOO is not available on a shard (every subject's data must be resident on one device)");
+        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
+        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
+        if (!rows) { rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows; }
+        HIPCHK(hipSetDevice(cfg.device));
+        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
+        return marginal_loo_run<real>(D, rows, n_rows, Q, stream, out12, pw);
     }
     // ---- scores: as the marginal WAIC, from the resident data set and item-trace rows; one post-burn-in row is enough
     int scores(int Q, const double* rows, int64_t n_rows, double* score, double* out4) override {
@@ -1917,6 +2023,14 @@ int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* 
     if (int rc = marg_nodes(n_nodes, &Q)) return rc;
     return h->e->marginal_waic(Q, nullptr, 0, out10, lppd_u, p_u);
 }
+int erm_get_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw)
+{
+    CHK_H;
+    if (!out12) return fail(ERM_ERR_ARG, "out is NULL");
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    return h->e->marginal_loo(Q, nullptr, 0, out12, pw);
+}
 int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4)
 {
     CHK_H;
@@ -2172,6 +2286,19 @@ int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10
     if (int rc = farm_row_table(f, 2, "the marginal WAIC needs at least two post-burn-in rows", dTab, &n_rows)) return rc;
     return f->eng[0]->e->marginal_waic(Q, dTab.as<double>(), n_rows, out10, lppd_u, p_u);
 }
+// The farm's marginal PSIS-LOO: the same table, the same device.
+int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw)
+{
+    CHK_F;
+    if (!out12) return fail(ERM_ERR_ARG, "out is NULL");
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
+    DevBuf dTab;
+    int64_t n_rows = 0;
+    if (int rc = farm_row_table(f, 1, "the marginal LOO needs post-burn-in rows (25 .. 8192 over the chains)", dTab, &n_rows)) return rc;
+    return f->eng[0]->e->marginal_loo(Q, dTab.as<double>(), n_rows, out12, pw);
+}
 // The farm's scores: the same table, the same device, equal weights.
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4)
 {
@@ -2268,6 +2395,28 @@ int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, i
     if (l) if (int rc = dL.try_alloc((size_t)n_subj * n_rows * sizeof(double), "erm_marginal_loglik's output")) return rc;
     if (int rc = marginal_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, nullptr, dL.as<double>(), out10, lppd_u, p_u)) return rc;
     if (l) HIPCHK(hipMemcpy(l, dL.p, (size_t)n_subj * n_rows * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int erm_psis_loo(int device, const double* l, int64_t n_subj, int64_t n_rows, double* out12, double* pw, double* lw)
+{
+    if (!l || !out12) return fail(ERM_ERR_ARG, "l / out is NULL");
+    if (n_subj <= 0 || n_subj >= (1LL << 32)) return fail(ERM_ERR_ARG, "n_subj out of range");
+    if (int rc = psis_rows_ok(n_rows)) return rc;
+    const int64_t N = n_subj, S = n_rows;
+    for (size_t e = 0; e < (size_t)N * S; ++e) if (!std::isfinite(l[e])) return fail(ERM_ERR_NONFINITE, "NaN or Inf in l (unit " + std::to_string(e % (size_t)N) + ", row " + std::to_string(e / (size_t)N) + ")");
+    HIPCHK(hipSetDevice(device));
+    auto fill = [&](int64_t c0, int64_t nc, double* dst) -> int {
+        HIPCHK(hipMemcpy2D(dst, (size_t)nc * sizeof(double), l + c0, (size_t)N * sizeof(double), (size_t)nc * sizeof(double), (size_t)S, hipMemcpyHostToDevice));
+        return 0;
+    };
+    auto take = [&](int64_t c0, int64_t nc, const double* src) -> int {
+        HIPCHK(hipMemcpy2D(lw + c0, (size_t)N * sizeof(double), src, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), (size_t)S, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    double s8[8];
+    if (int rc = psis_run(N, S, nullptr, fill, take, lw != nullptr, s8, pw)) return rc;
+    psis_out12(s8, N, S, 0, 0, out12);
     return 0;
 }
 

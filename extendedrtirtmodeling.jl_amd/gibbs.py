@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import InputPara, OutputDic, OutputPpc, OutputScores, OutputWaic, SimConditions
+from .base import InputPara, OutputDic, OutputLoo, OutputPpc, OutputScores, OutputWaic, SimConditions
 
 _PREC = {"f32": _lib.PREC_F32, "f64": _lib.PREC_F64}
 _TRACE = {"summary": _lib.TRACE_SUMMARY, "full": _lib.TRACE_FULL}
@@ -535,9 +535,15 @@ def getWaicHost(MCMC: _GibbsBase, unit) -> OutputWaic:
 
 def compareWaic(A, B) -> dict:
     """Two fits of the SAME data compared unit by unit: elpd_diff = sum_u (elpd_u^A - elpd_u^B) (positive: A predicts better) and its standard error
-    se_diff = sqrt(U Var_u(elpd_u^A - elpd_u^B)).  A, B: samplers (getWaic(pointwise=True) is called) or OutputWaic objects that carry the pointwise vectors."""
-    wa = A if isinstance(A, OutputWaic) else getWaic(A, pointwise=True)
-    wb = B if isinstance(B, OutputWaic) else getWaic(B, pointwise=True)
+    se_diff = sqrt(U Var_u(elpd_u^A - elpd_u^B)).  A, B: samplers (getWaic(pointwise=True) is called) or OutputWaic objects that carry the pointwise vectors -- or
+    two OutputLoo objects (getLooMarginal(pointwise=True)): the same paired difference on the PSIS-LOO elpd_u (compareLoo)."""
+    if isinstance(A, OutputLoo) or isinstance(B, OutputLoo):
+        if not (isinstance(A, OutputLoo) and isinstance(B, OutputLoo)):
+            raise ValueError("compareWaic: an OutputLoo can only be compared with another OutputLoo")
+        wa, wb = A, B
+    else:
+        wa = A if isinstance(A, OutputWaic) else getWaic(A, pointwise=True)
+        wb = B if isinstance(B, OutputWaic) else getWaic(B, pointwise=True)
     if wa.lppd_u is None or wb.lppd_u is None:
         raise ValueError("compareWaic needs the pointwise values (getWaic(..., pointwise=True))")
     if wa.unit != wb.unit:
@@ -547,6 +553,13 @@ def compareWaic(A, B) -> dict:
     d = np.ravel(wa.elpd_u) - np.ravel(wb.elpd_u)
     U = d.size
     return dict(elpd_diff=float(np.sum(d)), se_diff=float(np.sqrt(U * np.var(d, ddof=1))) if U > 1 else 0.0, unit=wa.unit, nUnits=U)
+
+
+def compareLoo(A, B) -> dict:
+    """compareWaic on two OutputLoo results (getLooMarginal(..., pointwise=True)), or on two samplers, for which getLooMarginal is called."""
+    la = A if isinstance(A, OutputLoo) else getLooMarginal(A, pointwise=True)
+    lb = B if isinstance(B, OutputLoo) else getLooMarginal(B, pointwise=True)
+    return compareWaic(la, lb)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -677,6 +690,134 @@ def getWaicMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) 
     X = np.asarray(D.X, dtype=np.float64) if t.sees_x and MCMC.Cond.nFeat > 0 else None
     L, S = marginalLogLikHost(MCMC._model, D.Y, D.logT if t.rt else None, X, rows, Q, with_S=True)
     return waicFromLogLik(L, nNodes=Q, nCoarse=int(np.sum(np.any(S < 2.0, axis=0))))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Marginal PSIS-LOO (include/ertirt.h: erm_get_marginal_loo).  Pareto-smoothed importance-sampling leave-one-subject-out on the marginal
+# log-likelihoods l_i^(s) of the marginal WAIC, with the Pareto k^ of every respondent.
+# ------------------------------------------------------------------------------------------------------------------
+def _loo_output(r, pointwise) -> OutputLoo:
+    g = (lambda k: r[k]) if pointwise else (lambda k: None)
+    return OutputLoo(elpd=r["elpd"], pLoo=r["pLoo"], LOOIC=r["LOOIC"], se=r["se"], lppd=r["lppd"], unit=MARGINAL_UNIT, nUnits=r["nUnits"], nRows=r["nRows"],
+                     nBadK=r["nBadK"], nHighK=r["nHighK"], tailLen=r["tailLen"], elpd_u=g("elpd_u"), p_u=g("p_u"), khat=g("khat"), nEff=g("nEff"),
+                     nNodes=r["nNodes"], nCoarse=r["nCoarse"])
+
+
+def _loo_rows(MCMC):
+    """The rows per unit a sampler's getLooMarginal would see, from its conditions alone (no device is touched)."""
+    C = MCMC.Cond
+    return (C.nIter - C.nBurnin) * C.nChain          # interleaved chains of one engine or the chains of a farm: the same count
+
+
+def getLooMarginal(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, pointwise=False) -> OutputLoo:
+    """Marginal PSIS-LOO of the last sample! -- of one engine or of the chain farm of sample!(...; devices=) -- computed on the device from the resident item trace
+    and data set (erm_get_marginal_loo / erm_farm_get_marginal_loo): Pareto-smoothed leave-one-subject-out with theta_i and zeta_i integrated out, the criterion
+    getWaicMarginal's nHighVar points to.  Needs 25 .. 8192 post-burn-in rows.  pointwise=True also fetches elpd_u, p_u, khat and nEff per subject: khat above
+    0.7 flags the respondents whose removal would move the posterior (aberrant or highly influential patterns)."""
+    Q = _marginal_check(MCMC, nodes, "getLooMarginal")
+    _lib.psis_rows(_loo_rows(MCMC))
+    return _loo_output(_marginal_source(MCMC, "getLooMarginal").marginal_loo(Q, pointwise=pointwise), pointwise)
+
+
+def psisLoo(L, device=0, want_lw=False):
+    """PSIS-LOO on the device (erm_psis_loo) of a saved table L (|S|, U) of pointwise log-likelihoods, rows in trace order -- marginalLogLikHost's layout; a
+    conditional table serves as well.  Returns an OutputLoo with the pointwise vectors (and the smoothed, normalised log-weights (|S|, U) if want_lw)."""
+    L = np.asarray(L, dtype=np.float64)
+    if L.ndim != 2:
+        raise ValueError("L must be (rows, units)")
+    _lib.psis_rows(L.shape[0])
+    r = _lib.psis_loo(L.T, want_lw=want_lw, device=device)
+    out = _loo_output(r, True)
+    out.unit = None
+    return (out, r["lw"].T) if want_lw else out
+
+
+def psisTailLen(S) -> int:
+    """M = min(ceil(S / 5), ceil(3 sqrt(S))), as the float formula gives it."""
+    return int(min(np.ceil(S / 5.0), np.ceil(3.0 * np.sqrt(S))))
+
+
+def psisLooHost(L, dtype=np.float64, with_lw=False, with_fit=False):
+    """PSIS-LOO of an (|S|, U) table of pointwise log-likelihoods with numpy (the test twin of psis_kernel), written from the papers: Vehtari, Gelman and Gabry
+    (2017) for the estimator, Vehtari, Simpson, Gelman, Yao and Gabry (2024, Algorithm 1 and Appendix) for the tail length, the smoothing and the k^ prior, Zhang
+    and Stephens (2009) for the generalised-Pareto fit; r_eff = 1.  dtype=np.longdouble runs the same arithmetic in extended precision (the tests' measure of the
+    computation's own conditioning).  Returns an OutputLoo with the pointwise vectors; with_lw: also the smoothed, normalised log-weights (|S|, U); with_fit: also
+    sigma (U,) (NaN where the tail could not be fitted)."""
+    from math import floor
+    L = np.asarray(L, dtype=dtype)
+    if L.ndim != 2:
+        raise ValueError("L must be (rows, units)")
+    S, U = L.shape
+    _lib.psis_rows(S)
+    fl = dtype
+    M = psisTailLen(S)
+    G = 30 + int(floor(np.sqrt(M)))
+
+    def lse(v):
+        m = np.max(v)
+        return m + np.log(np.sum(np.exp(v - m)))
+
+    elpd, p, khat, neff, sig = (np.empty(U, dtype=fl) for _ in range(5))
+    LW = np.empty((S, U), dtype=fl)
+    for u in range(U):
+        l = L[:, u]
+        lw = -l - np.max(-l)
+        order = np.argsort(lw, kind="stable")                 # ascending by (lw, position)
+        srt = lw[order]
+        c = srt[S - M - 1]
+        x = np.exp(srt[S - M:]) - np.exp(c)
+        k, sigma = fl(np.inf), fl(np.nan)
+        xstar = x[int(floor(M / 4 + 0.5)) - 1]
+        if xstar > 0 and x[-1] - x[0] > 0:
+            with np.errstate(all="ignore"):
+                j = np.arange(1, G + 1).astype(fl)
+                b = 1 / x[-1] + (1 - np.sqrt(G / (j - fl(0.5)))) / (3 * xstar)
+                kj = np.mean(np.log1p(-b[:, None] * x[None, :]), axis=1)
+                Lj = M * (np.log(-b / kj) - kj - 1)
+                w = np.exp(Lj - lse(Lj))
+                bh = np.sum(b * w)
+                kr = np.mean(np.log1p(-bh * x))
+                sg = -kr / bh
+                kh = (M * kr + 5) / fl(M + 10)
+            if np.isfinite(bh) and np.isfinite(sg) and np.isfinite(kh):
+                k, sigma = kh, sg
+        new = srt.copy()
+        if np.isfinite(k):
+            with np.errstate(all="ignore"):
+                pr = (np.arange(1, M + 1).astype(fl) - fl(0.5)) / M
+                q = -sigma * np.log1p(-pr) if k == 0 else sigma * np.expm1(-k * np.log1p(-pr)) / k
+                new[S - M:] = np.minimum(fl(0), np.log(np.exp(c) + q))
+        lwp = np.empty(S, dtype=fl)
+        lwp[order] = new
+        norm = lse(lwp)
+        elpd[u] = lse(lwp + l) - norm
+        p[u] = (lse(l) - np.log(fl(S))) - elpd[u]
+        khat[u], sig[u] = k, sigma
+        wn = np.exp(lwp - norm)
+        neff[u] = 1 / np.sum(wn * wn)
+        LW[:, u] = lwp - norm
+    thr = min(1.0 - 1.0 / np.log10(S), 0.7)
+    el = elpd.astype(np.float64)
+    se = 2.0 * float(np.sqrt(U * np.var(el, ddof=1))) if U > 1 else 0.0
+    out = OutputLoo(elpd=float(np.sum(elpd)), pLoo=float(np.sum(p)), LOOIC=-2.0 * float(np.sum(elpd)), se=se, lppd=float(np.sum(elpd + p)), unit=None, nUnits=U, nRows=S,
+                    nBadK=int(np.sum(khat > 0.7)), nHighK=int(np.sum(khat > thr)), tailLen=M, elpd_u=elpd, p_u=p, khat=khat, nEff=neff, nNodes=0, nCoarse=0)
+    extra = ([LW] if with_lw else []) + ([sig] if with_fit else [])
+    return (out, *extra) if extra else out
+
+
+def getLooMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) -> OutputLoo:
+    """getLooMarginal evaluated with numpy on the host (the test twin of the device path): marginalLogLikHost on MCMC.Data and the item-level trace rows
+    (marginalRows, or `rows`), then psisLooHost."""
+    Q = _marginal_check(MCMC, nodes, "getLooMarginal")
+    D, t = MCMC.Data, MCMC._traits
+    if D is None:
+        raise ValueError("Data is required")
+    rows = marginalRows(MCMC) if rows is None else rows
+    X = np.asarray(D.X, dtype=np.float64) if t.sees_x and MCMC.Cond.nFeat > 0 else None
+    L, S = marginalLogLikHost(MCMC._model, D.Y, D.logT if t.rt else None, X, rows, Q, with_S=True)
+    out = psisLooHost(L)
+    out.unit, out.nNodes, out.nCoarse = MARGINAL_UNIT, Q, int(np.sum(np.any(S < 2.0, axis=0)))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------

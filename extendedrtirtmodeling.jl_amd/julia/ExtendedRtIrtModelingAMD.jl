@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getScores, scoreRespondents, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getScores, scoreRespondents, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -400,6 +400,56 @@ function marginalLogLik(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64},
                 (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                 device, model, N, J, size(X, 2), Y, logT, X, rows, R, nodes, l, C_NULL, C_NULL, C_NULL))
     return l
+end
+
+# out12 and pw as erm_get_marginal_loo fills them (pw column-major [nSubj][4], the ERM_LOO_* columns) -> a named tuple
+function looTuple(out::Vector{Float64}, pw::Matrix{Float64})
+    res = (elpd = out[1], pLoo = out[2], LOOIC = out[3], se = out[4], lppd = out[5], nUnits = Int(out[6]), nRows = Int(out[7]), nBadK = Int(out[8]),
+           nHighK = Int(out[9]), tailLen = Int(out[10]), nNodes = Int(out[11]), nCoarse = Int(out[12]))
+    return isempty(pw) ? res : merge(res, (elpd_u = pw[:, 1], p_u = pw[:, 2], khat = pw[:, 3], nEff = pw[:, 4]))
+end
+
+"""
+    getLooMarginal(MCMC; nodes = 61, pointwise = false) -> (elpd, pLoo, LOOIC, se, lppd, nUnits, nRows, nBadK, nHighK, tailLen, nNodes, nCoarse[, elpd_u, p_u, khat, nEff])
+
+The marginal PSIS-LOO: Pareto-smoothed importance-sampling leave-one-subject-out on the marginal log-likelihoods of `getWaicMarginal`, computed on the device after
+`sample!` (`erm_get_marginal_loo`; after `sample!(MCMC; devices=...)` over the rows of all chains, `erm_farm_get_marginal_loo`).  Needs 25 .. 8192 post-burn-in rows.
+`khat` is the Pareto shape of a subject's importance ratios: above 0.7 (`nBadK`; `nHighK` counts those above min(1 - 1 / log10(nRows), 0.7)) the posterior would
+move if the subject were left out -- an aberrant or highly influential respondent -- and `elpd_u` is optimistic; `Inf`: the tail could not be fitted.  Not for the
+two quantile models.
+"""
+function getLooMarginal(M::GibbsAMD; nodes::Integer = 61, pointwise::Bool = false)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    out = zeros(12)
+    pw = pointwise ? zeros(M.Cond.nSubj, 4) : zeros(0, 4)
+    pp = pointwise ? pointer(pw) : Ptr{Float64}(C_NULL)
+    GC.@preserve pw begin
+        if farmed
+            check(ccall((:erm_farm_get_marginal_loo, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.farm, nodes, out, pp))
+        else
+            check(ccall((:erm_get_marginal_loo, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.handle, nodes, out, pp))
+        end
+    end
+    return looTuple(out, pw)
+end
+
+"""
+    psisLoo(l; device = 0, weights = false) -> the named tuple of `getLooMarginal(...; pointwise = true)`[, lw]
+
+The same kernel on a saved table `l[i, s]` of pointwise log-likelihoods (unit i, row s; what `marginalLogLik` returns -- a conditional table serves as well), 25 .. 8192
+rows (`erm_psis_loo`).  `weights = true` adds `lw[i, s]`, the smoothed, normalised log-weights.
+"""
+function psisLoo(l::Matrix{Float64}; device::Integer = 0, weights::Bool = false)
+    N, S = size(l)
+    out, pw = zeros(12), zeros(N, 4)
+    lw = weights ? zeros(N, S) : zeros(0, 0)
+    GC.@preserve lw begin
+        check(ccall((:erm_psis_loo, LIB[]), Cint, (Cint, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    device, l, N, S, out, pw, weights ? pointer(lw) : Ptr{Float64}(C_NULL)))
+    end
+    res = looTuple(out, pw)
+    return weights ? merge(res, (lw = lw,)) : res
 end
 
 # score as erm_get_scores fills it (column-major [nSubj][7], the ERM_SCORE_* columns) and out4 -> a named tuple with the EAP reliabilities

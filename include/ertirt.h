@@ -303,6 +303,50 @@ int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4);
 int erm_score(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
               int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4);
 
+/* Marginal PSIS-LOO: Pareto-smoothed importance-sampling leave-one-subject-out (Vehtari, Gelman and Gabry 2017; Vehtari, Simpson, Gelman, Yao and Gabry 2024), the
+ * criterion the "p_u > 0.4" count of erm_get_waic / erm_get_marginal_waic sends its reader to, and with it a Pareto k^ per respondent: for which respondents the
+ * posterior would move if they were left out -- the aberrant or highly influential response / time patterns.  (ERM_SCORE_LIKELIHOOD importance-weights the rows with raw
+ * weights; this is the stabilised form of that idea, with a diagnostic.)  It sits on l_s = l_i^(s) of erm_get_marginal_waic, the marginal log-likelihood of subject i at
+ * row s, so it too is computed AFTER the run from resident state, in both trace modes, and the calls only read the engine.  Served and refused as erm_get_marginal_waic
+ * serves and refuses (the two quantile models: ERM_ERR_ARG).  Everything is fp64 whatever the engine's precision.  Relative efficiency is taken as 1, as the R
+ * package loo does when none is supplied.
+ * Definition, for one unit with the values l_s, s = 1..S, in trace order (an engine: the post-burn-in rows behind Post.mean; a farm: the chain-major table of
+ * erm_farm_get_marginal_waic).  Limits: 25 <= S <= 8192 (ERM_ERR_ARG, the message names the limit): the lower one gives M >= 5, the upper one is that of the sort in LDS
+ * (the cap of erm_get_rank_diagnostics).
+ *   1. log ratios   lw_s = -l_s - max_t(-l_t): the largest is 0.
+ *   2. order        ascending by (lw, position s): the position breaks ties (the sorting network of erm_get_rank_diagnostics).
+ *   3. tail         M = min(ceil(S / 5), ceil(3 sqrt(S))) in integers (ceil(3 sqrt(S)) = the smallest m with m^2 >= 9 S; the arms cross at S = 225); the tail is the M
+ *                   largest; the cutoff c = the sorted value number S - M (1-based), the largest outside the tail; exceedances x_i = exp(tail_i) - exp(c), i = 1..M, ascending.
+ *   4. fit          (Zhang and Stephens 2009)  G = 30 + floor(sqrt(M)),  x* = x[floor(M / 4 + 0.5)] (1-based),  b_j = 1 / x_M + (1 - sqrt(G / (j - 0.5))) / (3 x*), j = 1..G,
+ *                   k_j = mean_i log1p(-b_j x_i),  L_j = M (log(-b_j / k_j) - k_j - 1),  w_j = exp(L_j - LSE(L)),  b^ = sum_j b_j w_j,  k_raw = mean_i log1p(-b^ x_i),
+ *                   sigma = -k_raw / b^,  k^ = (M k_raw + 5) / (M + 10).  Sums over i run i = 1..M in order, sums over j run j = 1..G in order, LSE(L) = max + log sum exp(L_j - max).
+ *                   Unfittable tail: x* <= 0, or x_M - x_1 <= 0, or any of b^, sigma, k^ not finite: k^ = +Inf and the weights stay unsmoothed.
+ *   5. smoothing    p_i = (i - 1/2) / M,  tail_i <- min(0, log(exp(c) + sigma expm1(-k^ log1p(-p_i)) / k^)), at k^ = 0 the limit -sigma log1p(-p_i); assigned in sorted order.
+ *   6. per unit     with lw' the smoothed log ratios:  elpd_i = LSE_s(lw'_s + l_s) - LSE_s(lw'_s),  p_i = lppd_i - elpd_i with lppd_i = max l + log(sum_s exp(l_s - max l) / S)
+ *                   (erm_get_marginal_waic's lppd_i),  neff_i = (sum w)^2 / sum w^2 with w = exp(lw'),  k^_i.
+ *                   A sum over s is taken in the SORTED order of step 2: 256 partial sums (sorted value number p, 0-based, goes to partial p mod 256, in rising p), a
+ *                   binary tree over each run of 64 partials (partial q += partial q + 32, then + 16, ... + 1), the four runs added in order; each LSE about its maximum.
+ *   7. out12        { elpd_loo = sum_u elpd_u, p_loo = sum_u p_u, looic = -2 elpd_loo, se = 2 sqrt(U Var_u(elpd_u)) (U - 1 in the denominator, the squared deviations
+ *                   about the mean in a second pass: as se_waic), lppd = sum_u lppd_u, n_units, n_rows = S, #(k^ > 0.7) (Inf included), #(k^ > min(1 - 1 / log10(S), 0.7)),
+ *                   M, Q, number of coarse units }.  A sum over the units: 256 partial sums (unit u to partial u mod 256, in rising u), the same tree, the four runs in order.
+ * Nothing is atomic.  A unit's result depends on its own l_s only -- not on n_subj, the other units, the launch, the chunking or how many units share a workgroup
+ * (one wave carries a unit up to 2048 padded rows, two up to 4096, a workgroup beyond: the order of every sum is the same in all three).  Results are
+ * bit-reproducible from call to call.
+ * What k^ means: the estimated shape of the tail of unit i's importance ratios.  k^ <= min(1 - 1 / log10(S), 0.7): elpd_i is reliable.  Above: the posterior without
+ * respondent i differs from the full posterior by more than S rows can correct -- the respondent is influential or poorly described by the model; elpd_i is optimistic.
+ * erm_get_marginal_loo: out12 as above; pw, column-major [n_subj][4] with the columns ERM_LOO_*, may be NULL.  n_nodes as erm_get_marginal_waic.  l is produced by the
+ *   marginal WAIC's kernel into bounded device scratch -- the subjects go through in chunks of at most 256 MB of l (twice that is held: l and its transpose), then
+ *   the PSIS kernel runs on the chunk; ERM_ERR_NOMEM if the scratch cannot be had.  Refused: as erm_get_marginal_waic (a quantile model: ERM_ERR_ARG; a shard, no data
+ *   set, a failed run: ERM_ERR_STATE), and S outside 25 .. 8192 (ERM_ERR_ARG).
+ * erm_farm_get_marginal_loo (below): the same over the farm's chain-major table on chain 0's device; every chain must have recorded the same number of rows, at least one
+ *   of them post-burn-in (ERM_ERR_STATE, the message names the chain), S = all chains' post-burn-in rows.  A farm of one chain returns its engine's result bit for bit.
+ * erm_psis_loo: the same kernel on a caller-supplied l, column-major [n_subj][n_rows] (the subject fastest), exactly what erm_marginal_loglik returns; lw (may be NULL)
+ *   receives the smoothed, normalised log-weights lw' - LSE(lw') in the same layout.  Q and the coarse count are 0.  A NaN or an infinity in l: ERM_ERR_NONFINITE.
+ *   Serves saved log-likelihood tables, conditional ones included, and the tests. */
+enum { ERM_LOO_ELPD = 0, ERM_LOO_P = 1, ERM_LOO_KHAT = 2, ERM_LOO_NEFF = 3, ERM_LOO_COLS = 4 };
+int erm_get_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw);
+int erm_psis_loo(int device, const double* l, int64_t n_subj, int64_t n_rows, double* out12, double* pw, double* lw);
+
 /* Posterior predictive checks (Gelman, Meng and Stern 1996; Sinharay 2006; Glas and Meijer 2003; Marianti et al. 2014), drawn and accumulated on the device.  The
  * reference has no counterpart.  Post-burn-in row number k = 1, 2, ... (the rows behind Post.mean) is a REPLICATE row when (k - 1) mod thin = 0.  At a replicate
  * row the whole data set is drawn again from the model at the values of that row -- the law whose log-density is WAIC's cell term: y_rep ~ Bernoulli(p),
@@ -387,6 +431,7 @@ int erm_farm_get_mean(erm_farm_handle f, erm_state* out);
 int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Dbar over the rows of all chains, Dhat at the joint Post.mean (the same reduction as erm_farm_get_mean, evaluated on the first device) */
 int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* the marginal WAIC over the rows of all chains: see erm_get_marginal_waic */
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4);                          /* the scores over the rows of all chains: see erm_get_scores */
+int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* the marginal PSIS-LOO over the rows of all chains: see erm_get_marginal_loo */
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed);
 /* The farm's joint convergence diagnostics: the estimators of erm_get_diagnostics / erm_get_convergence / erm_get_rank_diagnostics / erm_get_rank_convergence, as
  * defined there, applied to the L = erm_farm_chains chains jointly -- chain l takes the place of interleaved chain l: M = 2 L sequences of
