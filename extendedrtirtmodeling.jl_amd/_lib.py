@@ -69,6 +69,7 @@ EXPORTS = [
     "erm_get_marginal_waic", "erm_farm_get_marginal_waic", "erm_marginal_loglik",
     "erm_get_scores", "erm_farm_get_scores", "erm_score",
     "erm_get_marginal_loo", "erm_farm_get_marginal_loo", "erm_psis_loo",
+    "erm_get_plausible_values", "erm_farm_get_plausible_values", "erm_plausible_values",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -216,6 +217,10 @@ def load():
     lib.erm_get_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
     lib.erm_farm_get_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
     lib.erm_psis_loo.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_get_plausible_values.argtypes = [H, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_plausible_values.argtypes = [H, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_plausible_values.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -287,6 +292,33 @@ def _score_call(fn, h, nodes, n_subj):
     score, out = np.empty((len(SCORE_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
     check(fn(h, marginal_nodes(nodes), score.ctypes.data, out.ctypes.data))
     return _score_result(score, out)
+
+
+# erm_get_plausible_values / erm_farm_get_plausible_values / erm_plausible_values: the number of draws, the seed, and the outputs
+PV_DRAWS, PV_DRAWS_MAX, PV_SEED, PV_SITE = 5, 4096, 20191, 16
+
+
+def pv_draws(K):
+    """The number of plausible values per subject as the library takes it: 1 .. 4096."""
+    if isinstance(K, bool) or K != int(K) or int(K) < 1 or int(K) > PV_DRAWS_MAX:
+        raise ValueError(f"K must be an integer in 1 .. {PV_DRAWS_MAX}")
+    return int(K)
+
+
+def pv_seed(seed):
+    """The seed of the draws: an integer in 0 .. 2^64 - 1 (the Philox key)."""
+    if isinstance(seed, bool) or seed != int(seed) or int(seed) < 0 or int(seed) >= 1 << 64:
+        raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+    return int(seed)
+
+
+def _pv_call(fn, n_subj, K, seed, *head):
+    """fn(*head, K, seed, pv, node, coarse, out4) -> a dict: theta, zeta (n_subj, K), node (n_subj, K), coarse (n_subj,) bool, nSubj, nRows, nNodes, nCoarse, seed."""
+    K, seed = pv_draws(K), pv_seed(seed)
+    pv, node = np.empty((2, K, n_subj), dtype=np.float64), np.empty((K, n_subj), dtype=np.int32)       # C-ordered = column-major [n_subj][K][2], [n_subj][K]
+    coarse, out = np.empty(n_subj, dtype=np.int32), np.empty(4, dtype=np.float64)
+    check(fn(*head, K, seed, pv.ctypes.data, node.ctypes.data, coarse.ctypes.data, out.ctypes.data))
+    return dict(theta=pv[0].T, zeta=pv[1].T, node=node.T, coarse=coarse != 0, nSubj=int(out[0]), nRows=int(out[1]), nNodes=int(out[2]), nCoarse=int(out[3]), seed=seed)
 
 
 # erm_get_marginal_loo / erm_farm_get_marginal_loo / erm_psis_loo: the columns of pw [n_subj][4] (ERM_LOO_*) and the limits of the rows per unit
@@ -546,6 +578,11 @@ class Engine(_Diagnostics):
         resident item trace after the run (equal weights).  A dict of SCORE_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
         return _score_call(self._lib.erm_get_scores, self._h, nodes, self.cfg.n_subj)
 
+    def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
+        """erm_get_plausible_values: K draws of every subject's (theta, zeta) from its posterior given the resident item trace, computed on the device after the run.
+        A dict: theta, zeta (n_subj, K), node (n_subj, K), coarse (n_subj,), nSubj, nRows, nNodes, nCoarse, seed."""
+        return _pv_call(self._lib.erm_get_plausible_values, self.cfg.n_subj, K, seed, self._h, marginal_nodes(nodes))
+
     # ---- posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     def set_predictive(self, on=True, thin=1):
         """Enable the replicate pass (every thin-th post-burn-in row is replicated) or turn it off; only while no trace row is recorded."""
@@ -704,6 +741,10 @@ class Farm(_Diagnostics):
         """erm_farm_get_scores: Engine.scores over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
         return _score_call(self._lib.erm_farm_get_scores, self._h, nodes, self.cfg.n_subj)
 
+    def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
+        """erm_farm_get_plausible_values: Engine.plausible_values over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
+        return _pv_call(self._lib.erm_farm_get_plausible_values, self.cfg.n_subj, K, seed, self._h, marginal_nodes(nodes))
+
     # ---- joint convergence diagnostics over all chains: _Diagnostics over erm_farm_get_*; engine(l).diagnostics(which) stays the diagnostic of chain l alone
     _diag_prefix = "erm_farm_get_"
 
@@ -786,6 +827,25 @@ def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", d
     check(load().erm_score(int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, rr.shape[0], marginal_nodes(nodes), score_weighting(weighting),
                            sc.ctypes.data, out.ctypes.data))
     return _score_result(sc, out)
+
+
+def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES, device=0):
+    """erm_plausible_values: the plausible values' kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
+    Engine.item_trace() returns them, R >= 1.  Returns Engine.plausible_values' dict."""
+    Yf = np.asfortranarray(np.asarray(Y).astype(np.uint8))
+    if Yf.ndim != 2:
+        raise ValueError("Y must be [subject, item]")
+    N, J = Yf.shape
+    lt = None if logT is None else np.asfortranarray(logT, dtype=np.float64)
+    xx = None if X is None or np.size(X) == 0 else np.asfortranarray(X, dtype=np.float64)
+    F = 0 if xx is None else xx.shape[1]
+    if (lt is not None and lt.shape != (N, J)) or (xx is not None and xx.shape[0] != N):
+        raise ValueError("logT / X do not match Y")
+    rr = np.ascontiguousarray(rows, dtype=np.float64)
+    if model in MODEL_TRAITS and (rr.ndim != 2 or rr.shape[1] != item_trace_width(model, J, F)):
+        raise ValueError(f"rows must be [row, {item_trace_width(model, J, F)}]")
+    ptr = lambda a: None if a is None else a.ctypes.data
+    return _pv_call(load().erm_plausible_values, N, K, seed, int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, rr.shape[0], marginal_nodes(nodes))
 
 
 def psis_loo(l, *, want_lw=False, device=0):

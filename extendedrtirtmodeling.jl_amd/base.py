@@ -172,6 +172,21 @@ class OutputScores:
                 f"relTheta={self.relTheta:.4f}, relZeta={self.relZeta:.4f})")
 
 
+class OutputPv:
+    """Plausible values of the respondents (getPlausibleValues / drawPlausibleValues; the reference has no counterpart): theta (N, K) and zeta (N, K), K draws per
+    subject from its posterior given the item trace (zeta is NaN for GibbsMlIrt); node (N, K), the rule's node behind every draw; coarse (N,), the theta rule was too
+    coarse for the subject at some row it used (raise nodes); nRows, nNodes, nCoarse and the seed of the draws.  Column k over the subjects is one imputed data set:
+    analyse each of the K and pool the results by Rubin's rules."""
+
+    def __init__(self, theta=None, zeta=None, node=None, coarse=None, nRows=None, nNodes=None, nCoarse=None, seed=None):
+        self.theta, self.zeta, self.node, self.coarse = theta, zeta, node, coarse
+        self.nRows, self.nNodes, self.nCoarse, self.seed = nRows, nNodes, nCoarse, seed
+
+    def __repr__(self):
+        shape = None if self.theta is None else np.shape(self.theta)
+        return f"OutputPv(shape={shape}, nRows={self.nRows}, nNodes={self.nNodes}, nCoarse={self.nCoarse}, seed={self.seed})"
+
+
 class OutputPpc:
     """Posterior predictive checks of a fit (getPpc / getPpcHost; the reference has no counterpart).  R = the number of replicated data sets; item (3, 4, nItem),
     subj (2, 4, nSubj), total (2, 4): components RA (response deviance), RT (response-time chi^2; NaN for GibbsMlIrt)[, SCORE (item score)] x

@@ -16,8 +16,10 @@
 //                  Each node's e_q enters the lane's (M, S); a fixed butterfly of marg_ms_merge joins the eight lanes.
 //   4. accumulate  l = M + log S goes through pw_update into the subject's PwAcc, which lives in registers from the first row to the last and is stored once.
 // The covariates of the subject stay in registers across the rows.  Plain vector loads and stores, no atomics: every output word has one writer.
-// Steps 1 to 3 are __device__ helpers (marg_stage, marg_load_x, marg_stage_law, marg_item_sums, marg_lane_nodes) that score_kernel (erm_score_kernels.hpp) calls too.
+// Steps 1 to 3 are __device__ helpers (marg_stage, marg_load_x, marg_stage_law, marg_item_sums, marg_lane_nodes) that score_kernel (erm_score_kernels.hpp) and
+// pv_kernel (erm_pv_kernels.hpp) call too.
 #pragma once
+#include <type_traits>
 #include "erm_marginal.hpp"
 #include "erm_pointwise.hpp"
 
@@ -102,7 +104,7 @@ __device__ __forceinline__ void marg_item_sums(const MargArgs& A, const double* 
         }
     }
 }
-// nodes: lane s, nodes s, s + 8, ... in chunks of MARG_CHUNK; sink(e_q, z_q) receives the lane's nodes in order
+// nodes: lane s, nodes s, s + 8, ... in chunks of MARG_CHUNK; sink(e_q, z_q) -- or sink(e_q, z_q, q) if it takes the node's index too -- receives the lane's nodes in order
 template <int MODEL, typename Sink>
 __device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, int s, double h, double log_h, const MargLaw& w, const MargSums& ms, double A1, double A0, Sink&& sink)
 {
@@ -126,7 +128,8 @@ __device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, 
                 const double z = marg_node(qq, h);
                 double e = marg_log_weight(z, log_h) + (th[c] * A1 - A0 - lse[c]);
                 if constexpr (MODEL != MLIRT) e += marg_T(ms, J, w, th[c]);
-                sink(e, z);
+                if constexpr (std::is_invocable_v<Sink, double, double, int>) sink(e, z, qq);
+                else sink(e, z);
             }
         }
     }

@@ -23,6 +23,7 @@
 #include "erm_marginal_kernels.hpp"        // marginal WAIC: theta and zeta integrated out, from the item trace
 #include "erm_psis_kernels.hpp"            // marginal PSIS-LOO: Pareto-smoothed leave-one-subject-out from marginal_kernel's l
 #include "erm_score_kernels.hpp"           // scores of respondents: posterior moments of theta and zeta, from the item trace
+#include "erm_pv_kernels.hpp"              // plausible values: draws of theta and zeta from each subject's posterior, from the item trace
 #include "erm_farm_diag.hpp"               // the chain farm's joint diagnostics: chunk arithmetic
 #include "erm_geometry.hpp"
 #include "erm_model.hpp"
@@ -209,32 +210,52 @@ static int marg_nodes(int32_t n_nodes, int* Q)
     if (!marg_nodes_ok(*Q)) return fail(ERM_ERR_ARG, "n_nodes must be 0 (= " + std::to_string(MARG_NODES_DEFAULT) + ") or odd and in " + std::to_string(MARG_NODES_MIN) + " .. " + std::to_string(MARG_NODES_MAX));
     return 0;
 }
+// what marginal_kernel, score_kernel and pv_kernel share of a launch: the arguments common to the three (the outputs are the caller's to set), the LDS of the row
+// double buffer, the grid of one tile per workgroup, the model's instantiation, and the subjects [c0, c0 + nc) of a data set as a data set of their own
+static MargArgs marg_args(const MargData& D, const double* rows, int64_t n_rows, int Q)
+{
+    MargArgs a{};
+    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = item_trace_width(D.model, D.J, D.Fk); a.N = D.N; a.J = D.J; a.F = D.Fk; a.Q = Q;
+    return a;
+}
+static size_t marg_lds(const MargArgs& a) { return (size_t)2 * marg_row_lds(a.ld, a.J) * sizeof(double); }
+static dim3 marg_grid(const MargArgs& a) { return dim3((unsigned)((a.N + MARG_TILE - 1) / MARG_TILE)); }
+template <typename Launch>
+static int marg_dispatch(int model, Launch&& launch)
+{
+    switch (model) {
+    case ERM_MODEL_MLIRT: return launch(std::integral_constant<int, MLIRT>{});
+    case ERM_MODEL_RTIRT: return launch(std::integral_constant<int, RTIRT>{});
+    case ERM_MODEL_NULL: return launch(std::integral_constant<int, NULLM>{});
+    case ERM_MODEL_CROSS: return launch(std::integral_constant<int, CROSS>{});
+    case ERM_MODEL_LATENT: return launch(std::integral_constant<int, LATENT>{});
+    default: return marg_refuse_model(model);
+    }
+}
+template <typename real>
+static MargData marg_chunk(const MargData& D, int64_t c0, int64_t nc)
+{
+    MargData Dc = D;
+    Dc.Y = D.Y + (size_t)c0 * D.J;
+    Dc.C = D.C ? static_cast<const char*>(D.C) + (size_t)c0 * D.J * sizeof(real) : nullptr;
+    Dc.X = D.X ? static_cast<const char*>(D.X) + (size_t)c0 * D.Fk * sizeof(real) : nullptr;
+    Dc.N = nc;
+    return Dc;
+}
 // one launch of marginal_kernel over the subjects of D and the table of rows, waited for: l_dev [n_rows][D.N], the accumulators and the flags [D.N], any of them NULL
 template <typename real>
 static int marginal_launch(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double2* acc_ms, double2* acc_w, unsigned int* coarse)
 {
-    const int64_t N = D.N, ld = item_trace_width(D.model, D.J, D.Fk);
-    MargArgs a{};
-    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = ld; a.N = N; a.J = D.J; a.F = D.Fk; a.Q = Q;
+    MargArgs a = marg_args(D, rows, n_rows, Q);
     a.l_out = l_dev; a.acc_ms = acc_ms; a.acc_w = acc_w; a.coarse = coarse;
-    const size_t lds = (size_t)2 * marg_row_lds(ld, D.J) * sizeof(double);
-    const dim3 grid((unsigned)((N + MARG_TILE - 1) / MARG_TILE));
+    const size_t lds = marg_lds(a);
     auto launch = [&](auto M) -> int {
         constexpr int MODEL = decltype(M)::value;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&marginal_kernel<MODEL, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((marginal_kernel<MODEL, real>), grid, dim3(256), lds, stream, a);
+        hipLaunchKernelGGL((marginal_kernel<MODEL, real>), marg_grid(a), dim3(256), lds, stream, a);
         return 0;
     };
-    int rc = 0;
-    switch (D.model) {
-    case ERM_MODEL_MLIRT: rc = launch(std::integral_constant<int, MLIRT>{}); break;
-    case ERM_MODEL_RTIRT: rc = launch(std::integral_constant<int, RTIRT>{}); break;
-    case ERM_MODEL_NULL: rc = launch(std::integral_constant<int, NULLM>{}); break;
-    case ERM_MODEL_CROSS: rc = launch(std::integral_constant<int, CROSS>{}); break;
-    case ERM_MODEL_LATENT: rc = launch(std::integral_constant<int, LATENT>{}); break;
-    default: return marg_refuse_model(D.model);
-    }
-    if (rc) return rc;
+    if (int rc = marg_dispatch(D.model, launch)) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));
     return 0;
@@ -284,35 +305,24 @@ static int score_run(const MargData& D, const double* rows, int64_t n_rows, int 
 {
     if (n_rows < 1) return fail(ERM_ERR_STATE, "the scores need at least one post-burn-in row");
     if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
-    const int64_t N = D.N, ld = item_trace_width(D.model, D.J, D.Fk);
+    const int64_t N = D.N;
     DevBuf dScore, dCoarse, dCnt;
     const char* what = "the scores";
     if (int rc = dScore.try_alloc((size_t)N * SCORE_COLS * sizeof(double), what)) return rc;
     if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
     if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
-    MargArgs a{};
-    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = ld; a.N = N; a.J = D.J; a.F = D.Fk; a.Q = Q;
+    MargArgs a = marg_args(D, rows, n_rows, Q);
     a.coarse = dCoarse.as<unsigned int>();
-    const size_t lds = (size_t)2 * marg_row_lds(ld, D.J) * sizeof(double);
-    const dim3 grid((unsigned)((N + MARG_TILE - 1) / MARG_TILE));
+    const size_t lds = marg_lds(a);
     auto launch = [&](auto M, auto W) -> int {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool WEIGHTED = decltype(W)::value;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&score_kernel<MODEL, real, WEIGHTED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((score_kernel<MODEL, real, WEIGHTED>), grid, dim3(256), lds, stream, a, dScore.as<double>());
+        hipLaunchKernelGGL((score_kernel<MODEL, real, WEIGHTED>), marg_grid(a), dim3(256), lds, stream, a, dScore.as<double>());
         return 0;
     };
     auto pick = [&](auto M) -> int { return weighting == SCORE_LIKELIHOOD ? launch(M, std::true_type{}) : launch(M, std::false_type{}); };
-    int rc = 0;
-    switch (D.model) {
-    case ERM_MODEL_MLIRT: rc = pick(std::integral_constant<int, MLIRT>{}); break;
-    case ERM_MODEL_RTIRT: rc = pick(std::integral_constant<int, RTIRT>{}); break;
-    case ERM_MODEL_NULL: rc = pick(std::integral_constant<int, NULLM>{}); break;
-    case ERM_MODEL_CROSS: rc = pick(std::integral_constant<int, CROSS>{}); break;
-    case ERM_MODEL_LATENT: rc = pick(std::integral_constant<int, LATENT>{}); break;
-    default: return marg_refuse_model(D.model);
-    }
-    if (rc) return rc;
+    if (int rc = marg_dispatch(D.model, pick)) return rc;
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
     HIPCHK(hipGetLastError());
@@ -321,6 +331,58 @@ static int score_run(const MargData& D, const double* rows, int64_t n_rows, int 
     HIPCHK(hipMemcpy(&nc, dCnt.p, sizeof(nc), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(score, dScore.p, (size_t)N * SCORE_COLS * sizeof(double), hipMemcpyDeviceToHost));
     if (out4) { out4[0] = (double)N; out4[1] = (double)n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
+    return 0;
+}
+
+// Plausible values (erm_pv_kernels.hpp; include/ertirt.h: erm_get_plausible_values): the one place that launches pv_kernel -- for an engine's resident data set and
+// item trace, for a farm's table of rows and for erm_plausible_values' caller-supplied data.  The subjects go through in chunks whose draws (two doubles and an int
+// each) fit 256 MB whatever K (ERM_PV_CHUNK: a chunk length in subjects, for the tests of the chunk tails); a chunk's draws are copied into the caller's host arrays
+// pv [N][K][2] and node [N][K] (may be NULL), column-major, before the next chunk runs.  coarse [N] (may be NULL) and out4 are the caller's host arrays too.
+template <typename real>
+static int pv_run(const MargData& D, const double* rows, int64_t n_rows, int Q, int64_t K, uint64_t seed, hipStream_t stream, double* pv, int32_t* node, int32_t* coarse, double* out4)
+{
+    if (n_rows < 1) return fail(ERM_ERR_STATE, "the plausible values need at least one post-burn-in row");
+    if (!pv_draws_ok(K)) return fail(ERM_ERR_ARG, "n_draws must be in " + std::to_string(PV_DRAWS_MIN) + " .. " + std::to_string(PV_DRAWS_MAX));
+    const int64_t N = D.N;
+    const int64_t per = K * (int64_t)(2 * sizeof(double) + sizeof(int));
+    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / per);
+    if (const char* e = getenv("ERM_PV_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk = std::min<int64_t>(chunk, v); }
+    chunk = std::min(chunk, N);
+    DevBuf dPv, dNode, dCoarse, dCnt;
+    const char* what = "the plausible values";
+    if (int rc = dPv.try_alloc((size_t)chunk * K * 2 * sizeof(double), what)) return rc;
+    if (node) if (int rc = dNode.try_alloc((size_t)chunk * K * sizeof(int), what)) return rc;
+    if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
+    if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
+    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+        const int64_t nc = std::min(chunk, N - c0);
+        MargArgs a = marg_args(marg_chunk<real>(D, c0, nc), rows, n_rows, Q);
+        a.coarse = dCoarse.as<unsigned int>() + c0;
+        const PvArgs p{(long long)K, (unsigned long long)seed, (long long)c0, dPv.as<double>(), dNode.as<int>()};
+        const size_t lds = marg_lds(a);
+        auto launch = [&](auto M) -> int {
+            constexpr int MODEL = decltype(M)::value;
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pv_kernel<MODEL, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((pv_kernel<MODEL, real>), marg_grid(a), dim3(256), lds, stream, a, p);
+            return 0;
+        };
+        if (int rc = marg_dispatch(D.model, launch)) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipMemcpy2D(pv + c0, (size_t)N * sizeof(double), dPv.p, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), (size_t)(2 * K), hipMemcpyDeviceToHost));
+        if (node) HIPCHK(hipMemcpy2D(node + c0, (size_t)N * sizeof(int), dNode.p, (size_t)nc * sizeof(int), (size_t)nc * sizeof(int), (size_t)K, hipMemcpyDeviceToHost));
+    }
+    hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    unsigned long long n_coarse = 0;
+    HIPCHK(hipMemcpy(&n_coarse, dCnt.p, sizeof(n_coarse), hipMemcpyDeviceToHost));
+    if (coarse) {
+        std::vector<unsigned int> flag((size_t)N);
+        HIPCHK(hipMemcpy(flag.data(), dCoarse.p, flag.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < N; ++i) coarse[i] = (int32_t)flag[(size_t)i];
+    }
+    if (out4) { out4[0] = (double)N; out4[1] = (double)n_rows; out4[2] = (double)Q; out4[3] = (double)n_coarse; }
     return 0;
 }
 
@@ -389,12 +451,7 @@ static int marginal_loo_run(const MargData& D, const double* rows, int64_t n_row
     if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), "the marginal LOO's flags")) return rc;
     if (int rc = dCnt.try_alloc(sizeof(unsigned long long), "the marginal LOO's flags")) return rc;
     auto fill = [&](int64_t c0, int64_t nc, double* dst) -> int {
-        MargData Dc = D;
-        Dc.Y = D.Y + (size_t)c0 * D.J;
-        Dc.C = D.C ? static_cast<const char*>(D.C) + (size_t)c0 * D.J * sizeof(real) : nullptr;
-        Dc.X = D.X ? static_cast<const char*>(D.X) + (size_t)c0 * D.Fk * sizeof(real) : nullptr;
-        Dc.N = nc;
-        return marginal_launch<real>(Dc, rows, n_rows, Q, stream, dst, nullptr, nullptr, dCoarse.as<unsigned int>() + c0);
+        return marginal_launch<real>(marg_chunk<real>(D, c0, nc), rows, n_rows, Q, stream, dst, nullptr, nullptr, dCoarse.as<unsigned int>() + c0);
     };
     double s8[8];
     if (int rc = psis_run(N, n_rows, stream, fill, [](int64_t, int64_t, const double*) { return 0; }, false, s8, pw)) return rc;
@@ -435,6 +492,8 @@ struct EngineBase {
     virtual int marginal_loo(int Q, const double* rows, int64_t n_rows, double* out12, double* pw) = 0;
     // scores of respondents (erm_get_scores; rows as for marginal_waic), equal weights
     virtual int scores(int Q, const double* rows, int64_t n_rows, double* score, double* out4) = 0;
+    // plausible values (erm_get_plausible_values; rows as for marginal_waic)
+    virtual int plausible_values(int Q, const double* rows, int64_t n_rows, int64_t K, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4) = 0;
     // posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     virtual int set_predictive(int on, int32_t thin) = 0;
     virtual int64_t predictive_reps() const = 0;
@@ -1041,6 +1100,20 @@ template <typename real> struct Engine : EngineBase {
         HIPCHK(hipSetDevice(cfg.device));
         const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
         return score_run<real>(D, rows, n_rows, Q, SCORE_EQUAL, stream, score, out4);
+    }
+    // ---- plausible values: as the scores, from the resident data set and item-trace rows; one post-burn-in row is enough
+    int plausible_values(int Q, const double* rows, int64_t n_rows, int64_t K, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4) override {
+        if (int rc = marg_refuse_model(cfg.model)) return rc;
+        if (sharded()) return fail(ERM_ERR_STATE, "the plausible values are not available on a shard (every subject's data must be resident on one device)");
+        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
+        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
+        if (!rows) {
+            if (post_rows < 1) return fail(ERM_ERR_STATE, "the plausible values need at least one post-burn-in row");
+            rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows;
+        }
+        HIPCHK(hipSetDevice(cfg.device));
+        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
+        return pv_run<real>(D, rows, n_rows, Q, K, seed, stream, pv, node, coarse, out4);
     }
     int get_pointwise(double* lppd_u, double* p_u) override {
         if (int rc = pw_ready()) return rc;
@@ -2039,6 +2112,21 @@ int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4)
     if (int rc = marg_nodes(n_nodes, &Q)) return rc;
     return h->e->scores(Q, nullptr, 0, score, out4);
 }
+// what the three plausible-value entries check before anything else: the outputs, the node count, the number of draws
+static int pv_entry_args(int32_t n_nodes, int32_t n_draws, const double* pv, int* Q)
+{
+    if (!pv) return fail(ERM_ERR_ARG, "out is NULL");
+    if (int rc = marg_nodes(n_nodes, Q)) return rc;
+    if (!pv_draws_ok(n_draws)) return fail(ERM_ERR_ARG, "n_draws must be in " + std::to_string(PV_DRAWS_MIN) + " .. " + std::to_string(PV_DRAWS_MAX));
+    return 0;
+}
+int erm_get_plausible_values(erm_handle h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
+{
+    CHK_H;
+    int Q = 0;
+    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
+    return h->e->plausible_values(Q, nullptr, 0, n_draws, seed, pv, node, coarse, out4);
+}
 int erm_set_predictive(erm_handle h, int on, int32_t thin) { CHK_H; return h->e->set_predictive(on, thin); }
 int64_t erm_predictive_reps(erm_handle h) { return h ? h->e->predictive_reps() : -1; }
 int erm_get_predictive(erm_handle h, double* item, double* subj, double* total) { CHK_H; return h->e->get_predictive(item, subj, total); }
@@ -2312,6 +2400,18 @@ int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, doubl
     if (int rc = farm_row_table(f, 1, "the scores need at least one post-burn-in row", dTab, &n_rows)) return rc;
     return f->eng[0]->e->scores(Q, dTab.as<double>(), n_rows, score, out4);
 }
+// The farm's plausible values: the same table, the same device.
+int erm_farm_get_plausible_values(erm_farm_handle f, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
+{
+    CHK_F;
+    int Q = 0;
+    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
+    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
+    DevBuf dTab;
+    int64_t n_rows = 0;
+    if (int rc = farm_row_table(f, 1, "the plausible values need at least one post-burn-in row", dTab, &n_rows)) return rc;
+    return f->eng[0]->e->plausible_values(Q, dTab.as<double>(), n_rows, n_draws, seed, pv, node, coarse, out4);
+}
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed)
 {
     CHK_F;
@@ -2431,6 +2531,17 @@ int erm_score(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_f
     MargUpload U;
     if (int rc = marg_upload("erm_score's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", U)) return rc;
     return score_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, weighting, nullptr, score, out4);
+}
+
+int erm_plausible_values(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                         int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
+{
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
+    MargUpload U;
+    if (int rc = marg_upload("erm_plausible_values' inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", U)) return rc;
+    return pv_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, n_draws, seed, nullptr, pv, node, coarse, out4);
 }
 
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out)

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import InputPara, OutputDic, OutputLoo, OutputPpc, OutputScores, OutputWaic, SimConditions
+from .base import InputPara, OutputDic, OutputLoo, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions
 
 _PREC = {"f32": _lib.PREC_F32, "f64": _lib.PREC_F64}
 _TRACE = {"summary": _lib.TRACE_SUMMARY, "full": _lib.TRACE_FULL}
@@ -880,6 +880,99 @@ def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="eq
                         zetaSd=np.sqrt(np.maximum(mean(Vz) + mean((Ez - ze) ** 2), 0.0)) if rt else nan, cov=mean(Cz) + mean((E - th) * (Ez - ze)) if rt else nan,
                         rowEss=W * W / np.sum(om * om, axis=0), coarse=coarse, nRows=E.shape[0], nNodes=Q, nCoarse=int(np.sum(coarse)),
                         weighting="likelihood" if wt else "equal")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Plausible values (include/ertirt.h: erm_get_plausible_values).  K draws of every subject's (theta, zeta) from its posterior given the item-level
+# trace: draw k reads row r_k, picks a node of the marginal WAIC's rule by Gumbel-max on Philox stream 16, spreads theta over the node's cell and shrinks it back to
+# the row's mean and variance, and draws zeta from its Gaussian conditional.
+# ------------------------------------------------------------------------------------------------------------------
+def _pv_output(r) -> OutputPv:
+    return OutputPv(theta=r["theta"], zeta=r["zeta"], node=r["node"], coarse=r["coarse"], nRows=r["nRows"], nNodes=r["nNodes"], nCoarse=r["nCoarse"], seed=r["seed"])
+
+
+def getPlausibleValues(MCMC: _GibbsBase, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES) -> OutputPv:
+    """K plausible values per subject of the last sample! -- of one engine or of the chain farm of sample!(...; devices=) -- drawn on the device from the resident
+    item trace and data set (erm_get_plausible_values / erm_farm_get_plausible_values), in either trace mode: theta, zeta (N, K), node, coarse.  Draws from the
+    posterior getScores summarises: at every row a draw has the mean and the variance getScores reports there.  The same (K, seed, nodes) gives the same draws."""
+    Q = _marginal_check(MCMC, nodes, "getPlausibleValues")
+    K, seed = _lib.pv_draws(K), _lib.pv_seed(seed)
+    return _pv_output(_marginal_source(MCMC, "getPlausibleValues").plausible_values(K, seed, Q))
+
+
+def drawPlausibleValues(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES, device=0) -> OutputPv:
+    """Plausible values of respondents -- new ones, or those of a run that is no longer resident -- against saved item-trace rows [R, item_trace_width]
+    (Engine.item_trace()), on the device (erm_plausible_values).  model: the model code (_lib.MODEL_*); Y, logT [N, J], X [N, F] or None; every row counts once."""
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("drawPlausibleValues serves the five models without quantile weights")
+    Q, K, seed = _lib.marginal_nodes(nodes), _lib.pv_draws(K), _lib.pv_seed(seed)
+    return _pv_output(_lib.plausible_values(model, Y, logT, X, rows, K=K, seed=seed, nodes=Q, device=device))
+
+
+def pvRow(k, K, n_rows):
+    """The row of draw k: ((2 k + 1) n_rows) // (2 K) (pv_row of csrc/erm_pv.hpp)."""
+    return ((2 * np.asarray(k, dtype=np.int64) + 1) * np.int64(n_rows)) // np.int64(2 * K)
+
+
+def pvGumbel(w):
+    """The Gumbel variate of a 32-bit word: -log(-log((w + 1/2) 2^-32)) (pv_gumbel)."""
+    return -np.log(-np.log(_ppc_uniform(np.asarray(w, dtype=np.uint64))))
+
+
+def pvFinish(E, V, mu, sd, c0, c1, u, q, h, w0, w1, w2):
+    """(theta, zeta) of a draw at node q of a row with moments E, V, law (mu, sd) and zeta conditional (c0, c1, u), from the finishing block's words (pv_finish)."""
+    cell = sd * h
+    star = (mu + sd * (-6.0 + q * h)) + cell * (_ppc_uniform(w0) - 0.5)
+    c = np.where(V > 0.0, np.sqrt(V / (V + cell * cell / 12.0)), 0.0)
+    theta = E + c * (star - E)
+    return theta, (c0 + c1 * theta) + np.sqrt(u) * _ppc_normal(w1, w2)
+
+
+def plausibleValuesHost(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES, i_base=0, with_gap=False, with_rows=False):
+    """drawPlausibleValues with numpy (the test twin of pv_kernel), written beside scoresHost on _marginal_rows_host and _philox4x32_10.  i_base: the data-set index
+    of Y's first subject.  with_gap=True also returns, per draw, the difference of the two largest keys (N, K): a draw whose gap is below the rounding of e_q is
+    undecidable between two implementations.  with_rows=True also returns the rows r_k (K,) and the row moments E, V (N, K) each draw was made from."""
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("plausibleValuesHost serves the five models without quantile weights")
+    Q, K, seed = _lib.marginal_nodes(nodes), _lib.pv_draws(K), _lib.pv_seed(seed)
+    rt = _lib.MODEL_TRAITS[model].rt
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    rk = pvRow(np.arange(K), K, rows.shape[0])
+    used = np.unique(rk)
+    N = np.shape(Y)[0]
+    h = 12.0 / (Q - 1)
+    ii = (np.arange(N, dtype=np.uint64) + np.uint64(i_base))
+    site = _ppc_stream_word3(0, _lib.PV_SITE)
+    theta, zeta, node, gap = np.empty((N, K)), np.full((N, K), np.nan), np.empty((N, K), dtype=np.int32), np.empty((N, K))
+    Ek, Vk = np.empty((N, K)), np.empty((N, K))
+    coarse = np.zeros(N, dtype=bool)
+    for r, (e, z, (mu, sd, m0, m1, v), sums) in zip(used, _marginal_rows_host(model, Y, logT, X, rows[used], Q)):
+        M = np.max(e, axis=1, keepdims=True)
+        p = np.exp(e - M)
+        s = np.sum(p, axis=1)
+        w = p / s[:, None]
+        Z1, Z2 = w @ z, w @ (z * z)
+        E, V = mu + sd * Z1, np.maximum(sd * sd * (Z2 - Z1 * Z1), 0.0)
+        c0, c1, u = 0.0, 0.0, 0.0
+        if rt:
+            P, R0, R1 = sums
+            c0, c1, u = (m0 + v * R0) / (1 + v * P), (m1 - v * R1) / (1 + v * P), v / (1 + v * P)
+        coarse |= s < 2.0
+        ks = np.nonzero(rk == r)[0]
+        w0 = _philox4x32_10(ii[:, None, None], ks[None, :, None], np.arange(Q)[None, None, :], site, seed, seed >> 32)[0]      # (N, draws, Q)
+        key = e[:, None, :] + pvGumbel(w0)
+        q = np.argmax(key, axis=2)                                                                                           # the first of equal keys: the smaller q
+        top = np.sort(key, axis=2)
+        f0, f1, f2, _ = _philox4x32_10(ii[:, None], ks[None, :], 0xFFFFFFFF, site, seed, seed >> 32)                        # (N, draws)
+        col = lambda a: a[:, None] if np.ndim(a) else a
+        th, ze = pvFinish(col(E), col(V), col(mu), sd, col(c0), col(c1), u, q, h, f0, f1, f2)
+        theta[:, ks], node[:, ks], gap[:, ks] = th, q, top[:, :, -1] - top[:, :, -2]
+        Ek[:, ks], Vk[:, ks] = col(E), col(V)
+        if rt:
+            zeta[:, ks] = ze
+    out = OutputPv(theta=theta, zeta=zeta, node=node, coarse=coarse, nRows=rows.shape[0], nNodes=Q, nCoarse=int(np.sum(coarse)), seed=seed)
+    extra = ((gap,) if with_gap else ()) + ((rk, Ek, Vk),) * bool(with_rows)
+    return (out, *extra) if extra else out
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getScores, scoreRespondents, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getScores, scoreRespondents, getPlausibleValues, drawPlausibleValues, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -497,6 +497,52 @@ function scoreRespondents(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64
                 (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
                 device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, w, score, out))
     return scoresTuple(score, out)
+end
+
+# pv as erm_get_plausible_values fills it (column-major [nSubj][K][2]), node [nSubj][K], coarse [nSubj] and out4 -> a named tuple
+pvTuple(pv::Array{Float64,3}, node::Matrix{Int32}, coarse::Vector{Int32}, out::Vector{Float64}, seed::UInt64) =
+    (theta = pv[:, :, 1], zeta = pv[:, :, 2], node = node, coarse = coarse .!= 0, nRows = Int(out[2]), nNodes = Int(out[3]), nCoarse = Int(out[4]), seed = seed)
+
+"""
+    getPlausibleValues(MCMC; K = 5, seed = 20191, nodes = 61) -> (theta, zeta, node, coarse, nRows, nNodes, nCoarse, seed)
+
+`K` plausible values per subject of the last `sample!`: draws of (θ_i, ζ_i) from each subject's posterior given the resident item-level trace, computed on the device in
+either trace mode (`erm_get_plausible_values`; after `sample!(MCMC; devices=...)` over the rows of all chains, `erm_farm_get_plausible_values`).  `theta` and `zeta` are
+nSubj x K (ζ is NaN for GibbsMlIrt): column k is one imputed data set.  Draws from the posterior `getScores` summarises; the same (K, seed, nodes) gives the same
+draws.  Not for the two quantile models.
+"""
+function getPlausibleValues(M::GibbsAMD; K::Integer = 5, seed::Integer = 20191, nodes::Integer = 61)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    1 <= K <= 4096 || error("K must be in 1 .. 4096")
+    N = M.Cond.nSubj
+    pv, node, coarse, out = zeros(N, K, 2), zeros(Int32, N, K), zeros(Int32, N), zeros(4)
+    if farmed
+        check(ccall((:erm_farm_get_plausible_values, LIB[]), Cint, (Ptr{Cvoid}, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                    M.farm, nodes, K, seed, pv, node, coarse, out))
+    else
+        check(ccall((:erm_get_plausible_values, LIB[]), Cint, (Ptr{Cvoid}, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                    M.handle, nodes, K, seed, pv, node, coarse, out))
+    end
+    return pvTuple(pv, node, coarse, out, UInt64(seed))
+end
+
+"""
+    drawPlausibleValues(model, Y, logT, X, rows; K = 5, seed = 20191, nodes = 61, device = 0)
+
+`getPlausibleValues` for caller-supplied respondents (`Y` UInt8 nSubj x nItem, `logT`, `X` nSubj x nFeat) against saved item-trace rows (`rows` is
+item_trace_width x nRows, as `marginalLogLik` takes them), on the device (`erm_plausible_values`); every row counts once.
+"""
+function drawPlausibleValues(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}; K::Integer = 5, seed::Integer = 20191,
+                             nodes::Integer = 61, device::Integer = 0)
+    N, J = size(Y)
+    1 <= K <= 4096 || error("K must be in 1 .. 4096")
+    pv, node, coarse, out = zeros(N, K, 2), zeros(Int32, N, K), zeros(Int32, N), zeros(4)
+    check(ccall((:erm_plausible_values, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
+                 Ptr{Float64}),
+                device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, K, seed, pv, node, coarse, out))
+    return pvTuple(pv, node, coarse, out, UInt64(seed))
 end
 
 """

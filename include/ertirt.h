@@ -303,6 +303,46 @@ int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4);
 int erm_score(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
               int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4);
 
+/* Plausible values: K draws of (theta_i, zeta_i) from every subject's posterior, the input of a secondary analysis (a regression of ability on covariates, a population
+ * variance, a comparison of groups: Mislevy 1991; large-scale assessments publish five per student), from the item-level trace alone.  erm_get_scores gives a point and
+ * a standard error; these are draws from the same posterior -- at every row the draw has exactly the mean E_s and the variance V_s (and, for zeta, Ez_s, Vz_s and the
+ * covariance C_s) that erm_get_scores reports, with the shape of the rule's posterior, not a Gaussian's.  The traces cannot supply them: ERM_TRACE_SUMMARY keeps no
+ * theta or zeta draw, the draws ERM_TRACE_FULL keeps are not draws from the joint model for the response-time models (see erm_get_scores: the sampler's conditionals
+ * ignore Sigma_p[1,2]), and a new respondent scored against a saved posterior has no chain.  Computed AFTER the run from resident state, in both trace modes; the calls
+ * only read the engine.  Served and refused as erm_get_scores.
+ * Definition, for subject i, draw k = 0..K-1, over a table of n_rows item-trace rows (an engine: its post-burn-in rows; a farm: the chain-major table of
+ * erm_farm_get_marginal_waic), equal weights:
+ *   1. row      r_k = ((2 k + 1) n_rows) / (2 K) in 64-bit integer division: evenly spaced and rising with k, distinct when K <= n_rows, each row m times when K = m n_rows.
+ *   2. the rule at row r_k: exactly erm_get_marginal_waic's -- the same population law, item sums, nodes z_q, theta_q and e_q, q = 0..Q-1 -- and from them the row's
+ *               M, S, E, V of erm_get_scores and its zeta conditional (c0, c1, u).
+ *   3. node     Gumbel-max: key_q = e_q + g_q,  g_q = -log(-log u(w)),  u(w) = (w + 1/2) 2^-32,  w = word 0 of the Philox4x32-10 block with key = seed and
+ *               ctr = { i, k, q, 16 << 24 } (stream site 16; the chain bits are zero).  The chosen node q* has the largest key; of equal keys the smaller q wins.  This
+ *               picks q with probability w_q = exp(e_q - M) / S, and the maximum is associative: the choice does not depend on how the nodes are dealt to lanes.
+ *               The 32-bit uniform bounds g at about 22.9 (and at -3.13 below): a node whose weight is below e^-26 of the largest can never be chosen.
+ *   4. theta    one more block at ctr = { i, k, 0xFFFFFFFF, 16 << 24 } with words w0, w1, w2:  theta* = theta_q* + sd h (u(w0) - 1/2), uniform within the node's cell.
+ *               That adds sd^2 h^2 / 12 to the row's variance, so it is taken out:  c = sqrt(V / (V + sd^2 h^2 / 12)), c = 0 when V = 0;  theta = E + c (theta* - E).
+ *   5. zeta     zeta = c0 + c1 theta + sqrt(u) n,  n = sqrt(-2 log u(w1)) cos(2 pi u(w2)).  GibbsMlIrt has no zeta: its block is NaN.
+ *   6. coarse   a subject is coarse if S < 2 at some row it used (the marginal WAIC's rule, over the rows r_k only).
+ * Everything is fp64 whatever the engine's precision.  i is the subject's index within the call's data set.  A subject's draws depend on its own data, the rows, Q, K,
+ * seed and i only -- not on n_subj, the other subjects, the launch or the chunking, nor on whether draws that share a row share one node pass; nothing is atomic;
+ * results are bit-reproducible from call to call and do not depend on how the sweeps were split into erm_run calls.
+ * Output: pv, column-major [n_subj][K][2]: the theta block [n_subj][K] first, the zeta block second.  node (may be NULL), int32 column-major [n_subj][K]: q*, for the
+ *   tests and to show where a coarse rule put its mass.  coarse (may be NULL), int32 [n_subj]: 1 for a coarse subject, else 0.  out4 (may be NULL) = { n_subj, n_rows, Q,
+ *   number of coarse subjects }.  1 <= n_draws <= 4096, else ERM_ERR_ARG; n_nodes as erm_get_marginal_waic.  The draws pass through bounded device scratch: the subjects
+ *   go through in chunks of at most 256 MB of draws (ERM_PV_CHUNK in the environment caps the chunk length in subjects: no result changes by a bit); ERM_ERR_NOMEM if
+ *   the scratch cannot be had.
+ * erm_get_plausible_values: the post-burn-in rows of the resident item trace, read in place.  Refused as erm_get_scores refuses (a quantile model: ERM_ERR_ARG; a shard,
+ *   no data set, a failed run, no post-burn-in row: ERM_ERR_STATE); ONE post-burn-in row is enough.  erm_farm_get_plausible_values (below): the same over the farm's
+ *   chain-major table on chain 0's device; a farm of one chain returns its engine's result bit for bit.
+ * erm_plausible_values: the same kernel on caller-supplied data and rows, validated as erm_score validates them (a NaN: ERM_ERR_NONFINITE; a bad row: ERM_ERR_ARG, the
+ *   message names the row); n_rows >= 1.
+ * Out of scope: likelihood weighting of the rows (ERM_SCORE_LIKELIHOOD's weights would need a resampling pass over the rows before the draws), the two quantile models,
+ * and subject-sharded engines. */
+enum { ERM_PV_DRAWS_DEFAULT = 5, ERM_PV_DRAWS_MAX = 4096 };
+int erm_get_plausible_values(erm_handle h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4);
+int erm_plausible_values(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                         int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4);
+
 /* Marginal PSIS-LOO: Pareto-smoothed importance-sampling leave-one-subject-out (Vehtari, Gelman and Gabry 2017; Vehtari, Simpson, Gelman, Yao and Gabry 2024), the
  * criterion the "p_u > 0.4" count of erm_get_waic / erm_get_marginal_waic sends its reader to, and with it a Pareto k^ per respondent: for which respondents the
  * posterior would move if they were left out -- the aberrant or highly influential response / time patterns.  (ERM_SCORE_LIKELIHOOD importance-weights the rows with raw
@@ -432,6 +472,7 @@ int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Db
 int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* the marginal WAIC over the rows of all chains: see erm_get_marginal_waic */
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4);                          /* the scores over the rows of all chains: see erm_get_scores */
 int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* the marginal PSIS-LOO over the rows of all chains: see erm_get_marginal_loo */
+int erm_farm_get_plausible_values(erm_farm_handle f, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4);   /* plausible values over the rows of all chains: see erm_get_plausible_values */
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed);
 /* The farm's joint convergence diagnostics: the estimators of erm_get_diagnostics / erm_get_convergence / erm_get_rank_diagnostics / erm_get_rank_convergence, as
  * defined there, applied to the L = erm_farm_chains chains jointly -- chain l takes the place of interleaved chain l: M = 2 L sequences of
