@@ -370,8 +370,8 @@ def state_struct(arrays: dict):
 
 class _Diagnostics:
     """The four convergence queries of an Engine (erm_get_*: its own interleaved chains) and of a Farm (erm_farm_get_*: its chains jointly, M = 2 * n_chains split
-    sequences, computed on chain 0's device).  One implementation, keyed by the symbol prefix `_diag_prefix`; `_diag_width(which)` is the trace's width."""
-    _diag_prefix = "erm_get_"
+    sequences, computed on chain 0's device).  One implementation, keyed by the symbol prefix `_get_prefix`; `_diag_width(which)` is the trace's width."""
+    _get_prefix = "erm_get_"
 
     def _diag_width(self, which: int):
         return int(self._lib.erm_trace_width(self._h, which))
@@ -379,12 +379,12 @@ class _Diagnostics:
     def _diag_vectors(self, name: str, which: int, n: int):
         w = max(self._diag_width(which), 0)
         out = tuple(np.empty(w) for _ in range(n))
-        check(getattr(self._lib, self._diag_prefix + name)(self._h, which, *(v.ctypes.data for v in out)))
+        check(getattr(self._lib, self._get_prefix + name)(self._h, which, *(v.ctypes.data for v in out)))
         return out
 
     def _diag_counts(self, name: str, which: int, n: int):
         c = np.zeros(n, dtype=np.int64)
-        check(getattr(self._lib, self._diag_prefix + name)(self._h, which, c.ctypes.data))
+        check(getattr(self._lib, self._get_prefix + name)(self._h, which, c.ctypes.data))
         return tuple(int(v) for v in c)
 
     def diagnostics(self, which: int):
@@ -407,7 +407,35 @@ class _Diagnostics:
         return self._diag_counts("rank_convergence", which, 6)
 
 
-class Engine(_Diagnostics):
+class _ItemPasses:
+    """The four passes over the item trace of an Engine (erm_get_*: its resident data set and its own post-burn-in rows) and of a Farm (erm_farm_get_*: the
+    post-burn-in rows of all chains -- chain 0's, then chain 1's, ... -- on chain 0's device and data set).  One implementation, keyed by `_get_prefix`."""
+
+    def _pass(self, name: str):
+        return getattr(self._lib, self._get_prefix + name)
+
+    def marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_get_marginal_waic / erm_farm_get_marginal_waic: WAIC with every subject's theta and zeta integrated out, computed on the device from the resident
+        item trace after the run.  The totals (erm_get_waic's, with nNodes and nCoarse); with pointwise=True (totals, lppd_i, p_i)."""
+        return _marginal_call(self._pass("marginal_waic"), self._h, nodes, self.cfg.n_subj, pointwise)
+
+    def marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_get_marginal_loo / erm_farm_get_marginal_loo: Pareto-smoothed leave-one-subject-out on the marginal log-likelihoods, computed on the device from the
+        resident item trace after the run.  Returns a dict of out12; pointwise=True adds elpd_u, p_u, khat, nEff [n_subj]."""
+        return _loo_call(self._pass("marginal_loo"), self._h, nodes, self.cfg.n_subj, pointwise)
+
+    def scores(self, nodes=MARGINAL_NODES):
+        """erm_get_scores / erm_farm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on
+        the device from the resident item trace after the run (equal weights).  A dict of SCORE_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
+        return _score_call(self._pass("scores"), self._h, nodes, self.cfg.n_subj)
+
+    def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
+        """erm_get_plausible_values / erm_farm_get_plausible_values: K draws of every subject's (theta, zeta) from its posterior given the resident item trace,
+        computed on the device after the run.  A dict: theta, zeta (n_subj, K), node (n_subj, K), coarse (n_subj,), nSubj, nRows, nNodes, nCoarse, seed."""
+        return _pv_call(self._pass("plausible_values"), self.cfg.n_subj, K, seed, self._h, marginal_nodes(nodes))
+
+
+class Engine(_Diagnostics, _ItemPasses):
     """Thin RAII wrapper over an erm_handle."""
 
     def __init__(self, **kw):
@@ -563,26 +591,6 @@ class Engine(_Diagnostics):
             return lppd.reshape(sh, order="F"), p.reshape(sh, order="F")
         return lppd, p
 
-    def marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
-        """erm_get_marginal_waic: WAIC with every subject's theta and zeta integrated out, computed on the device from the resident item trace after the run.
-        The totals (erm_get_waic's, with nNodes and nCoarse); with pointwise=True (totals, lppd_i, p_i)."""
-        return _marginal_call(self._lib.erm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
-
-    def marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
-        """erm_get_marginal_loo: Pareto-smoothed leave-one-subject-out on the marginal log-likelihoods, computed on the device from the resident item trace after the
-        run.  Returns a dict of out12; pointwise=True adds elpd_u, p_u, khat, nEff [n_subj]."""
-        return _loo_call(self._lib.erm_get_marginal_loo, self._h, nodes, self.cfg.n_subj, pointwise)
-
-    def scores(self, nodes=MARGINAL_NODES):
-        """erm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on the device from the
-        resident item trace after the run (equal weights).  A dict of SCORE_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
-        return _score_call(self._lib.erm_get_scores, self._h, nodes, self.cfg.n_subj)
-
-    def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
-        """erm_get_plausible_values: K draws of every subject's (theta, zeta) from its posterior given the resident item trace, computed on the device after the run.
-        A dict: theta, zeta (n_subj, K), node (n_subj, K), coarse (n_subj,), nSubj, nRows, nNodes, nCoarse, seed."""
-        return _pv_call(self._lib.erm_get_plausible_values, self.cfg.n_subj, K, seed, self._h, marginal_nodes(nodes))
-
     # ---- posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     def set_predictive(self, on=True, thin=1):
         """Enable the replicate pass (every thin-th post-burn-in row is replicated) or turn it off; only while no trace row is recorded."""
@@ -639,7 +647,7 @@ class _Borrowed(Engine):
         self._h = None
 
 
-class Farm(_Diagnostics):
+class Farm(_Diagnostics, _ItemPasses):
     """erm_farm_*: nChain independent chains, chain l on device devices[l] (include/ertirt.h).  The chains sample concurrently on host
     threads of the library; get_mean() is the one collective (RCCL all-reduce over the devices)."""
 
@@ -729,24 +737,9 @@ class Farm(_Diagnostics):
         check(self._lib.erm_farm_get_dic(self._h, out.ctypes.data))
         return dict(Dbar=float(out[0]), Dhat=float(out[1]), pD=float(out[2]), DIC=float(out[3]))
 
-    def marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
-        """erm_farm_get_marginal_waic: Engine.marginal_waic over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
-        return _marginal_call(self._lib.erm_farm_get_marginal_waic, self._h, nodes, self.cfg.n_subj, pointwise)
-
-    def marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
-        """erm_farm_get_marginal_loo: Engine.marginal_loo over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
-        return _loo_call(self._lib.erm_farm_get_marginal_loo, self._h, nodes, self.cfg.n_subj, pointwise)
-
-    def scores(self, nodes=MARGINAL_NODES):
-        """erm_farm_get_scores: Engine.scores over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
-        return _score_call(self._lib.erm_farm_get_scores, self._h, nodes, self.cfg.n_subj)
-
-    def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
-        """erm_farm_get_plausible_values: Engine.plausible_values over the post-burn-in rows of all chains (chain 0's, then chain 1's, ...), on chain 0's device."""
-        return _pv_call(self._lib.erm_farm_get_plausible_values, self.cfg.n_subj, K, seed, self._h, marginal_nodes(nodes))
-
-    # ---- joint convergence diagnostics over all chains: _Diagnostics over erm_farm_get_*; engine(l).diagnostics(which) stays the diagnostic of chain l alone
-    _diag_prefix = "erm_farm_get_"
+    # ---- joint convergence diagnostics and item-trace passes over all chains: _Diagnostics and _ItemPasses over erm_farm_get_*; engine(l).diagnostics(which)
+    # stays the diagnostic of chain l alone
+    _get_prefix = "erm_farm_get_"
 
     def _diag_width(self, which: int):
         return int(self._lib.erm_trace_width(self._lib.erm_farm_engine(self._h, 0), which))
@@ -778,11 +771,10 @@ class Farm(_Diagnostics):
         return out
 
 
-def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
-    """erm_marginal_loglik: the marginal WAIC's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
-    Engine.item_trace() returns them.  Returns a dict: l [N, R] (every l_i^(s)), and -- with want_waic, which needs R >= 2 -- totals, lppd [N], p [N]."""
-    Ya = np.asarray(Y)
-    Yf = np.asfortranarray(Ya.astype(np.uint8))
+def _caller_data(model, Y, logT, X, rows):
+    """Caller-supplied data and rows as erm_marginal_loglik / erm_score / erm_plausible_values take them: (Y uint8 [N, J], logT [N, J] or None, X [N, F] or None --
+    column-major --, rows [R, item_trace_width] row-major) and (N, J, F, R)."""
+    Yf = np.asfortranarray(np.asarray(Y).astype(np.uint8))
     if Yf.ndim != 2:
         raise ValueError("Y must be [subject, item]")
     N, J = Yf.shape
@@ -794,13 +786,24 @@ def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=Tru
     rr = np.ascontiguousarray(rows, dtype=np.float64)
     if model in MODEL_TRAITS and (rr.ndim != 2 or rr.shape[1] != item_trace_width(model, J, F)):
         raise ValueError(f"rows must be [row, {item_trace_width(model, J, F)}]")
-    R = rr.shape[0]
+    return (Yf, lt, xx, rr), (N, J, F, rr.shape[0])
+
+
+def _caller_head(device, model, arrays, dims):
+    """The leading arguments of the three entries: device, model, N, J, F, Y, logT, X, rows, R (the arrays stay the caller's to keep alive)."""
+    N, J, F, R = dims
+    return (int(device), int(model), N, J, F, *(None if a is None else a.ctypes.data for a in arrays), R)
+
+
+def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
+    """erm_marginal_loglik: the marginal WAIC's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
+    Engine.item_trace() returns them.  Returns a dict: l [N, R] (every l_i^(s)), and -- with want_waic, which needs R >= 2 -- totals, lppd [N], p [N]."""
+    arrays, (N, J, F, R) = _caller_data(model, Y, logT, X, rows)
     l = np.empty((N, R), dtype=np.float64, order="F") if want_l else None
     out = np.empty(10, dtype=np.float64) if want_waic else None
     lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
     ptr = lambda a: None if a is None else a.ctypes.data
-    check(load().erm_marginal_loglik(int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, R, marginal_nodes(nodes),
-                                     ptr(l), ptr(out), ptr(lppd), ptr(p)))
+    check(load().erm_marginal_loglik(*_caller_head(device, model, arrays, (N, J, F, R)), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
     res = dict(l=l)
     if want_waic:
         res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
@@ -810,42 +813,18 @@ def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=Tru
 def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", device=0):
     """erm_score: the scores' kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as Engine.item_trace()
     returns them, R >= 1; weighting "equal" | "likelihood".  Returns Engine.scores' dict."""
-    Yf = np.asfortranarray(np.asarray(Y).astype(np.uint8))
-    if Yf.ndim != 2:
-        raise ValueError("Y must be [subject, item]")
-    N, J = Yf.shape
-    lt = None if logT is None else np.asfortranarray(logT, dtype=np.float64)
-    xx = None if X is None or np.size(X) == 0 else np.asfortranarray(X, dtype=np.float64)
-    F = 0 if xx is None else xx.shape[1]
-    if (lt is not None and lt.shape != (N, J)) or (xx is not None and xx.shape[0] != N):
-        raise ValueError("logT / X do not match Y")
-    rr = np.ascontiguousarray(rows, dtype=np.float64)
-    if model in MODEL_TRAITS and (rr.ndim != 2 or rr.shape[1] != item_trace_width(model, J, F)):
-        raise ValueError(f"rows must be [row, {item_trace_width(model, J, F)}]")
+    arrays, dims = _caller_data(model, Y, logT, X, rows)
+    N = dims[0]
     sc, out = np.empty((len(SCORE_COLUMNS), N), dtype=np.float64), np.empty(4, dtype=np.float64)
-    ptr = lambda a: None if a is None else a.ctypes.data
-    check(load().erm_score(int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, rr.shape[0], marginal_nodes(nodes), score_weighting(weighting),
-                           sc.ctypes.data, out.ctypes.data))
+    check(load().erm_score(*_caller_head(device, model, arrays, dims), marginal_nodes(nodes), score_weighting(weighting), sc.ctypes.data, out.ctypes.data))
     return _score_result(sc, out)
 
 
 def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES, device=0):
     """erm_plausible_values: the plausible values' kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
     Engine.item_trace() returns them, R >= 1.  Returns Engine.plausible_values' dict."""
-    Yf = np.asfortranarray(np.asarray(Y).astype(np.uint8))
-    if Yf.ndim != 2:
-        raise ValueError("Y must be [subject, item]")
-    N, J = Yf.shape
-    lt = None if logT is None else np.asfortranarray(logT, dtype=np.float64)
-    xx = None if X is None or np.size(X) == 0 else np.asfortranarray(X, dtype=np.float64)
-    F = 0 if xx is None else xx.shape[1]
-    if (lt is not None and lt.shape != (N, J)) or (xx is not None and xx.shape[0] != N):
-        raise ValueError("logT / X do not match Y")
-    rr = np.ascontiguousarray(rows, dtype=np.float64)
-    if model in MODEL_TRAITS and (rr.ndim != 2 or rr.shape[1] != item_trace_width(model, J, F)):
-        raise ValueError(f"rows must be [row, {item_trace_width(model, J, F)}]")
-    ptr = lambda a: None if a is None else a.ctypes.data
-    return _pv_call(load().erm_plausible_values, N, K, seed, int(device), int(model), N, J, F, Yf.ctypes.data, ptr(lt), ptr(xx), rr.ctypes.data, rr.shape[0], marginal_nodes(nodes))
+    arrays, dims = _caller_data(model, Y, logT, X, rows)
+    return _pv_call(load().erm_plausible_values, dims[0], K, seed, *_caller_head(device, model, arrays, dims), marginal_nodes(nodes))
 
 
 def psis_loo(l, *, want_lw=False, device=0):

@@ -1,0 +1,394 @@
+// erm_item_pass.hpp -- the host path of the passes that run after sampling from a data set and a table of item-trace rows: the marginal WAIC, the
+// marginal PSIS-LOO, the scores and the plausible values.  Each of erm_get_* / erm_farm_get_* (four each) and erm_marginal_loglik / erm_score / erm_plausible_values
+// is its own argument checks, ONE source maker (item_source) and ONE product call (item_waic / item_loo / item_scores / item_pv).
+//
+// The first half is plain C++: the facts of a pass as one table, the refusals built from it and the chunk rule; g++ compiles this half with
+// -fsanitize=undefined -ftrapv into tests/item_pass_check (tests/test_item_pass_host.py).
+// The second half (hipcc only) is what the tile kernels share of a launch, the coarse flags, the resolved source with its three makers and the four products.
+// ertirt.hip includes this header where its DevBuf, fail / HIPCHK, pw_totals / pw_finish_on, EngineBase and the two handles are in scope.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+
+namespace erm {
+
+enum ItemPass { PASS_WAIC = 0, PASS_LOO, PASS_SCORES, PASS_PV, N_ITEM_PASSES };
+// noun: the pass as its refusals name it; engine_rows: the fewest post-burn-in rows an engine must hold (0: the pass has limits of its own -- PSIS-LOO's
+// 25 .. 8192); farm_rows: the fewest every chain of a farm must hold; need: what the refusal of too few rows asks for
+struct ItemPassFacts { const char* noun; bool plural; int engine_rows, farm_rows; const char* need; };
+constexpr ItemPassFacts ITEM_PASSES[N_ITEM_PASSES] = {
+    { "the marginal WAIC",    false, 2, 2, "at least two post-burn-in rows" },
+    { "the marginal LOO",     false, 0, 1, "post-burn-in rows (25 .. 8192 over the chains)" },
+    { "the scores",           true,  1, 1, "at least one post-burn-in row" },
+    { "the plausible values", true,  1, 1, "at least one post-burn-in row" },
+};
+inline std::string item_pass_on_shard(int pass)
+{
+    const ItemPassFacts& p = ITEM_PASSES[pass];
+    return std::string(p.noun) + (p.plural ? " are" : " is") + " not available on a shard (every subject's data must be resident on one device)";
+}
+// too few rows: an engine's own (engine_rows > 0) and a farm chain's ("chain l: " in front)
+inline std::string item_pass_needs_rows(int pass)
+{
+    const ItemPassFacts& p = ITEM_PASSES[pass];
+    return std::string(p.noun) + (p.plural ? " need " : " needs ") + p.need;
+}
+
+// The subjects of a pass go through in chunks whose per-chunk device buffers fit 256 MB whatever a subject costs; cap > 0: a shorter chunk (the callers'
+// ERM_PV_CHUNK / ERM_PSIS_CHUNK, for the tests of the chunk tails)
+inline int64_t item_pass_chunk(int64_t bytes_per_subject, int64_t N, int64_t cap)
+{
+    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / bytes_per_subject);
+    if (cap > 0) chunk = std::min(chunk, cap);
+    return std::min(chunk, N);
+}
+
+}  // namespace erm
+
+#ifdef __HIPCC__
+namespace {      // (as ertirt.hip's own: EngineBase names ItemSource)
+
+// ---- what marginal_kernel, score_kernel and pv_kernel share of a launch.  Everything a launch is given lives on the current device.
+// a data set as the kernels read it: row-major, C and X in the element type of `elem` bytes (float or double)
+struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; size_t elem; };
+static int marg_refuse_model(int model)
+{
+    if (model == ERM_MODEL_CROSSQR || model == ERM_MODEL_LATENTQR)
+        return fail(ERM_ERR_ARG, "the marginal WAIC serves the five models without quantile weights: with nu integrated out the response-time term is no longer "
+                                 "Gaussian in zeta and the zeta integral has no closed form");
+    if (!marg_served(model)) return fail(ERM_ERR_ARG, "unknown model");
+    return 0;
+}
+static int marg_nodes(int32_t n_nodes, int* Q)
+{
+    *Q = n_nodes == 0 ? MARG_NODES_DEFAULT : n_nodes;
+    if (!marg_nodes_ok(*Q)) return fail(ERM_ERR_ARG, "n_nodes must be 0 (= " + std::to_string(MARG_NODES_DEFAULT) + ") or odd and in " + std::to_string(MARG_NODES_MIN) + " .. " + std::to_string(MARG_NODES_MAX));
+    return 0;
+}
+// the arguments common to the three kernels (the outputs are the caller's to set), the LDS of the row double buffer, the grid of one tile per workgroup, the
+// instantiation for the data set's model and element type -- launch(model constant, real()) --, and the subjects [c0, c0 + nc) of a data set as a data set of their own
+static MargArgs marg_args(const MargData& D, const double* rows, int64_t n_rows, int Q)
+{
+    MargArgs a{};
+    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = item_trace_width(D.model, D.J, D.Fk); a.N = D.N; a.J = D.J; a.F = D.Fk; a.Q = Q;
+    return a;
+}
+static size_t marg_lds(const MargArgs& a) { return (size_t)2 * marg_row_lds(a.ld, a.J) * sizeof(double); }
+static dim3 marg_grid(const MargArgs& a) { return dim3((unsigned)((a.N + MARG_TILE - 1) / MARG_TILE)); }
+template <typename Launch>
+static int marg_dispatch(const MargData& D, Launch&& launch)
+{
+    auto of = [&](auto M) -> int { return D.elem == sizeof(float) ? launch(M, float()) : launch(M, double()); };
+    switch (D.model) {
+    case ERM_MODEL_MLIRT: return of(std::integral_constant<int, MLIRT>{});
+    case ERM_MODEL_RTIRT: return of(std::integral_constant<int, RTIRT>{});
+    case ERM_MODEL_NULL: return of(std::integral_constant<int, NULLM>{});
+    case ERM_MODEL_CROSS: return of(std::integral_constant<int, CROSS>{});
+    case ERM_MODEL_LATENT: return of(std::integral_constant<int, LATENT>{});
+    default: return marg_refuse_model(D.model);
+    }
+}
+static MargData marg_chunk(const MargData& D, int64_t c0, int64_t nc)
+{
+    MargData Dc = D;
+    Dc.Y = D.Y + (size_t)c0 * D.J;
+    Dc.C = D.C ? static_cast<const char*>(D.C) + (size_t)c0 * D.J * D.elem : nullptr;
+    Dc.X = D.X ? static_cast<const char*>(D.X) + (size_t)c0 * D.Fk * D.elem : nullptr;
+    Dc.N = nc;
+    return Dc;
+}
+// one launch of a tile kernel with the arguments a (and the kernel's own), waited for
+template <typename... P, typename... A>
+static int marg_tile_launch(void (*kernel)(P...), const MargArgs& a, hipStream_t stream, const A&... own)
+{
+    const size_t lds = marg_lds(a);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, marg_grid(a), dim3(256), lds, stream, a, own...);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+// one launch of marginal_kernel over the subjects of D and the table of rows: l_dev [n_rows][D.N], the accumulators and the flags [D.N], any of them NULL
+static int marginal_launch(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double2* acc_ms, double2* acc_w, unsigned int* coarse)
+{
+    MargArgs a = marg_args(D, rows, n_rows, Q);
+    a.l_out = l_dev; a.acc_ms = acc_ms; a.acc_w = acc_w; a.coarse = coarse;
+    return marg_dispatch(D, [&](auto M, auto real) { return marg_tile_launch(&marginal_kernel<decltype(M)::value, decltype(real)>, a, stream); });
+}
+
+// The coarse flags of a pass: flags()[i] = 1 if subject i's grid was too coarse at any row, written by the tile kernels (a chunk's at flags() + c0), and their
+// count (marginal_count_kernel).  Not allocated: flags() is NULL, which the kernels take for "no flags".
+struct CoarseFlags {
+    DevBuf dFlag, dCnt; int64_t N = 0;
+    int alloc(int64_t n, const char* what) {
+        N = n;
+        if (int rc = dFlag.try_alloc((size_t)n * sizeof(unsigned int), what)) return rc;
+        return dCnt.try_alloc(sizeof(unsigned long long), what);
+    }
+    unsigned int* flags() const { return dFlag.as<unsigned int>(); }
+    int count(hipStream_t stream, unsigned long long* n) const {
+        hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, flags(), (long long)N, dCnt.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipMemcpy(n, dCnt.p, sizeof(*n), hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
+// ---- PSIS-LOO (erm_psis_kernels.hpp): the one place that launches psis_kernel -- for item_loo's l, which marginal_kernel writes chunk by chunk, and for
+// erm_psis_loo's caller-supplied table.  The subjects go through in chunks (item_pass_chunk; ERM_PSIS_CHUNK caps the chunk length); fill(c0, nc, dst) puts l of the
+// subjects [c0, c0 + nc) into dst as [S][nc], and take(c0, nc, src), if wanted, receives their smoothed log-weights in the same layout.
+static int psis_rows_ok(int64_t S)
+{
+    if (S < PSIS_MIN_ROWS) return fail(ERM_ERR_ARG, "PSIS-LOO needs at least " + std::to_string(PSIS_MIN_ROWS) + " rows per unit (" + std::to_string(S) + " given): fewer leave a tail of less than 5 values");
+    if (S > PSIS_MAX_ROWS) return fail(ERM_ERR_ARG, "PSIS-LOO takes at most " + std::to_string(PSIS_MAX_ROWS) + " rows per unit (" + std::to_string(S) + " given): a unit's rows are sorted in LDS");
+    return 0;
+}
+static int64_t item_chunk_cap(const char* name) { const char* e = getenv(name); return e ? atoll(e) : 0; }
+template <typename Fill, typename Take>
+static int psis_run(int64_t N, int64_t S, hipStream_t stream, Fill&& fill, Take&& take, bool want_lw, double* out8, double* pw)
+{
+    const int P = rk_pad((int)S);
+    const int64_t chunk = item_pass_chunk(S * (int64_t)sizeof(double), N, item_chunk_cap("ERM_PSIS_CHUNK"));
+    DevBuf dL, dXs, dPw, dOut;
+    if (int rc = dL.try_alloc((size_t)chunk * S * sizeof(double), "PSIS-LOO's log-likelihoods")) return rc;
+    if (int rc = dXs.try_alloc((size_t)chunk * S * sizeof(double), "PSIS-LOO's staged log-likelihoods")) return rc;
+    if (int rc = dPw.try_alloc((size_t)N * PSIS_DEV_COLS * sizeof(double), "PSIS-LOO's pointwise table")) return rc;
+    if (int rc = dOut.try_alloc(8 * sizeof(double), "PSIS-LOO's totals")) return rc;
+    const int tps = P <= 2048 ? 64 : P <= 4096 ? 128 : 256, ns = 256 / tps;
+    const size_t lds = (size_t)ns * P * 10;
+    const void* kern = tps == 64 ? reinterpret_cast<const void*>(&psis_kernel<64>) : tps == 128 ? reinterpret_cast<const void*>(&psis_kernel<128>) : reinterpret_cast<const void*>(&psis_kernel<256>);
+    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+        const int64_t nc = std::min(chunk, N - c0);
+        if (int rc = fill(c0, nc, dL.as<double>())) return rc;
+        hipLaunchKernelGGL(psis_transpose_kernel, dim3((unsigned)((nc + 31) / 32), (unsigned)((S + 31) / 32)), dim3(256), 0, stream, dL.as<double>(), (long long)S, (long long)nc, dXs.as<double>());
+        PsisArgs a{};
+        a.xs = dXs.as<double>(); a.n = nc; a.S = (int)S; a.P = P; a.pw = dPw.as<double>(); a.n_all = N; a.c0 = c0; a.want_lw = want_lw ? 1 : 0;
+        const dim3 grid((unsigned)((nc + ns - 1) / ns));
+        if (tps == 64) hipLaunchKernelGGL(psis_kernel<64>, grid, dim3(256), lds, stream, a);
+        else if (tps == 128) hipLaunchKernelGGL(psis_kernel<128>, grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL(psis_kernel<256>, grid, dim3(256), lds, stream, a);
+        if (want_lw) hipLaunchKernelGGL(psis_transpose_kernel, dim3((unsigned)((S + 31) / 32), (unsigned)((nc + 31) / 32)), dim3(256), 0, stream, dXs.as<double>(), (long long)nc, (long long)S, dL.as<double>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        if (want_lw) if (int rc = take(c0, nc, dL.as<double>())) return rc;
+    }
+    hipLaunchKernelGGL(psis_totals_kernel, dim3(1), dim3(256), 0, stream, dPw.as<double>(), (long long)N, psis_k_threshold(S), dOut.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(out8, dOut.p, 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (pw) HIPCHK(hipMemcpy(pw, dPw.p, (size_t)N * PSIS_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+// out12 from psis_totals_kernel's sums
+static void psis_out12(const double* s8, int64_t N, int64_t S, int Q, int64_t n_coarse, double* out12)
+{
+    const double U = (double)N, var_u = N > 1 ? s8[3] / (U - 1.0) : 0.0;
+    out12[0] = s8[0]; out12[1] = s8[1]; out12[2] = -2.0 * s8[0]; out12[3] = 2.0 * std::sqrt(U * var_u); out12[4] = s8[2]; out12[5] = U; out12[6] = (double)S;
+    out12[7] = s8[4]; out12[8] = s8[5]; out12[9] = (double)psis_tail_len(S); out12[10] = (double)Q; out12[11] = (double)n_coarse;
+}
+
+// ---- The resolved source of a pass: a data set and a table of n_rows item-trace rows on the current device, the stream the kernels run on, and the device
+// buffers the source owns (caller data: all four; a farm: its table of rows; an engine: none, everything is read in place).
+struct ItemSource {
+    MargData D{}; const double* rows = nullptr; int64_t n_rows = 0; hipStream_t stream = nullptr;
+    DevBuf dY, dC, dX, dRows;
+};
+// an engine's resident data set and its own post-burn-in rows, read in place (EngineBase::item_source: the refusals of a shard, a poisoned state, no data set and
+// too few rows, in this order, after the model's)
+static int item_source(erm_handle h, int pass, ItemSource& S)
+{
+    if (int rc = marg_refuse_model(h->e->cfg.model)) return rc;
+    return h->e->item_source(pass, S);
+}
+// a farm's: the post-burn-in item-trace rows of chain 0, chain 1, ... as ONE table on chain 0's device, whose resident data set supplies the data.  A chain's rows
+// cross through the host whatever its device (item-level: a few hundred kilobytes); a farm of one chain takes the same path as several.
+static int item_source(erm_farm_handle f, int pass, ItemSource& S)
+{
+    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
+    const int L = (int)f->eng.size();
+    const EngineBase* e0 = f->eng[0]->e.get();
+    const int64_t wi = e0->item_trace_width(), rows = e0->rows_done, post = e0->post_rows;
+    for (int l = 0; l < L; ++l) {
+        const EngineBase* e = f->eng[l]->e.get();
+        if (e->rows_done != rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + std::to_string(e->rows_done) + " rows recorded where chain 0 has " + std::to_string(rows));
+        if (e->post_rows < ITEM_PASSES[pass].farm_rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + item_pass_needs_rows(pass));
+    }
+    std::vector<double> table((size_t)L * post * wi);
+    for (int l = 0; l < L; ++l) {
+        const EngineBase* e = f->eng[l]->e.get();
+        HIPCHK(hipSetDevice(f->dev[l]));
+        HIPCHK(hipStreamSynchronize(e->work_stream()));
+        HIPCHK(hipMemcpy(table.data() + (size_t)l * post * wi, e->item_trace_dev() + (size_t)(rows - post) * wi, (size_t)post * wi * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipSetDevice(f->dev[0]));
+    if (int rc = S.dRows.try_alloc(table.size() * sizeof(double), "the farm's table of item-trace rows")) return rc;
+    H2D(S.dRows.p, table.data(), table.size() * sizeof(double));
+    S.rows = S.dRows.as<double>(); S.n_rows = (int64_t)L * post;
+    return item_source(f->eng[0].get(), pass, S);
+}
+// caller-supplied data and rows (erm_marginal_loglik, erm_score, erm_plausible_values): validated on the host, then uploaded to `device` row-major in fp64, as the
+// kernels read an engine's, for the NULL stream.  min_rows / rows_msg: the fewest rows the caller's outputs need.
+static int item_source(const char* what, int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
+                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, ItemSource& S)
+{
+    const ModelTraits mt = model_traits(model);
+    if (n_subj <= 0 || n_subj >= (1LL << 32) || n_item <= 0 || n_item > 896 || n_feat < 0 || n_feat > MARG_MAXF) return fail(ERM_ERR_ARG, "n_subj, n_item (1 .. 896) or n_feat (0 .. " + std::to_string(MARG_MAXF) + ") out of range");
+    const int64_t N = n_subj; const int J = n_item, Fk = kernel_feat(model, n_feat);
+    if (!Y || !rows) return fail(ERM_ERR_ARG, "Y / rows is NULL");
+    if (mt.rt && !logT) return fail(ERM_ERR_ARG, "logT is required for response-time models");
+    if (Fk > 0 && !X) return fail(ERM_ERR_ARG, "X is required when n_feat > 0");
+    if (n_rows < min_rows) return fail(ERM_ERR_ARG, rows_msg);
+    const int64_t wi = item_trace_width(model, J, Fk);
+    const size_t NJ = (size_t)N * J;
+    // ---- the inputs: a NaN anywhere, then rows outside the model's domain
+    for (size_t e = 0; e < (size_t)n_rows * wi; ++e) if (rows[e] != rows[e]) return fail(ERM_ERR_NONFINITE, "NaN in row " + std::to_string(e / (size_t)wi));
+    if (mt.rt) for (size_t e = 0; e < NJ; ++e) if (logT[e] != logT[e]) return fail(ERM_ERR_NONFINITE, "NaN in logT");
+    for (size_t e = 0; e < (size_t)N * Fk; ++e) if (X[e] != X[e]) return fail(ERM_ERR_NONFINITE, "NaN in X");
+    for (size_t e = 0; e < NJ; ++e) if (Y[e] > 1) return fail(ERM_ERR_ARG, "Y must be 0/1");
+    if (mt.rt) for (int64_t r = 0; r < n_rows; ++r) {
+        const double* row = rows + (size_t)r * wi;
+        for (int j = 0; j < J; ++j) if (!(row[3 * J + j] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": sig2t must be positive");
+        const double* Sp = row + 4 * J + qr_sigp_off(model, J, Fk);
+        if (!(Sp[0] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": Sigma_p[1,1] must be positive");
+        if (marg_law(model, 0.0, 0.0, 0.0, Sp).v < 0.0) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": the conditional variance of zeta given theta is negative (Sigma_p is not positive semi-definite)");
+    }
+    HIPCHK(hipSetDevice(device));
+    // ---- upload: the data set row-major in fp64, as the kernel reads an engine's
+    {
+        std::vector<uint8_t> y(NJ);
+        cols_to_rows(Y, y.data(), N, (int64_t)J);
+        if (int rc = S.dY.try_alloc(NJ, what)) return rc;
+        H2D(S.dY.p, y.data(), NJ);
+    }
+    if (mt.rt) {
+        std::vector<double> c(NJ);
+        cols_to_rows(logT, c.data(), N, (int64_t)J);
+        if (int rc = S.dC.try_alloc(NJ * sizeof(double), what)) return rc;
+        H2D(S.dC.p, c.data(), NJ * sizeof(double));
+    }
+    if (Fk > 0) {
+        std::vector<double> x((size_t)N * Fk);
+        cols_to_rows(X, x.data(), N, (int64_t)Fk);
+        if (int rc = S.dX.try_alloc(x.size() * sizeof(double), what)) return rc;
+        H2D(S.dX.p, x.data(), x.size() * sizeof(double));
+    }
+    if (int rc = S.dRows.try_alloc((size_t)n_rows * wi * sizeof(double), what)) return rc;
+    H2D(S.dRows.p, rows, (size_t)n_rows * wi * sizeof(double));
+    S.D = MargData{S.dY.as<uint8_t>(), S.dC.p, S.dX.p, nullptr, N, J, Fk, model, sizeof(double)};
+    S.rows = S.dRows.as<double>(); S.n_rows = n_rows;
+    return 0;
+}
+
+// ---- The four products of a source.  The makers have refused a source with too few rows for the outputs asked for; all outputs are the caller's host arrays.
+// Marginal WAIC (erm_marginal_kernels.hpp; include/ertirt.h: erm_get_marginal_waic, erm_marginal_loglik): l [n_rows][N] (may be NULL), and the totals out10 with
+// lppd_u / p_u [N] (all three NULL: l alone)
+static int item_waic(const ItemSource& S, int Q, double* l, double* out10, double* lppd_u, double* p_u)
+{
+    const bool totals = out10 || lppd_u || p_u;
+    const int64_t N = S.D.N;
+    DevBuf dMs, dW, dL, dP, dLik;
+    CoarseFlags coarse;
+    const char* what = "the marginal WAIC's accumulators";
+    if (l) if (int rc = dLik.try_alloc((size_t)N * S.n_rows * sizeof(double), "erm_marginal_loglik's output")) return rc;
+    if (totals) {
+        if (int rc = dMs.try_alloc((size_t)N * sizeof(double2), what)) return rc;
+        if (int rc = dW.try_alloc((size_t)N * sizeof(double2), what)) return rc;
+        if (int rc = coarse.alloc(N, what)) return rc;
+        if (lppd_u) if (int rc = dL.try_alloc((size_t)N * sizeof(double), what)) return rc;
+        if (p_u) if (int rc = dP.try_alloc((size_t)N * sizeof(double), what)) return rc;
+    }
+    if (int rc = marginal_launch(S.D, S.rows, S.n_rows, Q, S.stream, dLik.as<double>(), dMs.as<double2>(), dW.as<double2>(), coarse.flags())) return rc;
+    if (l) HIPCHK(hipMemcpy(l, dLik.p, (size_t)N * S.n_rows * sizeof(double), hipMemcpyDeviceToHost));
+    if (!totals) return 0;
+    double out8[8], sums[PW_FIN_COLS];
+    if (int rc = pw_totals(dMs.as<double2>(), dW.as<double2>(), N, S.n_rows, S.stream, out8)) return rc;
+    if (lppd_u || p_u) {
+        if (int rc = pw_finish_on(dMs.as<double2>(), dW.as<double2>(), N, S.n_rows, 0.0, dL.as<double>(), dP.as<double>(), S.stream, sums)) return rc;
+        if (lppd_u) HIPCHK(hipMemcpy(lppd_u, dL.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+        if (p_u) HIPCHK(hipMemcpy(p_u, dP.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (out10) {
+        unsigned long long nc = 0;
+        if (int rc = coarse.count(S.stream, &nc)) return rc;
+        for (int k = 0; k < 8; ++k) out10[k] = out8[k];
+        out10[8] = (double)Q; out10[9] = (double)nc;
+    }
+    return 0;
+}
+// Marginal PSIS-LOO (include/ertirt.h: erm_get_marginal_loo): psis_run on l of every chunk from marginal_kernel; 25 .. 8192 rows
+static int item_loo(const ItemSource& S, int Q, double* out12, double* pw)
+{
+    if (int rc = psis_rows_ok(S.n_rows)) return rc;
+    const int64_t N = S.D.N;
+    CoarseFlags coarse;
+    if (int rc = coarse.alloc(N, "the marginal LOO's flags")) return rc;
+    auto fill = [&](int64_t c0, int64_t nc, double* dst) -> int {
+        return marginal_launch(marg_chunk(S.D, c0, nc), S.rows, S.n_rows, Q, S.stream, dst, nullptr, nullptr, coarse.flags() + c0);
+    };
+    double s8[8];
+    if (int rc = psis_run(N, S.n_rows, S.stream, fill, [](int64_t, int64_t, const double*) { return 0; }, false, s8, pw)) return rc;
+    unsigned long long nc = 0;
+    if (int rc = coarse.count(S.stream, &nc)) return rc;
+    psis_out12(s8, N, S.n_rows, Q, (int64_t)nc, out12);
+    return 0;
+}
+// Scores of respondents (erm_score_kernels.hpp; include/ertirt.h: erm_get_scores, erm_score): the one place that launches score_kernel; score [N][7]
+static int item_scores(const ItemSource& S, int Q, int weighting, double* score, double* out4)
+{
+    const int64_t N = S.D.N;
+    DevBuf dScore;
+    CoarseFlags coarse;
+    const char* what = "the scores";
+    if (int rc = dScore.try_alloc((size_t)N * SCORE_COLS * sizeof(double), what)) return rc;
+    if (int rc = coarse.alloc(N, what)) return rc;
+    MargArgs a = marg_args(S.D, S.rows, S.n_rows, Q);
+    a.coarse = coarse.flags();
+    auto launch = [&](auto M, auto real) -> int {
+        if (weighting == SCORE_LIKELIHOOD) return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), true>, a, S.stream, dScore.as<double>());
+        return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), false>, a, S.stream, dScore.as<double>());
+    };
+    if (int rc = marg_dispatch(S.D, launch)) return rc;
+    unsigned long long nc = 0;
+    if (int rc = coarse.count(S.stream, &nc)) return rc;
+    HIPCHK(hipMemcpy(score, dScore.p, (size_t)N * SCORE_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
+    return 0;
+}
+// Plausible values (erm_pv_kernels.hpp; include/ertirt.h: erm_get_plausible_values, erm_plausible_values): the one place that launches pv_kernel.  The subjects
+// go through in chunks whose draws (two doubles and an int each) fit item_pass_chunk's budget whatever K (ERM_PV_CHUNK caps the chunk length); a chunk's draws are
+// copied into pv [N][K][2] and node [N][K] (may be NULL), column-major, before the next chunk runs.  coarse [N] may be NULL.
+static int item_pv(const ItemSource& S, int Q, int64_t K, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
+{
+    const int64_t N = S.D.N;
+    const int64_t chunk = item_pass_chunk(K * (int64_t)(2 * sizeof(double) + sizeof(int)), N, item_chunk_cap("ERM_PV_CHUNK"));
+    DevBuf dPv, dNode;
+    CoarseFlags flags;
+    const char* what = "the plausible values";
+    if (int rc = dPv.try_alloc((size_t)chunk * K * 2 * sizeof(double), what)) return rc;
+    if (node) if (int rc = dNode.try_alloc((size_t)chunk * K * sizeof(int), what)) return rc;
+    if (int rc = flags.alloc(N, what)) return rc;
+    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+        const int64_t nc = std::min(chunk, N - c0);
+        MargArgs a = marg_args(marg_chunk(S.D, c0, nc), S.rows, S.n_rows, Q);
+        a.coarse = flags.flags() + c0;
+        const PvArgs p{(long long)K, (unsigned long long)seed, (long long)c0, dPv.as<double>(), dNode.as<int>()};
+        if (int rc = marg_dispatch(S.D, [&](auto M, auto real) { return marg_tile_launch(&pv_kernel<decltype(M)::value, decltype(real)>, a, S.stream, p); })) return rc;
+        HIPCHK(hipMemcpy2D(pv + c0, (size_t)N * sizeof(double), dPv.p, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), (size_t)(2 * K), hipMemcpyDeviceToHost));
+        if (node) HIPCHK(hipMemcpy2D(node + c0, (size_t)N * sizeof(int), dNode.p, (size_t)nc * sizeof(int), (size_t)nc * sizeof(int), (size_t)K, hipMemcpyDeviceToHost));
+    }
+    unsigned long long n_coarse = 0;
+    if (int rc = flags.count(S.stream, &n_coarse)) return rc;
+    if (coarse) {
+        std::vector<unsigned int> flag((size_t)N);
+        HIPCHK(hipMemcpy(flag.data(), flags.flags(), flag.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < N; ++i) coarse[i] = (int32_t)flag[(size_t)i];
+    }
+    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)n_coarse; }
+    return 0;
+}
+
+}  // namespace
+#endif  // __HIPCC__

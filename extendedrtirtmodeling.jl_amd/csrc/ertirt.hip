@@ -192,282 +192,11 @@ static int pw_totals(const double2* acc_ms, const double2* acc_w, int64_t units,
     return 0;
 }
 
-// Marginal WAIC (erm_marginal_kernels.hpp; include/ertirt.h: erm_get_marginal_waic): marginal_launch is the one place that launches marginal_kernel -- for
-// marginal_run (an engine's resident data set and item trace, a farm's table of rows, erm_marginal_loglik's caller-supplied data) and for the chunks of the
-// marginal PSIS-LOO (marginal_loo_run).  Everything they are given lives on the current device.
-struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; };
-static int marg_refuse_model(int model)
-{
-    if (model == ERM_MODEL_CROSSQR || model == ERM_MODEL_LATENTQR)
-        return fail(ERM_ERR_ARG, "the marginal WAIC serves the five models without quantile weights: with nu integrated out the response-time term is no longer "
-                                 "Gaussian in zeta and the zeta integral has no closed form");
-    if (!marg_served(model)) return fail(ERM_ERR_ARG, "unknown model");
-    return 0;
-}
-static int marg_nodes(int32_t n_nodes, int* Q)
-{
-    *Q = n_nodes == 0 ? MARG_NODES_DEFAULT : n_nodes;
-    if (!marg_nodes_ok(*Q)) return fail(ERM_ERR_ARG, "n_nodes must be 0 (= " + std::to_string(MARG_NODES_DEFAULT) + ") or odd and in " + std::to_string(MARG_NODES_MIN) + " .. " + std::to_string(MARG_NODES_MAX));
-    return 0;
-}
-// what marginal_kernel, score_kernel and pv_kernel share of a launch: the arguments common to the three (the outputs are the caller's to set), the LDS of the row
-// double buffer, the grid of one tile per workgroup, the model's instantiation, and the subjects [c0, c0 + nc) of a data set as a data set of their own
-static MargArgs marg_args(const MargData& D, const double* rows, int64_t n_rows, int Q)
-{
-    MargArgs a{};
-    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = item_trace_width(D.model, D.J, D.Fk); a.N = D.N; a.J = D.J; a.F = D.Fk; a.Q = Q;
-    return a;
-}
-static size_t marg_lds(const MargArgs& a) { return (size_t)2 * marg_row_lds(a.ld, a.J) * sizeof(double); }
-static dim3 marg_grid(const MargArgs& a) { return dim3((unsigned)((a.N + MARG_TILE - 1) / MARG_TILE)); }
-template <typename Launch>
-static int marg_dispatch(int model, Launch&& launch)
-{
-    switch (model) {
-    case ERM_MODEL_MLIRT: return launch(std::integral_constant<int, MLIRT>{});
-    case ERM_MODEL_RTIRT: return launch(std::integral_constant<int, RTIRT>{});
-    case ERM_MODEL_NULL: return launch(std::integral_constant<int, NULLM>{});
-    case ERM_MODEL_CROSS: return launch(std::integral_constant<int, CROSS>{});
-    case ERM_MODEL_LATENT: return launch(std::integral_constant<int, LATENT>{});
-    default: return marg_refuse_model(model);
-    }
-}
-template <typename real>
-static MargData marg_chunk(const MargData& D, int64_t c0, int64_t nc)
-{
-    MargData Dc = D;
-    Dc.Y = D.Y + (size_t)c0 * D.J;
-    Dc.C = D.C ? static_cast<const char*>(D.C) + (size_t)c0 * D.J * sizeof(real) : nullptr;
-    Dc.X = D.X ? static_cast<const char*>(D.X) + (size_t)c0 * D.Fk * sizeof(real) : nullptr;
-    Dc.N = nc;
-    return Dc;
-}
-// one launch of marginal_kernel over the subjects of D and the table of rows, waited for: l_dev [n_rows][D.N], the accumulators and the flags [D.N], any of them NULL
-template <typename real>
-static int marginal_launch(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double2* acc_ms, double2* acc_w, unsigned int* coarse)
-{
-    MargArgs a = marg_args(D, rows, n_rows, Q);
-    a.l_out = l_dev; a.acc_ms = acc_ms; a.acc_w = acc_w; a.coarse = coarse;
-    const size_t lds = marg_lds(a);
-    auto launch = [&](auto M) -> int {
-        constexpr int MODEL = decltype(M)::value;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&marginal_kernel<MODEL, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((marginal_kernel<MODEL, real>), marg_grid(a), dim3(256), lds, stream, a);
-        return 0;
-    };
-    if (int rc = marg_dispatch(D.model, launch)) return rc;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    return 0;
-}
-template <typename real>
-static int marginal_run(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* l_dev, double* out10, double* lppd_u, double* p_u)
-{
-    const bool totals = out10 || lppd_u || p_u;
-    if (totals && n_rows < 2) return fail(ERM_ERR_STATE, "the marginal WAIC needs at least two post-burn-in rows");
-    const int64_t N = D.N;
-    DevBuf dMs, dW, dCoarse, dCnt, dL, dP;
-    const char* what = "the marginal WAIC's accumulators";
-    if (totals) {
-        if (int rc = dMs.try_alloc((size_t)N * sizeof(double2), what)) return rc;
-        if (int rc = dW.try_alloc((size_t)N * sizeof(double2), what)) return rc;
-        if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
-        if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
-        if (lppd_u) if (int rc = dL.try_alloc((size_t)N * sizeof(double), what)) return rc;
-        if (p_u) if (int rc = dP.try_alloc((size_t)N * sizeof(double), what)) return rc;
-    }
-    if (int rc = marginal_launch<real>(D, rows, n_rows, Q, stream, l_dev, dMs.as<double2>(), dW.as<double2>(), dCoarse.as<unsigned int>())) return rc;
-    if (!totals) return 0;
-    double out8[8], sums[PW_FIN_COLS];
-    if (int rc2 = pw_totals(dMs.as<double2>(), dW.as<double2>(), N, n_rows, stream, out8)) return rc2;
-    if (lppd_u || p_u) {
-        if (int rc2 = pw_finish_on(dMs.as<double2>(), dW.as<double2>(), N, n_rows, 0.0, dL.as<double>(), dP.as<double>(), stream, sums)) return rc2;
-        if (lppd_u) HIPCHK(hipMemcpy(lppd_u, dL.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-        if (p_u) HIPCHK(hipMemcpy(p_u, dP.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (out10) {
-        hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
-        unsigned long long nc = 0;
-        HIPCHK(hipMemcpy(&nc, dCnt.p, sizeof(nc), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 8; ++k) out10[k] = out8[k];
-        out10[8] = (double)Q; out10[9] = (double)nc;
-    }
-    return 0;
-}
-
-// Scores of respondents (erm_score_kernels.hpp; include/ertirt.h: erm_get_scores): the one place that launches score_kernel -- for an engine's resident data set
-// and item trace, for a farm's table of rows and for erm_score's caller-supplied data.  Everything it is given lives on the current device; score [N][7] and out4
-// are the caller's host arrays.
-template <typename real>
-static int score_run(const MargData& D, const double* rows, int64_t n_rows, int Q, int weighting, hipStream_t stream, double* score, double* out4)
-{
-    if (n_rows < 1) return fail(ERM_ERR_STATE, "the scores need at least one post-burn-in row");
-    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
-    const int64_t N = D.N;
-    DevBuf dScore, dCoarse, dCnt;
-    const char* what = "the scores";
-    if (int rc = dScore.try_alloc((size_t)N * SCORE_COLS * sizeof(double), what)) return rc;
-    if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
-    if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
-    MargArgs a = marg_args(D, rows, n_rows, Q);
-    a.coarse = dCoarse.as<unsigned int>();
-    const size_t lds = marg_lds(a);
-    auto launch = [&](auto M, auto W) -> int {
-        constexpr int MODEL = decltype(M)::value;
-        constexpr bool WEIGHTED = decltype(W)::value;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&score_kernel<MODEL, real, WEIGHTED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((score_kernel<MODEL, real, WEIGHTED>), marg_grid(a), dim3(256), lds, stream, a, dScore.as<double>());
-        return 0;
-    };
-    auto pick = [&](auto M) -> int { return weighting == SCORE_LIKELIHOOD ? launch(M, std::true_type{}) : launch(M, std::false_type{}); };
-    if (int rc = marg_dispatch(D.model, pick)) return rc;
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    unsigned long long nc = 0;
-    HIPCHK(hipMemcpy(&nc, dCnt.p, sizeof(nc), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(score, dScore.p, (size_t)N * SCORE_COLS * sizeof(double), hipMemcpyDeviceToHost));
-    if (out4) { out4[0] = (double)N; out4[1] = (double)n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
-    return 0;
-}
-
-// Plausible values (erm_pv_kernels.hpp; include/ertirt.h: erm_get_plausible_values): the one place that launches pv_kernel -- for an engine's resident data set and
-// item trace, for a farm's table of rows and for erm_plausible_values' caller-supplied data.  The subjects go through in chunks whose draws (two doubles and an int
-// each) fit 256 MB whatever K (ERM_PV_CHUNK: a chunk length in subjects, for the tests of the chunk tails); a chunk's draws are copied into the caller's host arrays
-// pv [N][K][2] and node [N][K] (may be NULL), column-major, before the next chunk runs.  coarse [N] (may be NULL) and out4 are the caller's host arrays too.
-template <typename real>
-static int pv_run(const MargData& D, const double* rows, int64_t n_rows, int Q, int64_t K, uint64_t seed, hipStream_t stream, double* pv, int32_t* node, int32_t* coarse, double* out4)
-{
-    if (n_rows < 1) return fail(ERM_ERR_STATE, "the plausible values need at least one post-burn-in row");
-    if (!pv_draws_ok(K)) return fail(ERM_ERR_ARG, "n_draws must be in " + std::to_string(PV_DRAWS_MIN) + " .. " + std::to_string(PV_DRAWS_MAX));
-    const int64_t N = D.N;
-    const int64_t per = K * (int64_t)(2 * sizeof(double) + sizeof(int));
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / per);
-    if (const char* e = getenv("ERM_PV_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk = std::min<int64_t>(chunk, v); }
-    chunk = std::min(chunk, N);
-    DevBuf dPv, dNode, dCoarse, dCnt;
-    const char* what = "the plausible values";
-    if (int rc = dPv.try_alloc((size_t)chunk * K * 2 * sizeof(double), what)) return rc;
-    if (node) if (int rc = dNode.try_alloc((size_t)chunk * K * sizeof(int), what)) return rc;
-    if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), what)) return rc;
-    if (int rc = dCnt.try_alloc(sizeof(unsigned long long), what)) return rc;
-    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
-        const int64_t nc = std::min(chunk, N - c0);
-        MargArgs a = marg_args(marg_chunk<real>(D, c0, nc), rows, n_rows, Q);
-        a.coarse = dCoarse.as<unsigned int>() + c0;
-        const PvArgs p{(long long)K, (unsigned long long)seed, (long long)c0, dPv.as<double>(), dNode.as<int>()};
-        const size_t lds = marg_lds(a);
-        auto launch = [&](auto M) -> int {
-            constexpr int MODEL = decltype(M)::value;
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pv_kernel<MODEL, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((pv_kernel<MODEL, real>), marg_grid(a), dim3(256), lds, stream, a, p);
-            return 0;
-        };
-        if (int rc = marg_dispatch(D.model, launch)) return rc;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipMemcpy2D(pv + c0, (size_t)N * sizeof(double), dPv.p, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), (size_t)(2 * K), hipMemcpyDeviceToHost));
-        if (node) HIPCHK(hipMemcpy2D(node + c0, (size_t)N * sizeof(int), dNode.p, (size_t)nc * sizeof(int), (size_t)nc * sizeof(int), (size_t)K, hipMemcpyDeviceToHost));
-    }
-    hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    unsigned long long n_coarse = 0;
-    HIPCHK(hipMemcpy(&n_coarse, dCnt.p, sizeof(n_coarse), hipMemcpyDeviceToHost));
-    if (coarse) {
-        std::vector<unsigned int> flag((size_t)N);
-        HIPCHK(hipMemcpy(flag.data(), dCoarse.p, flag.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < N; ++i) coarse[i] = (int32_t)flag[(size_t)i];
-    }
-    if (out4) { out4[0] = (double)N; out4[1] = (double)n_rows; out4[2] = (double)Q; out4[3] = (double)n_coarse; }
-    return 0;
-}
-
-// Marginal PSIS-LOO (erm_psis_kernels.hpp; include/ertirt.h: erm_get_marginal_loo): the one place that launches psis_kernel -- for an engine's or a farm's l, which
-// marginal_kernel writes chunk by chunk, and for erm_psis_loo's caller-supplied table.  The subjects go through in chunks whose staged l fits 256 MB whatever S
-// (ERM_PSIS_CHUNK: a chunk length in subjects, for the tests of the chunk tails); fill(c0, nc, dst) puts l of the subjects [c0, c0 + nc) into dst as [S][nc], and
-// take(c0, nc, src), if given, receives their smoothed log-weights in the same layout.
-static int psis_rows_ok(int64_t S)
-{
-    if (S < PSIS_MIN_ROWS) return fail(ERM_ERR_ARG, "PSIS-LOO needs at least " + std::to_string(PSIS_MIN_ROWS) + " rows per unit (" + std::to_string(S) + " given): fewer leave a tail of less than 5 values");
-    if (S > PSIS_MAX_ROWS) return fail(ERM_ERR_ARG, "PSIS-LOO takes at most " + std::to_string(PSIS_MAX_ROWS) + " rows per unit (" + std::to_string(S) + " given): a unit's rows are sorted in LDS");
-    return 0;
-}
-template <typename Fill, typename Take>
-static int psis_run(int64_t N, int64_t S, hipStream_t stream, Fill&& fill, Take&& take, bool want_lw, double* out8, double* pw)
-{
-    const int P = rk_pad((int)S);
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / (S * (int64_t)sizeof(double)));
-    if (const char* e = getenv("ERM_PSIS_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk = std::min<int64_t>(chunk, v); }
-    chunk = std::min(chunk, N);
-    DevBuf dL, dXs, dPw, dOut;
-    if (int rc = dL.try_alloc((size_t)chunk * S * sizeof(double), "PSIS-LOO's log-likelihoods")) return rc;
-    if (int rc = dXs.try_alloc((size_t)chunk * S * sizeof(double), "PSIS-LOO's staged log-likelihoods")) return rc;
-    if (int rc = dPw.try_alloc((size_t)N * PSIS_DEV_COLS * sizeof(double), "PSIS-LOO's pointwise table")) return rc;
-    if (int rc = dOut.try_alloc(8 * sizeof(double), "PSIS-LOO's totals")) return rc;
-    const int tps = P <= 2048 ? 64 : P <= 4096 ? 128 : 256, ns = 256 / tps;
-    const size_t lds = (size_t)ns * P * 10;
-    const void* kern = tps == 64 ? reinterpret_cast<const void*>(&psis_kernel<64>) : tps == 128 ? reinterpret_cast<const void*>(&psis_kernel<128>) : reinterpret_cast<const void*>(&psis_kernel<256>);
-    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
-        const int64_t nc = std::min(chunk, N - c0);
-        if (int rc = fill(c0, nc, dL.as<double>())) return rc;
-        hipLaunchKernelGGL(psis_transpose_kernel, dim3((unsigned)((nc + 31) / 32), (unsigned)((S + 31) / 32)), dim3(256), 0, stream, dL.as<double>(), (long long)S, (long long)nc, dXs.as<double>());
-        PsisArgs a{};
-        a.xs = dXs.as<double>(); a.n = nc; a.S = (int)S; a.P = P; a.pw = dPw.as<double>(); a.n_all = N; a.c0 = c0; a.want_lw = want_lw ? 1 : 0;
-        const dim3 grid((unsigned)((nc + ns - 1) / ns));
-        if (tps == 64) hipLaunchKernelGGL(psis_kernel<64>, grid, dim3(256), lds, stream, a);
-        else if (tps == 128) hipLaunchKernelGGL(psis_kernel<128>, grid, dim3(256), lds, stream, a);
-        else hipLaunchKernelGGL(psis_kernel<256>, grid, dim3(256), lds, stream, a);
-        if (want_lw) hipLaunchKernelGGL(psis_transpose_kernel, dim3((unsigned)((S + 31) / 32), (unsigned)((nc + 31) / 32)), dim3(256), 0, stream, dXs.as<double>(), (long long)nc, (long long)S, dL.as<double>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
-        if (want_lw) if (int rc = take(c0, nc, dL.as<double>())) return rc;
-    }
-    hipLaunchKernelGGL(psis_totals_kernel, dim3(1), dim3(256), 0, stream, dPw.as<double>(), (long long)N, psis_k_threshold(S), dOut.as<double>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipMemcpy(out8, dOut.p, 8 * sizeof(double), hipMemcpyDeviceToHost));
-    if (pw) HIPCHK(hipMemcpy(pw, dPw.p, (size_t)N * PSIS_COLS * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-// out12 from psis_totals_kernel's sums
-static void psis_out12(const double* s8, int64_t N, int64_t S, int Q, int64_t n_coarse, double* out12)
-{
-    const double U = (double)N, var_u = N > 1 ? s8[3] / (U - 1.0) : 0.0;
-    out12[0] = s8[0]; out12[1] = s8[1]; out12[2] = -2.0 * s8[0]; out12[3] = 2.0 * std::sqrt(U * var_u); out12[4] = s8[2]; out12[5] = U; out12[6] = (double)S;
-    out12[7] = s8[4]; out12[8] = s8[5]; out12[9] = (double)psis_tail_len(S); out12[10] = (double)Q; out12[11] = (double)n_coarse;
-}
-// an engine's or a farm's: l of every chunk from marginal_kernel, on the data set D and the table of rows (both on the current device)
-template <typename real>
-static int marginal_loo_run(const MargData& D, const double* rows, int64_t n_rows, int Q, hipStream_t stream, double* out12, double* pw)
-{
-    if (int rc = psis_rows_ok(n_rows)) return rc;
-    const int64_t N = D.N;
-    DevBuf dCoarse, dCnt;
-    if (int rc = dCoarse.try_alloc((size_t)N * sizeof(unsigned int), "the marginal LOO's flags")) return rc;
-    if (int rc = dCnt.try_alloc(sizeof(unsigned long long), "the marginal LOO's flags")) return rc;
-    auto fill = [&](int64_t c0, int64_t nc, double* dst) -> int {
-        return marginal_launch<real>(marg_chunk<real>(D, c0, nc), rows, n_rows, Q, stream, dst, nullptr, nullptr, dCoarse.as<unsigned int>() + c0);
-    };
-    double s8[8];
-    if (int rc = psis_run(N, n_rows, stream, fill, [](int64_t, int64_t, const double*) { return 0; }, false, s8, pw)) return rc;
-    hipLaunchKernelGGL(marginal_count_kernel, dim3(1), dim3(256), 0, stream, dCoarse.as<unsigned int>(), (long long)N, dCnt.as<unsigned long long>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    unsigned long long nc = 0;
-    HIPCHK(hipMemcpy(&nc, dCnt.p, sizeof(nc), hipMemcpyDeviceToHost));
-    psis_out12(s8, N, n_rows, Q, (int64_t)nc, out12);
-    return 0;
-}
-
 // A persistent launch needs all its workgroups resident at once.  Two persistent launches of ONE process on one device (a farm's chains sharing a
 // device, several engines) could each hold some compute units and wait for the other's for ever: they take turns.
 std::mutex g_persist_mu[64];
 
+struct ItemSource;      // erm_item_pass.hpp
 struct EngineBase {
     erm_config cfg{};
     virtual ~EngineBase() {}
@@ -485,15 +214,11 @@ struct EngineBase {
     virtual int get_waic(double* out8) = 0;
     virtual int64_t pointwise_units() const = 0;
     virtual int get_pointwise(double* lppd_u, double* p_u) = 0;
-    // marginal WAIC (erm_get_marginal_waic; the farm hands chain 0 a table of the rows of all chains on its device: rows != NULL), and the resident item trace
-    virtual int marginal_waic(int Q, const double* rows, int64_t n_rows, double* out10, double* lppd_u, double* p_u) = 0;
+    // the passes over the item trace (erm_item_pass.hpp: marginal WAIC and LOO, scores, plausible values): this engine's resident data set as the source of `pass`,
+    // or the refusal in the pass's words; S.rows == NULL: with its own post-burn-in rows, read in place (the farm hands chain 0 a table of the rows of all chains
+    // on its device).  And the resident item trace.
+    virtual int item_source(int pass, ItemSource& S) = 0;
     virtual const double* item_trace_dev() const = 0;
-    // marginal PSIS-LOO (erm_get_marginal_loo; rows as for marginal_waic)
-    virtual int marginal_loo(int Q, const double* rows, int64_t n_rows, double* out12, double* pw) = 0;
-    // scores of respondents (erm_get_scores; rows as for marginal_waic), equal weights
-    virtual int scores(int Q, const double* rows, int64_t n_rows, double* score, double* out4) = 0;
-    // plausible values (erm_get_plausible_values; rows as for marginal_waic)
-    virtual int plausible_values(int Q, const double* rows, int64_t n_rows, int64_t K, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4) = 0;
     // posterior predictive checks (erm_set_predictive / erm_predictive_reps / erm_get_predictive)
     virtual int set_predictive(int on, int32_t thin) = 0;
     virtual int64_t predictive_reps() const = 0;
@@ -1061,60 +786,9 @@ template <typename real> struct Engine : EngineBase {
         if (int rc = pw_ready()) return rc;
         return pw_totals(dPwMs.as<double2>(), dPwW.as<double2>(), pointwise_units(), post_rows, stream, out8);
     }
-    // ---- marginal WAIC: computed after the run from the resident data set and item-trace rows (rows == NULL: this chain's own post-burn-in rows, read in place)
+    // ---- the passes over the item trace, computed after the run from the resident data set and item-trace rows (defined where ItemSource is: below erm_item_pass.hpp)
     const double* item_trace_dev() const override { return dTrItem.as<double>(); }
-    int marginal_waic(int Q, const double* rows, int64_t n_rows, double* out10, double* lppd_u, double* p_u) override {
-        if (int rc = marg_refuse_model(cfg.model)) return rc;
-        if (sharded()) return fail(ERM_ERR_STATE, "the marginal WAIC is not available on a shard (every subject's data must be resident on one device)");
-        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
-        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
-        if (!rows) {
-            if (post_rows < 2) return fail(ERM_ERR_STATE, "the marginal WAIC needs at least two post-burn-in rows");
-            rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows;
-        }
-        HIPCHK(hipSetDevice(cfg.device));
-        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
-        return marginal_run<real>(D, rows, n_rows, Q, stream, nullptr, out10, lppd_u, p_u);
-    }
-    // ---- marginal PSIS-LOO: as the marginal WAIC, from the resident data set and item-trace rows; 25 .. 8192 of them
-    int marginal_loo(int Q, const double* rows, int64_t n_rows, double* out12, double* pw) override {
-        if (int rc = marg_refuse_model(cfg.model)) return rc;
-        if (sharded()) return fail(ERM_ERR_STATE, "the marginal LOO is not available on a shard (every subject's data must be resident on one device)");
-        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
-        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
-        if (!rows) { rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows; }
-        HIPCHK(hipSetDevice(cfg.device));
-        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
-        return marginal_loo_run<real>(D, rows, n_rows, Q, stream, out12, pw);
-    }
-    // ---- scores: as the marginal WAIC, from the resident data set and item-trace rows; one post-burn-in row is enough
-    int scores(int Q, const double* rows, int64_t n_rows, double* score, double* out4) override {
-        if (int rc = marg_refuse_model(cfg.model)) return rc;
-        if (sharded()) return fail(ERM_ERR_STATE, "the scores are not available on a shard (every subject's data must be resident on one device)");
-        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
-        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
-        if (!rows) {
-            if (post_rows < 1) return fail(ERM_ERR_STATE, "the scores need at least one post-burn-in row");
-            rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows;
-        }
-        HIPCHK(hipSetDevice(cfg.device));
-        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
-        return score_run<real>(D, rows, n_rows, Q, SCORE_EQUAL, stream, score, out4);
-    }
-    // ---- plausible values: as the scores, from the resident data set and item-trace rows; one post-burn-in row is enough
-    int plausible_values(int Q, const double* rows, int64_t n_rows, int64_t K, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4) override {
-        if (int rc = marg_refuse_model(cfg.model)) return rc;
-        if (sharded()) return fail(ERM_ERR_STATE, "the plausible values are not available on a shard (every subject's data must be resident on one device)");
-        if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
-        if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
-        if (!rows) {
-            if (post_rows < 1) return fail(ERM_ERR_STATE, "the plausible values need at least one post-burn-in row");
-            rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); n_rows = post_rows;
-        }
-        HIPCHK(hipSetDevice(cfg.device));
-        const MargData D{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model};
-        return pv_run<real>(D, rows, n_rows, Q, K, seed, stream, pv, node, coarse, out4);
-    }
+    int item_source(int pass, ItemSource& S) override;
     int get_pointwise(double* lppd_u, double* p_u) override {
         if (int rc = pw_ready()) return rc;
         const int64_t U = pointwise_units();
@@ -2045,6 +1719,70 @@ static int debug_upload(const double* x, int64_t n_draw, int64_t n_col, int32_t 
 }
 
 #include "erm_diagnostics.hpp"             // the convergence diagnostics' host path: the engine's, the farm's and the debug entries'
+#include "erm_item_pass.hpp"               // the item-trace passes' host path: marginal WAIC and LOO, scores, plausible values
+
+namespace {
+// an engine as the source of a pass (EngineBase::item_source)
+template <typename real> int Engine<real>::item_source(int pass, ItemSource& S)
+{
+    if (sharded()) return fail(ERM_ERR_STATE, item_pass_on_shard(pass));
+    if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
+    if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
+    if (!S.rows) {
+        if (post_rows < ITEM_PASSES[pass].engine_rows) return fail(ERM_ERR_STATE, item_pass_needs_rows(pass));
+        S.rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); S.n_rows = post_rows;
+    }
+    HIPCHK(hipSetDevice(cfg.device));
+    S.D = MargData{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model, sizeof(real)};
+    S.stream = stream;
+    return 0;
+}
+// what every entry of a pass checks first: its output, the node count -- and the plausible values' the number of draws
+static int item_entry_args(const void* out, int32_t n_nodes, int* Q)
+{
+    if (!out) return fail(ERM_ERR_ARG, "out is NULL");
+    return marg_nodes(n_nodes, Q);
+}
+static int pv_entry_args(int32_t n_nodes, int32_t n_draws, const double* pv, int* Q)
+{
+    if (int rc = item_entry_args(pv, n_nodes, Q)) return rc;
+    if (!pv_draws_ok(n_draws)) return fail(ERM_ERR_ARG, "n_draws must be in " + std::to_string(PV_DRAWS_MIN) + " .. " + std::to_string(PV_DRAWS_MAX));
+    return 0;
+}
+// erm_get_* (H = erm_handle) and erm_farm_get_* (H = erm_farm_handle) of the four passes: the checks, the source, the product
+template <typename H> static int get_marginal_waic(H h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
+{
+    int Q = 0;
+    ItemSource S;
+    if (int rc = item_entry_args(out10, n_nodes, &Q)) return rc;
+    if (int rc = item_source(h, PASS_WAIC, S)) return rc;
+    return item_waic(S, Q, nullptr, out10, lppd_u, p_u);
+}
+template <typename H> static int get_marginal_loo(H h, int32_t n_nodes, double* out12, double* pw)
+{
+    int Q = 0;
+    ItemSource S;
+    if (int rc = item_entry_args(out12, n_nodes, &Q)) return rc;
+    if (int rc = item_source(h, PASS_LOO, S)) return rc;
+    return item_loo(S, Q, out12, pw);
+}
+template <typename H> static int get_scores(H h, int32_t n_nodes, double* score, double* out4)
+{
+    int Q = 0;
+    ItemSource S;
+    if (int rc = item_entry_args(score, n_nodes, &Q)) return rc;
+    if (int rc = item_source(h, PASS_SCORES, S)) return rc;
+    return item_scores(S, Q, SCORE_EQUAL, score, out4);
+}
+template <typename H> static int get_plausible_values(H h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
+{
+    int Q = 0;
+    ItemSource S;
+    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
+    if (int rc = item_source(h, PASS_PV, S)) return rc;
+    return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
+}
+}  // namespace
 
 extern "C" {
 
@@ -2088,44 +1826,13 @@ int erm_set_pointwise(erm_handle h, int unit) { CHK_H; return h->e->set_pointwis
 int erm_get_waic(erm_handle h, double* out_eight) { CHK_H; if (!out_eight) return fail(ERM_ERR_ARG, "out is NULL"); return h->e->get_waic(out_eight); }
 int64_t erm_pointwise_units(erm_handle h) { return h ? h->e->pointwise_units() : -1; }
 int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u) { CHK_H; return h->e->get_pointwise(lppd_u, p_u); }
-int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
-{
-    CHK_H;
-    if (!out10) return fail(ERM_ERR_ARG, "out is NULL");
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    return h->e->marginal_waic(Q, nullptr, 0, out10, lppd_u, p_u);
-}
-int erm_get_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw)
-{
-    CHK_H;
-    if (!out12) return fail(ERM_ERR_ARG, "out is NULL");
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    return h->e->marginal_loo(Q, nullptr, 0, out12, pw);
-}
-int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4)
-{
-    CHK_H;
-    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    return h->e->scores(Q, nullptr, 0, score, out4);
-}
-// what the three plausible-value entries check before anything else: the outputs, the node count, the number of draws
-static int pv_entry_args(int32_t n_nodes, int32_t n_draws, const double* pv, int* Q)
-{
-    if (!pv) return fail(ERM_ERR_ARG, "out is NULL");
-    if (int rc = marg_nodes(n_nodes, Q)) return rc;
-    if (!pv_draws_ok(n_draws)) return fail(ERM_ERR_ARG, "n_draws must be in " + std::to_string(PV_DRAWS_MIN) + " .. " + std::to_string(PV_DRAWS_MAX));
-    return 0;
-}
+int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_H; return get_marginal_waic(h, n_nodes, out10, lppd_u, p_u); }
+int erm_get_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw) { CHK_H; return get_marginal_loo(h, n_nodes, out12, pw); }
+int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4) { CHK_H; return get_scores(h, n_nodes, score, out4); }
 int erm_get_plausible_values(erm_handle h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
     CHK_H;
-    int Q = 0;
-    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
-    return h->e->plausible_values(Q, nullptr, 0, n_draws, seed, pv, node, coarse, out4);
+    return get_plausible_values(h, n_nodes, n_draws, seed, pv, node, coarse, out4);
 }
 int erm_set_predictive(erm_handle h, int on, int32_t thin) { CHK_H; return h->e->set_predictive(on, thin); }
 int64_t erm_predictive_reps(erm_handle h) { return h ? h->e->predictive_reps() : -1; }
@@ -2336,81 +2043,14 @@ int erm_farm_get_dic(erm_farm_handle f, double* out4)
     for (auto& e : f->eng) chains.push_back(e->e.get());
     return dic_from_summary(chains.data(), chains.size(), acc[d0].as<double>(), total, out4);
 }
-// The farm's marginal WAIC: the post-burn-in item-trace rows of chain 0, chain 1, ... as ONE table on chain 0's device, whose resident data set supplies the data.
-// A chain's rows cross through the host whatever its device (item-level: a few hundred kilobytes); a farm of one chain takes the same path as several.
-// (the table of both farm entries: min_post = the post-burn-in rows every chain must have, need = the refusal's words; the current device is chain 0's on return)
-static int farm_row_table(erm_farm_handle f, int64_t min_post, const char* need, DevBuf& dTab, int64_t* n_rows)
-{
-    const int L = (int)f->eng.size();
-    EngineBase* e0 = f->eng[0]->e.get();
-    const int64_t wi = e0->item_trace_width(), rows = e0->rows_done, post = e0->post_rows;
-    for (int l = 0; l < L; ++l) {
-        const EngineBase* e = f->eng[l]->e.get();
-        if (e->rows_done != rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + std::to_string(e->rows_done) + " rows recorded where chain 0 has " + std::to_string(rows));
-        if (e->post_rows < min_post) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + need);
-    }
-    std::vector<double> table((size_t)L * post * wi);
-    for (int l = 0; l < L; ++l) {
-        const EngineBase* e = f->eng[l]->e.get();
-        HIPCHK(hipSetDevice(f->dev[l]));
-        HIPCHK(hipStreamSynchronize(e->work_stream()));
-        HIPCHK(hipMemcpy(table.data() + (size_t)l * post * wi, e->item_trace_dev() + (size_t)(rows - post) * wi, (size_t)post * wi * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    HIPCHK(hipSetDevice(f->dev[0]));
-    if (int rc = dTab.try_alloc(table.size() * sizeof(double), "the farm's table of item-trace rows")) return rc;
-    H2D(dTab.p, table.data(), table.size() * sizeof(double));
-    *n_rows = (int64_t)L * post;
-    return 0;
-}
-int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
-{
-    CHK_F;
-    if (!out10) return fail(ERM_ERR_ARG, "out is NULL");
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
-    DevBuf dTab;
-    int64_t n_rows = 0;
-    if (int rc = farm_row_table(f, 2, "the marginal WAIC needs at least two post-burn-in rows", dTab, &n_rows)) return rc;
-    return f->eng[0]->e->marginal_waic(Q, dTab.as<double>(), n_rows, out10, lppd_u, p_u);
-}
-// The farm's marginal PSIS-LOO: the same table, the same device.
-int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw)
-{
-    CHK_F;
-    if (!out12) return fail(ERM_ERR_ARG, "out is NULL");
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
-    DevBuf dTab;
-    int64_t n_rows = 0;
-    if (int rc = farm_row_table(f, 1, "the marginal LOO needs post-burn-in rows (25 .. 8192 over the chains)", dTab, &n_rows)) return rc;
-    return f->eng[0]->e->marginal_loo(Q, dTab.as<double>(), n_rows, out12, pw);
-}
-// The farm's scores: the same table, the same device, equal weights.
-int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4)
-{
-    CHK_F;
-    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
-    DevBuf dTab;
-    int64_t n_rows = 0;
-    if (int rc = farm_row_table(f, 1, "the scores need at least one post-burn-in row", dTab, &n_rows)) return rc;
-    return f->eng[0]->e->scores(Q, dTab.as<double>(), n_rows, score, out4);
-}
-// The farm's plausible values: the same table, the same device.
+// the farm's passes over the item trace: the engine's, over the post-burn-in rows of all chains as one table on chain 0's device (erm_item_pass.hpp)
+int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_F; return get_marginal_waic(f, n_nodes, out10, lppd_u, p_u); }
+int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw) { CHK_F; return get_marginal_loo(f, n_nodes, out12, pw); }
+int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4) { CHK_F; return get_scores(f, n_nodes, score, out4); }
 int erm_farm_get_plausible_values(erm_farm_handle f, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
     CHK_F;
-    int Q = 0;
-    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
-    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
-    DevBuf dTab;
-    int64_t n_rows = 0;
-    if (int rc = farm_row_table(f, 1, "the plausible values need at least one post-burn-in row", dTab, &n_rows)) return rc;
-    return f->eng[0]->e->plausible_values(Q, dTab.as<double>(), n_rows, n_draws, seed, pv, node, coarse, out4);
+    return get_plausible_values(f, n_nodes, n_draws, seed, pv, node, coarse, out4);
 }
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed)
 {
@@ -2428,74 +2068,16 @@ const char* erm_last_error(void) { return g_err.c_str(); }
 const char* erm_version(void) { return "ertirt-amd 0.4.0 (gfx950)"; }
 int erm_abi_version(void) { return ERM_ABI_VERSION; }
 
-// Caller-supplied data and rows for marginal_run / score_run (erm_marginal_loglik, erm_score): validated on the host, then uploaded to `device` row-major in fp64,
-// as the kernels read an engine's.  min_rows / rows_msg: the fewest rows the caller's outputs need.
-struct MargUpload { DevBuf dY, dC, dX, dRows; MargData D; };
-static int marg_upload(const char* what, int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
-                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, MargUpload& U)
-{
-    const ModelTraits mt = model_traits(model);
-    if (n_subj <= 0 || n_subj >= (1LL << 32) || n_item <= 0 || n_item > 896 || n_feat < 0 || n_feat > MARG_MAXF) return fail(ERM_ERR_ARG, "n_subj, n_item (1 .. 896) or n_feat (0 .. " + std::to_string(MARG_MAXF) + ") out of range");
-    const int64_t N = n_subj; const int J = n_item, Fk = kernel_feat(model, n_feat);
-    if (!Y || !rows) return fail(ERM_ERR_ARG, "Y / rows is NULL");
-    if (mt.rt && !logT) return fail(ERM_ERR_ARG, "logT is required for response-time models");
-    if (Fk > 0 && !X) return fail(ERM_ERR_ARG, "X is required when n_feat > 0");
-    if (n_rows < min_rows) return fail(ERM_ERR_ARG, rows_msg);
-    const int64_t wi = item_trace_width(model, J, Fk);
-    const size_t NJ = (size_t)N * J;
-    // ---- the inputs: a NaN anywhere, then rows outside the model's domain
-    for (size_t e = 0; e < (size_t)n_rows * wi; ++e) if (rows[e] != rows[e]) return fail(ERM_ERR_NONFINITE, "NaN in row " + std::to_string(e / (size_t)wi));
-    if (mt.rt) for (size_t e = 0; e < NJ; ++e) if (logT[e] != logT[e]) return fail(ERM_ERR_NONFINITE, "NaN in logT");
-    for (size_t e = 0; e < (size_t)N * Fk; ++e) if (X[e] != X[e]) return fail(ERM_ERR_NONFINITE, "NaN in X");
-    for (size_t e = 0; e < NJ; ++e) if (Y[e] > 1) return fail(ERM_ERR_ARG, "Y must be 0/1");
-    if (mt.rt) for (int64_t r = 0; r < n_rows; ++r) {
-        const double* row = rows + (size_t)r * wi;
-        for (int j = 0; j < J; ++j) if (!(row[3 * J + j] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": sig2t must be positive");
-        const double* S = row + 4 * J + qr_sigp_off(model, J, Fk);
-        if (!(S[0] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": Sigma_p[1,1] must be positive");
-        if (marg_law(model, 0.0, 0.0, 0.0, S).v < 0.0) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": the conditional variance of zeta given theta is negative (Sigma_p is not positive semi-definite)");
-    }
-    HIPCHK(hipSetDevice(device));
-    // ---- upload: the data set row-major in fp64, as the kernel reads an engine's
-    {
-        std::vector<uint8_t> y(NJ);
-        cols_to_rows(Y, y.data(), N, (int64_t)J);
-        if (int rc = U.dY.try_alloc(NJ, what)) return rc;
-        H2D(U.dY.p, y.data(), NJ);
-    }
-    if (mt.rt) {
-        std::vector<double> c(NJ);
-        cols_to_rows(logT, c.data(), N, (int64_t)J);
-        if (int rc = U.dC.try_alloc(NJ * sizeof(double), what)) return rc;
-        H2D(U.dC.p, c.data(), NJ * sizeof(double));
-    }
-    if (Fk > 0) {
-        std::vector<double> x((size_t)N * Fk);
-        cols_to_rows(X, x.data(), N, (int64_t)Fk);
-        if (int rc = U.dX.try_alloc(x.size() * sizeof(double), what)) return rc;
-        H2D(U.dX.p, x.data(), x.size() * sizeof(double));
-    }
-    if (int rc = U.dRows.try_alloc((size_t)n_rows * wi * sizeof(double), what)) return rc;
-    H2D(U.dRows.p, rows, (size_t)n_rows * wi * sizeof(double));
-    U.D = MargData{U.dY.as<uint8_t>(), U.dC.p, U.dX.p, nullptr, N, J, Fk, model};
-    return 0;
-}
-
 int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                         int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u)
 {
     if (int rc = marg_refuse_model(model)) return rc;
     int Q = 0;
     if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    const bool totals = out10 || lppd_u || p_u;
-    MargUpload U;
-    if (int rc = marg_upload("erm_marginal_loglik's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, totals ? 2 : 1,
-                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", U)) return rc;
-    DevBuf dL;
-    if (l) if (int rc = dL.try_alloc((size_t)n_subj * n_rows * sizeof(double), "erm_marginal_loglik's output")) return rc;
-    if (int rc = marginal_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, nullptr, dL.as<double>(), out10, lppd_u, p_u)) return rc;
-    if (l) HIPCHK(hipMemcpy(l, dL.p, (size_t)n_subj * n_rows * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    ItemSource S;
+    if (int rc = item_source("erm_marginal_loglik's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, out10 || lppd_u || p_u ? 2 : 1,
+                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S)) return rc;
+    return item_waic(S, Q, l, out10, lppd_u, p_u);
 }
 
 int erm_psis_loo(int device, const double* l, int64_t n_subj, int64_t n_rows, double* out12, double* pw, double* lw)
@@ -2528,9 +2110,9 @@ int erm_score(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_f
     if (int rc = marg_nodes(n_nodes, &Q)) return rc;
     if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
     if (!score) return fail(ERM_ERR_ARG, "out is NULL");
-    MargUpload U;
-    if (int rc = marg_upload("erm_score's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", U)) return rc;
-    return score_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, weighting, nullptr, score, out4);
+    ItemSource S;
+    if (int rc = item_source("erm_score's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S)) return rc;
+    return item_scores(S, Q, weighting, score, out4);
 }
 
 int erm_plausible_values(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
@@ -2539,9 +2121,9 @@ int erm_plausible_values(int device, int model, int64_t n_subj, int32_t n_item, 
     if (int rc = marg_refuse_model(model)) return rc;
     int Q = 0;
     if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
-    MargUpload U;
-    if (int rc = marg_upload("erm_plausible_values' inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", U)) return rc;
-    return pv_run<double>(U.D, U.dRows.as<double>(), n_rows, Q, n_draws, seed, nullptr, pv, node, coarse, out4);
+    ItemSource S;
+    if (int rc = item_source("erm_plausible_values' inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S)) return rc;
+    return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
 }
 
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out)

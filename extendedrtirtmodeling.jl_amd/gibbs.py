@@ -679,17 +679,23 @@ def marginalRows(MCMC: _GibbsBase) -> np.ndarray:
     return src.item_trace()[C.nBurnin * C.nChain:]
 
 
-def getWaicMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) -> OutputWaic:
-    """getWaicMarginal evaluated with numpy / scipy on the host (the test twin of the device path) from MCMC.Data and the item-level trace rows (marginalRows, or
-    `rows`)."""
-    Q = _marginal_check(MCMC, nodes)
+def _marginal_loglik_host(MCMC, nodes, rows, who):
+    """What getWaicMarginalHost and getLooMarginalHost start from: marginalLogLikHost's l [S, N], the node count, the subjects with a grid too coarse at any row."""
+    Q = _marginal_check(MCMC, nodes, who)
     D, t = MCMC.Data, MCMC._traits
     if D is None:
         raise ValueError("Data is required")
     rows = marginalRows(MCMC) if rows is None else rows
     X = np.asarray(D.X, dtype=np.float64) if t.sees_x and MCMC.Cond.nFeat > 0 else None
     L, S = marginalLogLikHost(MCMC._model, D.Y, D.logT if t.rt else None, X, rows, Q, with_S=True)
-    return waicFromLogLik(L, nNodes=Q, nCoarse=int(np.sum(np.any(S < 2.0, axis=0))))
+    return L, Q, int(np.sum(np.any(S < 2.0, axis=0)))
+
+
+def getWaicMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) -> OutputWaic:
+    """getWaicMarginal evaluated with numpy / scipy on the host (the test twin of the device path) from MCMC.Data and the item-level trace rows (marginalRows, or
+    `rows`)."""
+    L, Q, n_coarse = _marginal_loglik_host(MCMC, nodes, rows, "getWaicMarginal")
+    return waicFromLogLik(L, nNodes=Q, nCoarse=n_coarse)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -808,15 +814,9 @@ def psisLooHost(L, dtype=np.float64, with_lw=False, with_fit=False):
 def getLooMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) -> OutputLoo:
     """getLooMarginal evaluated with numpy on the host (the test twin of the device path): marginalLogLikHost on MCMC.Data and the item-level trace rows
     (marginalRows, or `rows`), then psisLooHost."""
-    Q = _marginal_check(MCMC, nodes, "getLooMarginal")
-    D, t = MCMC.Data, MCMC._traits
-    if D is None:
-        raise ValueError("Data is required")
-    rows = marginalRows(MCMC) if rows is None else rows
-    X = np.asarray(D.X, dtype=np.float64) if t.sees_x and MCMC.Cond.nFeat > 0 else None
-    L, S = marginalLogLikHost(MCMC._model, D.Y, D.logT if t.rt else None, X, rows, Q, with_S=True)
+    L, Q, n_coarse = _marginal_loglik_host(MCMC, nodes, rows, "getLooMarginal")
     out = psisLooHost(L)
-    out.unit, out.nNodes, out.nCoarse = MARGINAL_UNIT, Q, int(np.sum(np.any(S < 2.0, axis=0)))
+    out.unit, out.nNodes, out.nCoarse = MARGINAL_UNIT, Q, n_coarse
     return out
 
 
@@ -848,6 +848,23 @@ def scoreRespondents(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighti
     return _scores_output(_lib.score(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), weighting=w, device=device), "likelihood" if w else "equal")
 
 
+def _row_moments(e, z, law, sums, rt):
+    """A row of _marginal_rows_host for scoresHost and plausibleValuesHost: theta's mean and variance E, V (N,) on the rule, zeta | theta ~ N(c0 + c1 theta, u)
+    (zeros without response times), the largest e_q, M (N, 1), and the sum s (N,) of exp(e_q - M)."""
+    mu, sd, m0, m1, v = law
+    M = np.max(e, axis=1, keepdims=True)
+    p = np.exp(e - M)
+    s = np.sum(p, axis=1)
+    w = p / s[:, None]
+    Z1, Z2 = w @ z, w @ (z * z)
+    E, V = mu + sd * Z1, np.maximum(sd * sd * (Z2 - Z1 * Z1), 0.0)
+    c0, c1, u = 0.0, 0.0, 0.0
+    if rt:
+        P, R0, R1 = sums
+        c0, c1, u = (m0 + v * R0) / (1 + v * P), (m1 - v * R1) / (1 + v * P), v / (1 + v * P)
+    return E, V, c0, c1, u, M, s
+
+
 def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal") -> OutputScores:
     """scoreRespondents with numpy (the test twin of score_kernel), written beside marginalLogLikHost: the rule's weights at every row, the moments of theta, the
     zeta conditional, and the rows joined in two passes (the means, then the deviations from them)."""
@@ -856,17 +873,8 @@ def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="eq
     Q, wt = _lib.marginal_nodes(nodes), _lib.score_weighting(weighting)
     rt = _lib.MODEL_TRAITS[model].rt
     E, V, Ez, Vz, Cz, l, S = ([] for _ in range(7))
-    for e, z, (mu, sd, m0, m1, v), sums in _marginal_rows_host(model, Y, logT, X, rows, Q):
-        M = np.max(e, axis=1, keepdims=True)
-        p = np.exp(e - M)
-        s = np.sum(p, axis=1)
-        w = p / s[:, None]
-        Z1, Z2 = w @ z, w @ (z * z)
-        Es, Vs = mu + sd * Z1, np.maximum(sd * sd * (Z2 - Z1 * Z1), 0.0)
-        c0, c1, u = 0.0, 0.0, 0.0
-        if rt:
-            P, R0, R1 = sums
-            c0, c1, u = (m0 + v * R0) / (1 + v * P), (m1 - v * R1) / (1 + v * P), v / (1 + v * P)
+    for e, z, law, sums in _marginal_rows_host(model, Y, logT, X, rows, Q):
+        Es, Vs, c0, c1, u, M, s = _row_moments(e, z, law, sums, rt)
         for lst, val in zip((E, V, Ez, Vz, Cz, l, S), (Es, Vs, c0 + c1 * Es, u + c1 * c1 * Vs, c1 * Vs, M[:, 0] + np.log(s), s)):
             lst.append(val)
     E, V, Ez, Vz, Cz, l, S = (np.array(a) for a in (E, V, Ez, Vz, Cz, l, S))             # (R, N)
@@ -946,17 +954,8 @@ def plausibleValuesHost(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_S
     theta, zeta, node, gap = np.empty((N, K)), np.full((N, K), np.nan), np.empty((N, K), dtype=np.int32), np.empty((N, K))
     Ek, Vk = np.empty((N, K)), np.empty((N, K))
     coarse = np.zeros(N, dtype=bool)
-    for r, (e, z, (mu, sd, m0, m1, v), sums) in zip(used, _marginal_rows_host(model, Y, logT, X, rows[used], Q)):
-        M = np.max(e, axis=1, keepdims=True)
-        p = np.exp(e - M)
-        s = np.sum(p, axis=1)
-        w = p / s[:, None]
-        Z1, Z2 = w @ z, w @ (z * z)
-        E, V = mu + sd * Z1, np.maximum(sd * sd * (Z2 - Z1 * Z1), 0.0)
-        c0, c1, u = 0.0, 0.0, 0.0
-        if rt:
-            P, R0, R1 = sums
-            c0, c1, u = (m0 + v * R0) / (1 + v * P), (m1 - v * R1) / (1 + v * P), v / (1 + v * P)
+    for r, (e, z, law, sums) in zip(used, _marginal_rows_host(model, Y, logT, X, rows[used], Q)):
+        (mu, sd), (E, V, c0, c1, u, _, s) = law[:2], _row_moments(e, z, law, sums, rt)
         coarse |= s < 2.0
         ks = np.nonzero(rk == r)[0]
         w0 = _philox4x32_10(ii[:, None, None], ks[None, :, None], np.arange(Q)[None, None, :], site, seed, seed >> 32)[0]      # (N, draws, Q)
