@@ -5,7 +5,7 @@ Export list mirrors the part of /root/reference/src/ExtendedRtIrtModeling.jl:33-
 from .base import InputData, InputData4R, InputPara, OutputDic, OutputLoo, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions, setCond
 from .gibbs import (GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCross, GibbsRtIrtCrossQr, GibbsRtIrtLatent, GibbsRtIrtLatentQr, GibbsRtIrtNull,
                     GibbsRtIrtQuantile, checkConvergence, coef, ess_rhat, rank_ess_rhat, getDic, getDicHost, simulateData, getWaic, getWaicHost, compareWaic, pointwiseLogLikHost, getWaicMarginal, getWaicMarginalHost, marginalLogLikHost, getPpc, getPpcHost,
-                    getScores, scoreRespondents, scoresHost, getPlausibleValues, drawPlausibleValues, plausibleValuesHost, getLooMarginal, getLooMarginalHost, psisLoo, psisLooHost, compareLoo,
+                    getScores, scoreRespondents, scoresHost, getPlausibleValues, drawPlausibleValues, plausibleValuesHost, getLooMarginal, getLooMarginalHost, getWaicMarginalQr, getWaicMarginalQrHost, getLooMarginalQr, getLooMarginalQrHost, quantileMarginalLogLikHost, psisLoo, psisLooHost, compareLoo,
                     getLogLikelihood, precis, sample, sample_b)
 from .simtools import (comparePara, getBias, getMetrics, getMetrics2, getRmse, runSimulation, setDataMlIrt, setDataRtIrt, setDataRtIrtCross,
                        setDataRtIrtLatent, setDataRtIrtNull,
@@ -17,6 +17,6 @@ __all__ = [
     "setDataMlIrt", "setDataRtIrt", "setDataRtIrtCross", "setDataRtIrtLatent", "setDataRtIrtNull", "runSimulation", "getMetrics", "getMetrics2",
     "comparePara",
     "setTrueParaMlIrt", "setTrueParaRtIrt", "setTrueParaRtIrtCross", "setTrueParaRtIrtLatent",
-    "getBias", "getRmse", "getDic", "getDicHost", "getWaic", "getWaicHost", "compareWaic", "pointwiseLogLikHost", "getWaicMarginal", "getWaicMarginalHost", "marginalLogLikHost", "OutputWaic", "getScores", "scoreRespondents", "scoresHost", "OutputScores", "getPlausibleValues", "drawPlausibleValues", "plausibleValuesHost", "OutputPv", "getLooMarginal", "getLooMarginalHost", "psisLoo", "psisLooHost", "compareLoo", "OutputLoo", "getPpc", "getPpcHost", "OutputPpc", "checkConvergence", "ess_rhat", "rank_ess_rhat", "simulateData", "getLogLikelihood", "sample_b", "sample",
+    "getBias", "getRmse", "getDic", "getDicHost", "getWaic", "getWaicHost", "compareWaic", "pointwiseLogLikHost", "getWaicMarginal", "getWaicMarginalHost", "marginalLogLikHost", "OutputWaic", "getScores", "scoreRespondents", "scoresHost", "OutputScores", "getPlausibleValues", "drawPlausibleValues", "plausibleValuesHost", "OutputPv", "getLooMarginal", "getLooMarginalHost", "getWaicMarginalQr", "getWaicMarginalQrHost", "getLooMarginalQr", "getLooMarginalQrHost", "quantileMarginalLogLikHost", "psisLoo", "psisLooHost", "compareLoo", "OutputLoo", "getPpc", "getPpcHost", "OutputPpc", "checkConvergence", "ess_rhat", "rank_ess_rhat", "simulateData", "getLogLikelihood", "sample_b", "sample",
     "GibbsMlIrt", "GibbsRtIrt", "GibbsRtIrtCrossQr", "GibbsRtIrtLatentQr", "GibbsRtIrtQuantile", "GibbsRtIrtNull", "GibbsRtIrtCross", "GibbsRtIrtLatent", "coef", "precis",
 ]

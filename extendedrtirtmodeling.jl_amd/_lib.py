@@ -70,6 +70,8 @@ EXPORTS = [
     "erm_get_scores", "erm_farm_get_scores", "erm_score",
     "erm_get_marginal_loo", "erm_farm_get_marginal_loo", "erm_psis_loo",
     "erm_get_plausible_values", "erm_farm_get_plausible_values", "erm_plausible_values",
+    "erm_get_quantile_marginal_waic", "erm_farm_get_quantile_marginal_waic", "erm_get_quantile_marginal_loo", "erm_farm_get_quantile_marginal_loo",
+    "erm_quantile_marginal_loglik",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -221,6 +223,12 @@ def load():
     lib.erm_farm_get_plausible_values.argtypes = [H, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erm_plausible_values.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                          C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_get_quantile_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_quantile_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erm_get_quantile_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.erm_farm_get_quantile_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.erm_quantile_marginal_loglik.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -231,6 +239,7 @@ def check(rc: int):
 
 
 MARGINAL_MODELS = (MODEL_MLIRT, MODEL_RTIRT, MODEL_NULL, MODEL_CROSS, MODEL_LATENT)      # the models erm_get_marginal_waic serves (no quantile weights)
+QUANTILE_MARGINAL_MODELS = (MODEL_LATENTQR,)      # the model erm_get_quantile_marginal_waic serves (nu integrated out with theta and zeta)
 MARGINAL_NODES = 61
 
 
@@ -423,6 +432,15 @@ class _ItemPasses:
         """erm_get_marginal_loo / erm_farm_get_marginal_loo: Pareto-smoothed leave-one-subject-out on the marginal log-likelihoods, computed on the device from the
         resident item trace after the run.  Returns a dict of out12; pointwise=True adds elpd_u, p_u, khat, nEff [n_subj]."""
         return _loo_call(self._pass("marginal_loo"), self._h, nodes, self.cfg.n_subj, pointwise)
+
+    def quantile_marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_get_quantile_marginal_waic / erm_farm_get_quantile_marginal_waic: marginal_waic for a LatentQr engine or farm, with the quantile weights integrated
+        out too, at its q_rt.  The same outputs."""
+        return _marginal_call(self._pass("quantile_marginal_waic"), self._h, nodes, self.cfg.n_subj, pointwise)
+
+    def quantile_marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
+        """erm_get_quantile_marginal_loo / erm_farm_get_quantile_marginal_loo: marginal_loo for a LatentQr engine or farm.  The same outputs."""
+        return _loo_call(self._pass("quantile_marginal_loo"), self._h, nodes, self.cfg.n_subj, pointwise)
 
     def scores(self, nodes=MARGINAL_NODES):
         """erm_get_scores / erm_farm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on
@@ -804,6 +822,20 @@ def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=Tru
     lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
     ptr = lambda a: None if a is None else a.ctypes.data
     check(load().erm_marginal_loglik(*_caller_head(device, model, arrays, (N, J, F, R)), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
+    res = dict(l=l)
+    if want_waic:
+        res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
+    return res
+
+
+def quantile_marginal_loglik(model, Y, logT, X, rows, q_rt, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
+    """erm_quantile_marginal_loglik: marginal_loglik for LatentQr rows (Latent's layout) at the quantile level q_rt, nu integrated out.  The same dict."""
+    arrays, (N, J, F, R) = _caller_data(model, Y, logT, X, rows)
+    l = np.empty((N, R), dtype=np.float64, order="F") if want_l else None
+    out = np.empty(10, dtype=np.float64) if want_waic else None
+    lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    check(load().erm_quantile_marginal_loglik(*_caller_head(device, model, arrays, (N, J, F, R)), float(q_rt), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
     res = dict(l=l)
     if want_waic:
         res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)

@@ -1,6 +1,7 @@
 // erm_item_pass.hpp -- the host path of the passes that run after sampling from a data set and a table of item-trace rows: the marginal WAIC, the
 // marginal PSIS-LOO, the scores and the plausible values.  Each of erm_get_* / erm_farm_get_* (four each) and erm_marginal_loglik / erm_score / erm_plausible_values
-// is its own argument checks, ONE source maker (item_source) and ONE product call (item_waic / item_loo / item_scores / item_pv).
+// is its own argument checks, ONE source maker (item_source) and ONE product call (item_waic / item_loo / item_scores / item_pv).  The five entries of LatentQr's
+// marginal WAIC and LOO (erm_get_quantile_marginal_* and erm_quantile_marginal_loglik) are the same makers and products for FAMILY_QUANTILE.
 //
 // The first half is plain C++: the facts of a pass as one table, the refusals built from it and the chunk rule; g++ compiles this half with
 // -fsanitize=undefined -ftrapv into tests/item_pass_check (tests/test_item_pass_host.py).
@@ -14,6 +15,9 @@
 namespace erm {
 
 enum ItemPass { PASS_WAIC = 0, PASS_LOO, PASS_SCORES, PASS_PV, N_ITEM_PASSES };
+// the family of models an entry serves: the five without quantile weights (zeta's integral is Gaussian: erm_marginal.hpp), or LatentQr with nu integrated out
+// (erm_qmarginal.hpp: the marginal WAIC and LOO only)
+enum ItemFamily { FAMILY_GAUSSIAN = 0, FAMILY_QUANTILE };
 // noun: the pass as its refusals name it; engine_rows: the fewest post-burn-in rows an engine must hold (0: the pass has limits of its own -- PSIS-LOO's
 // 25 .. 8192); farm_rows: the fewest every chain of a farm must hold; need: what the refusal of too few rows asks for
 struct ItemPassFacts { const char* noun; bool plural; int engine_rows, farm_rows; const char* need; };
@@ -51,12 +55,24 @@ namespace {      // (as ertirt.hip's own: EngineBase names ItemSource)
 
 // ---- what marginal_kernel, score_kernel and pv_kernel share of a launch.  Everything a launch is given lives on the current device.
 // a data set as the kernels read it: row-major, C and X in the element type of `elem` bytes (float or double)
-struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; size_t elem; };
-static int marg_refuse_model(int model)
+// (q_rt: the quantile level, read for LatentQr only)
+struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; size_t elem; double q_rt; };
+static int marg_refuse_crossqr()
 {
+    return fail(ERM_ERR_ARG, "CrossQr is not served: with the quantile weights nu_ij integrated out every cell's response time is asymmetric Laplace in zeta, "
+                             "so the zeta integral is piecewise with J kinks that move with theta and has no closed form");
+}
+// what the entries of a family refuse: the other family's models, by name of the entry that serves them
+static int marg_refuse_model(int model, int family = FAMILY_GAUSSIAN)
+{
+    if (family == FAMILY_QUANTILE) {
+        if (model == ERM_MODEL_CROSSQR) return marg_refuse_crossqr();
+        if (marg_served(model)) return fail(ERM_ERR_ARG, "the quantile entries serve LatentQr only: this model has no quantile weights, use erm_get_marginal_waic / erm_get_marginal_loo / erm_marginal_loglik");
+        return qmarg_served(model) ? 0 : fail(ERM_ERR_ARG, "unknown model");
+    }
     if (model == ERM_MODEL_CROSSQR || model == ERM_MODEL_LATENTQR)
-        return fail(ERM_ERR_ARG, "the marginal WAIC serves the five models without quantile weights: with nu integrated out the response-time term is no longer "
-                                 "Gaussian in zeta and the zeta integral has no closed form");
+        return fail(ERM_ERR_ARG, "this entry serves the five models without quantile weights: with nu integrated out the response-time term is no longer Gaussian in zeta "
+                                 "(LatentQr: the zeta integral is that of erm_get_quantile_marginal_waic / erm_get_quantile_marginal_loo; CrossQr: it has no closed form)");
     if (!marg_served(model)) return fail(ERM_ERR_ARG, "unknown model");
     return 0;
 }
@@ -71,7 +87,7 @@ static int marg_nodes(int32_t n_nodes, int* Q)
 static MargArgs marg_args(const MargData& D, const double* rows, int64_t n_rows, int Q)
 {
     MargArgs a{};
-    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = item_trace_width(D.model, D.J, D.Fk); a.N = D.N; a.J = D.J; a.F = D.Fk; a.Q = Q;
+    a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = item_trace_width(D.model, D.J, D.Fk); a.N = D.N; a.J = D.J; a.F = D.Fk; a.Q = Q; a.q = D.q_rt;
     return a;
 }
 static size_t marg_lds(const MargArgs& a) { return (size_t)2 * marg_row_lds(a.ld, a.J) * sizeof(double); }
@@ -114,6 +130,8 @@ static int marginal_launch(const MargData& D, const double* rows, int64_t n_rows
 {
     MargArgs a = marg_args(D, rows, n_rows, Q);
     a.l_out = l_dev; a.acc_ms = acc_ms; a.acc_w = acc_w; a.coarse = coarse;
+    if (D.model == ERM_MODEL_LATENTQR)      // the one kernel LatentQr has (a source of FAMILY_QUANTILE; marg_dispatch's kernels refuse the model)
+        return D.elem == sizeof(float) ? marg_tile_launch(&marginal_kernel<LATENTQR, float>, a, stream) : marg_tile_launch(&marginal_kernel<LATENTQR, double>, a, stream);
     return marg_dispatch(D, [&](auto M, auto real) { return marg_tile_launch(&marginal_kernel<decltype(M)::value, decltype(real)>, a, stream); });
 }
 
@@ -198,16 +216,16 @@ struct ItemSource {
 };
 // an engine's resident data set and its own post-burn-in rows, read in place (EngineBase::item_source: the refusals of a shard, a poisoned state, no data set and
 // too few rows, in this order, after the model's)
-static int item_source(erm_handle h, int pass, ItemSource& S)
+static int item_source(erm_handle h, int pass, ItemSource& S, int family = FAMILY_GAUSSIAN)
 {
-    if (int rc = marg_refuse_model(h->e->cfg.model)) return rc;
+    if (int rc = marg_refuse_model(h->e->cfg.model, family)) return rc;
     return h->e->item_source(pass, S);
 }
 // a farm's: the post-burn-in item-trace rows of chain 0, chain 1, ... as ONE table on chain 0's device, whose resident data set supplies the data.  A chain's rows
 // cross through the host whatever its device (item-level: a few hundred kilobytes); a farm of one chain takes the same path as several.
-static int item_source(erm_farm_handle f, int pass, ItemSource& S)
+static int item_source(erm_farm_handle f, int pass, ItemSource& S, int family = FAMILY_GAUSSIAN)
 {
-    if (int rc = marg_refuse_model(f->cfg.model)) return rc;
+    if (int rc = marg_refuse_model(f->cfg.model, family)) return rc;
     const int L = (int)f->eng.size();
     const EngineBase* e0 = f->eng[0]->e.get();
     const int64_t wi = e0->item_trace_width(), rows = e0->rows_done, post = e0->post_rows;
@@ -227,12 +245,13 @@ static int item_source(erm_farm_handle f, int pass, ItemSource& S)
     if (int rc = S.dRows.try_alloc(table.size() * sizeof(double), "the farm's table of item-trace rows")) return rc;
     H2D(S.dRows.p, table.data(), table.size() * sizeof(double));
     S.rows = S.dRows.as<double>(); S.n_rows = (int64_t)L * post;
-    return item_source(f->eng[0].get(), pass, S);
+    return item_source(f->eng[0].get(), pass, S, family);
 }
 // caller-supplied data and rows (erm_marginal_loglik, erm_score, erm_plausible_values): validated on the host, then uploaded to `device` row-major in fp64, as the
-// kernels read an engine's, for the NULL stream.  min_rows / rows_msg: the fewest rows the caller's outputs need.
+// kernels read an engine's, for the NULL stream.  min_rows / rows_msg: the fewest rows the caller's outputs need.  FAMILY_QUANTILE (the model is LatentQr): q_rt is
+// the quantile level, and every row's Sigma_p[2,2], the scale of zeta's law, must be positive.
 static int item_source(const char* what, int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
-                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, ItemSource& S)
+                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, ItemSource& S, int family = FAMILY_GAUSSIAN, double q_rt = 0.0)
 {
     const ModelTraits mt = model_traits(model);
     if (n_subj <= 0 || n_subj >= (1LL << 32) || n_item <= 0 || n_item > 896 || n_feat < 0 || n_feat > MARG_MAXF) return fail(ERM_ERR_ARG, "n_subj, n_item (1 .. 896) or n_feat (0 .. " + std::to_string(MARG_MAXF) + ") out of range");
@@ -241,6 +260,7 @@ static int item_source(const char* what, int device, int model, int64_t n_subj, 
     if (mt.rt && !logT) return fail(ERM_ERR_ARG, "logT is required for response-time models");
     if (Fk > 0 && !X) return fail(ERM_ERR_ARG, "X is required when n_feat > 0");
     if (n_rows < min_rows) return fail(ERM_ERR_ARG, rows_msg);
+    if (family == FAMILY_QUANTILE && !qmarg_level_ok(q_rt)) return fail(ERM_ERR_ARG, "q_rt must be inside (0, 1)");
     const int64_t wi = item_trace_width(model, J, Fk);
     const size_t NJ = (size_t)N * J;
     // ---- the inputs: a NaN anywhere, then rows outside the model's domain
@@ -253,6 +273,7 @@ static int item_source(const char* what, int device, int model, int64_t n_subj, 
         for (int j = 0; j < J; ++j) if (!(row[3 * J + j] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": sig2t must be positive");
         const double* Sp = row + 4 * J + qr_sigp_off(model, J, Fk);
         if (!(Sp[0] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": Sigma_p[1,1] must be positive");
+        if (family == FAMILY_QUANTILE && !(Sp[3] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": Sigma_p[2,2] must be positive");
         if (marg_law(model, 0.0, 0.0, 0.0, Sp).v < 0.0) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": the conditional variance of zeta given theta is negative (Sigma_p is not positive semi-definite)");
     }
     HIPCHK(hipSetDevice(device));
@@ -277,7 +298,7 @@ static int item_source(const char* what, int device, int model, int64_t n_subj, 
     }
     if (int rc = S.dRows.try_alloc((size_t)n_rows * wi * sizeof(double), what)) return rc;
     H2D(S.dRows.p, rows, (size_t)n_rows * wi * sizeof(double));
-    S.D = MargData{S.dY.as<uint8_t>(), S.dC.p, S.dX.p, nullptr, N, J, Fk, model, sizeof(double)};
+    S.D = MargData{S.dY.as<uint8_t>(), S.dC.p, S.dX.p, nullptr, N, J, Fk, model, sizeof(double), q_rt};
     S.rows = S.dRows.as<double>(); S.n_rows = n_rows;
     return 0;
 }

@@ -29,7 +29,7 @@ constexpr double MARG_COARSE_S = 2.0;
 constexpr double MARG_LOG_2PI = 1.8378770664093454836;
 
 constexpr bool marg_nodes_ok(int Q) { return Q >= MARG_NODES_MIN && Q <= MARG_NODES_MAX && (Q & 1) == 1; }
-// the models whose zeta integral is Gaussian (the quantile models' is not: nu would have to be integrated out with it)
+// the models whose zeta integral is Gaussian (the quantile models' is not: nu has to be integrated out with it -- LatentQr: erm_qmarginal.hpp)
 constexpr bool marg_served(int model) { return model == MLIRT || model == RTIRT || model == NULLM || model == CROSS || model == LATENT; }
 
 struct MargLaw { double mu, sd, m0, m1, v; };
@@ -46,7 +46,7 @@ ERM_MG_FN MargLaw marg_law(int model, double xb0, double xb1, double bth, const 
 {
     if (model == MLIRT) return {xb0, 1.0, 0.0, 0.0, 0.0};
     const double s11 = S[0], s12 = 0.5 * (S[1] + S[2]), s22 = S[3];
-    if (model == LATENT) return {0.0, sqrt(s11), xb0, bth, s22};
+    if (model == LATENT || model == LATENTQR) return {0.0, sqrt(s11), xb0, bth, s22};      // (LatentQr: v is the scale of zeta's asymmetric Laplace law)
     const double m1 = s12 / s11;
     return {model == RTIRT ? xb0 : 0.0, sqrt(s11), model == RTIRT ? xb1 - m1 * xb0 : 0.0, m1, s22 - s12 * s12 / s11};
 }

@@ -18,9 +18,12 @@
 // The covariates of the subject stay in registers across the rows.  Plain vector loads and stores, no atomics: every output word has one writer.
 // Steps 1 to 3 are __device__ helpers (marg_stage, marg_load_x, marg_stage_law, marg_item_sums, marg_lane_nodes) that score_kernel (erm_score_kernels.hpp) and
 // pv_kernel (erm_pv_kernels.hpp) call too.
+// MODEL = LATENTQR is the same kernel with the quantile weight nu_i integrated out as well: Latent's law with v read as the scale of zeta's asymmetric
+// Laplace law, and qmarg_T (erm_qmarginal.hpp) at the level MargArgs::q in the place of marg_T.  marginal_kernel alone is instantiated for it.
 #pragma once
 #include <type_traits>
 #include "erm_marginal.hpp"
+#include "erm_qmarginal.hpp"
 #include "erm_pointwise.hpp"
 
 namespace erm {
@@ -35,6 +38,7 @@ struct MargArgs {
     double* l_out;                                        // [n_rows][N] (the caller's column-major [N][n_rows]) or nullptr
     double2* acc_ms; double2* acc_w;                      // [N] or nullptr
     unsigned int* coarse;                                 // [N]: 1 if S < MARG_COARSE_S at any row; or nullptr
+    double q;                                             // LatentQr: the quantile level q_rt of qmarg_T (erm_qmarginal.hpp); unread otherwise
 };
 // doubles of LDS per half of the row buffer: the row | g [J] | log sig2t [J]
 __host__ __device__ constexpr long long marg_row_lds(long long ld, int J) { return ld + 2 * (long long)J; }
@@ -104,9 +108,11 @@ __device__ __forceinline__ void marg_item_sums(const MargArgs& A, const double* 
         }
     }
 }
-// nodes: lane s, nodes s, s + 8, ... in chunks of MARG_CHUNK; sink(e_q, z_q) -- or sink(e_q, z_q, q) if it takes the node's index too -- receives the lane's nodes in order
+// nodes: lane s, nodes s, s + 8, ... in chunks of MARG_CHUNK; sink(e_q, z_q) -- or sink(e_q, z_q, q) if it takes the node's index too -- receives the lane's nodes in order.
+// LatentQr takes qmarg_T at the level q_rt for marg_T: two logPhi per node beside the J evaluations of log(1 + e^eta)
 template <int MODEL, typename Sink>
-__device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, int s, double h, double log_h, const MargLaw& w, const MargSums& ms, double A1, double A0, Sink&& sink)
+__device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, int s, double h, double log_h, const MargLaw& w, const MargSums& ms, double A1, double A0, Sink&& sink,
+                                                double q_rt = 0.0)
 {
     for (int q0 = s; q0 < Q; q0 += MARG_LANES * MARG_CHUNK) {
         double th[MARG_CHUNK], lse[MARG_CHUNK];
@@ -127,7 +133,8 @@ __device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, 
             if (qq < Q) {
                 const double z = marg_node(qq, h);
                 double e = marg_log_weight(z, log_h) + (th[c] * A1 - A0 - lse[c]);
-                if constexpr (MODEL != MLIRT) e += marg_T(ms, J, w, th[c]);
+                if constexpr (MODEL == LATENTQR) e += qmarg_T(ms, J, w, th[c], q_rt);
+                else if constexpr (MODEL != MLIRT) e += marg_T(ms, J, w, th[c]);
                 if constexpr (std::is_invocable_v<Sink, double, double, int>) sink(e, z, qq);
                 else sink(e, z);
             }
@@ -165,7 +172,7 @@ __global__ void __launch_bounds__(256) marginal_kernel(const MargArgs A)
         double A1, A0;
         marg_item_sums<MODEL, real>(A, sa, Yi, Ci, s, ms, A1, A0);
         MargMS part{0.0, 0.0};
-        marg_lane_nodes<MODEL>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double) { marg_ms_add(part, e); });
+        marg_lane_nodes<MODEL>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double) { marg_ms_add(part, e); }, A.q);
         for (int m = 1; m < MARG_LANES; m <<= 1) {
             const MargMS o{__shfl_xor(part.M, m, 64), __shfl_xor(part.S, m, 64)};
             part = marg_ms_merge(part, o);

@@ -1733,7 +1733,7 @@ template <typename real> int Engine<real>::item_source(int pass, ItemSource& S)
         S.rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); S.n_rows = post_rows;
     }
     HIPCHK(hipSetDevice(cfg.device));
-    S.D = MargData{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model, sizeof(real)};
+    S.D = MargData{dY.as<uint8_t>(), dC.p, dX.p, is_rt() ? dCst.as<double>() + cst_off_m(J) : nullptr, N, J, Fk, cfg.model, sizeof(real), cfg.q_rt};
     S.stream = stream;
     return 0;
 }
@@ -1750,20 +1750,20 @@ static int pv_entry_args(int32_t n_nodes, int32_t n_draws, const double* pv, int
     return 0;
 }
 // erm_get_* (H = erm_handle) and erm_farm_get_* (H = erm_farm_handle) of the four passes: the checks, the source, the product
-template <typename H> static int get_marginal_waic(H h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u)
+template <typename H> static int get_marginal_waic(H h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u, int family = FAMILY_GAUSSIAN)
 {
     int Q = 0;
     ItemSource S;
     if (int rc = item_entry_args(out10, n_nodes, &Q)) return rc;
-    if (int rc = item_source(h, PASS_WAIC, S)) return rc;
+    if (int rc = item_source(h, PASS_WAIC, S, family)) return rc;
     return item_waic(S, Q, nullptr, out10, lppd_u, p_u);
 }
-template <typename H> static int get_marginal_loo(H h, int32_t n_nodes, double* out12, double* pw)
+template <typename H> static int get_marginal_loo(H h, int32_t n_nodes, double* out12, double* pw, int family = FAMILY_GAUSSIAN)
 {
     int Q = 0;
     ItemSource S;
     if (int rc = item_entry_args(out12, n_nodes, &Q)) return rc;
-    if (int rc = item_source(h, PASS_LOO, S)) return rc;
+    if (int rc = item_source(h, PASS_LOO, S, family)) return rc;
     return item_loo(S, Q, out12, pw);
 }
 template <typename H> static int get_scores(H h, int32_t n_nodes, double* score, double* out4)
@@ -1828,6 +1828,8 @@ int64_t erm_pointwise_units(erm_handle h) { return h ? h->e->pointwise_units() :
 int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u) { CHK_H; return h->e->get_pointwise(lppd_u, p_u); }
 int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_H; return get_marginal_waic(h, n_nodes, out10, lppd_u, p_u); }
 int erm_get_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw) { CHK_H; return get_marginal_loo(h, n_nodes, out12, pw); }
+int erm_get_quantile_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_H; return get_marginal_waic(h, n_nodes, out10, lppd_u, p_u, FAMILY_QUANTILE); }
+int erm_get_quantile_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw) { CHK_H; return get_marginal_loo(h, n_nodes, out12, pw, FAMILY_QUANTILE); }
 int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4) { CHK_H; return get_scores(h, n_nodes, score, out4); }
 int erm_get_plausible_values(erm_handle h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
@@ -2046,6 +2048,8 @@ int erm_farm_get_dic(erm_farm_handle f, double* out4)
 // the farm's passes over the item trace: the engine's, over the post-burn-in rows of all chains as one table on chain 0's device (erm_item_pass.hpp)
 int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_F; return get_marginal_waic(f, n_nodes, out10, lppd_u, p_u); }
 int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw) { CHK_F; return get_marginal_loo(f, n_nodes, out12, pw); }
+int erm_farm_get_quantile_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_F; return get_marginal_waic(f, n_nodes, out10, lppd_u, p_u, FAMILY_QUANTILE); }
+int erm_farm_get_quantile_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw) { CHK_F; return get_marginal_loo(f, n_nodes, out12, pw, FAMILY_QUANTILE); }
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4) { CHK_F; return get_scores(f, n_nodes, score, out4); }
 int erm_farm_get_plausible_values(erm_farm_handle f, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
@@ -2077,6 +2081,19 @@ int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, i
     ItemSource S;
     if (int rc = item_source("erm_marginal_loglik's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, out10 || lppd_u || p_u ? 2 : 1,
                              "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S)) return rc;
+    return item_waic(S, Q, l, out10, lppd_u, p_u);
+}
+
+// LatentQr's: the same path with the quantile family's checks and the caller's q_rt
+int erm_quantile_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                                 int64_t n_rows, double q_rt, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u)
+{
+    if (int rc = marg_refuse_model(model, FAMILY_QUANTILE)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    ItemSource S;
+    if (int rc = item_source("erm_quantile_marginal_loglik's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, out10 || lppd_u || p_u ? 2 : 1,
+                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S, FAMILY_QUANTILE, q_rt)) return rc;
     return item_waic(S, Q, l, out10, lppd_u, p_u);
 }
 

@@ -579,7 +579,7 @@ def _marginal_source(MCMC, who="getWaicMarginal"):
 def _marginal_check(MCMC, nodes, who="getWaicMarginal"):
     if MCMC._model not in _lib.MARGINAL_MODELS:
         raise ValueError(f"{who} is not available for {type(MCMC).__name__}: with the quantile weights integrated out the response-time term is not Gaussian in "
-                         "zeta and the zeta integral has no closed form")
+                         "zeta (GibbsRtIrtLatentQr: getWaicMarginalQr / getLooMarginalQr; GibbsRtIrtCrossQr: the zeta integral has no closed form)")
     if MCMC.shard is not None:
         raise ValueError(f"{who} is not available for a subject-sharded sampler (every subject's data must be resident on one device)")
     return _lib.marginal_nodes(nodes)
@@ -696,6 +696,131 @@ def getWaicMarginalHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) 
     `rows`)."""
     L, Q, n_coarse = _marginal_loglik_host(MCMC, nodes, rows, "getWaicMarginal")
     return waicFromLogLik(L, nNodes=Q, nCoarse=n_coarse)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Marginal WAIC and PSIS-LOO of GibbsRtIrtLatentQr (DESIGN.md 7l; include/ertirt.h: erm_get_quantile_marginal_waic).  Unit = a subject with theta_i, zeta_i and the
+# quantile weight nu_i integrated out: nu turns zeta's law into an asymmetric Laplace one, zeta then integrates to two normal-CDF terms, theta goes by the same rule.
+# ------------------------------------------------------------------------------------------------------------------
+_QMARG_SERIES_X = -36.0
+
+
+def _qmarg_log_ndtr(x):
+    """log Phi(x) in the three arms of csrc/erm_qmarginal.hpp (qmarg_log_ndtr), restated with scipy's erfc: x >= 0: log1p(-erfc(x / sqrt 2) / 2);
+    -36 <= x < 0: log(erfc(-x / sqrt 2) / 2); x < -36: -x^2 / 2 - log(-x) - 1/2 log 2 pi + log1p(-r + 3 r^2 - ... + 2027025 r^8), r = 1 / x^2."""
+    from scipy.special import erfc
+    x = np.asarray(x, dtype=np.float64)
+    out = np.empty_like(x)
+    hi, lo = x >= 0.0, x < _QMARG_SERIES_X
+    mid = ~hi & ~lo
+    out[hi] = np.log1p(-0.5 * erfc(x[hi] * np.sqrt(0.5)))
+    out[mid] = np.log(0.5 * erfc(-x[mid] * np.sqrt(0.5)))
+    xl = x[lo]
+    r = 1.0 / (xl * xl)
+    p = np.full_like(r, 2027025.0)
+    for c in (-135135.0, 10395.0, -945.0, 105.0, -15.0, 3.0, -1.0):
+        p = c + r * p
+    out[lo] = -0.5 * xl * xl - np.log(-xl) - 0.5 * np.log(2 * np.pi) + np.log1p(r * p)
+    return out
+
+
+def _qmarginal_check(MCMC, nodes, who):
+    if MCMC._model not in _lib.QUANTILE_MARGINAL_MODELS:
+        if MCMC._model in _lib.MARGINAL_MODELS:
+            raise ValueError(f"{who} is for GibbsRtIrtLatentQr: {type(MCMC).__name__} has no quantile weights, use {who[:-2]}")
+        raise ValueError(f"{who} is not available for {type(MCMC).__name__}: with the quantile weights nu_ij integrated out every cell's response time is asymmetric "
+                         "Laplace in zeta, and the zeta integral (J kinks that move with theta) has no closed form")
+    if MCMC.shard is not None:
+        raise ValueError(f"{who} is not available for a subject-sharded sampler (every subject's data must be resident on one device)")
+    return _lib.marginal_nodes(nodes)
+
+
+def quantileMarginalLogLikHost(model, Y, logT, X, rows, qRt, nodes=_lib.MARGINAL_NODES, with_S=False) -> np.ndarray:
+    """l_i^(s) of GibbsRtIrtLatentQr's marginal WAIC with numpy (the test twin of marginal_kernel<LATENTQR>): an (R, N) array for the item-trace rows
+    [R, item_trace_width] (Latent's layout) and the data Y, logT [N, J], X [N, F] or None at the quantile level qRt.  include/ertirt.h's definition restated:
+    theta by the rule of marginalLogLikHost, zeta | theta asymmetric Laplace (m0 + m1 theta, s = Sigma_p[2,2], qRt) integrated against the Gaussian response times
+    in closed form.  with_S=True also returns S per (row, subject)."""
+    from scipy.special import logsumexp
+    if model not in _lib.QUANTILE_MARGINAL_MODELS:
+        raise ValueError("quantileMarginalLogLikHost serves GibbsRtIrtLatentQr only")
+    q = float(qRt)
+    if not 0.0 < q < 1.0:
+        raise ValueError("qRt must be inside (0, 1)")
+    Q = _lib.marginal_nodes(nodes)
+    Y = np.asarray(Y, dtype=np.float64)
+    lt = np.asarray(logT, dtype=np.float64)
+    N, J = Y.shape
+    F = 0 if X is None else np.shape(X)[1]
+    x1 = np.ones((N, 1)) if F == 0 else np.hstack([np.ones((N, 1)), np.asarray(X, dtype=np.float64)])
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    if rows.shape[1] != _lib.item_trace_width(model, J, F):
+        raise ValueError(f"rows must have {_lib.item_trace_width(model, J, F)} columns")
+    h = 12.0 / (Q - 1)
+    z = -6.0 + h * np.arange(Q)
+    out, outS = np.empty((rows.shape[0], N)), np.empty((rows.shape[0], N))
+    for r, row in enumerate(rows):
+        a, b, lam, sg, qq = row[:J], row[J:2 * J], row[2 * J:3 * J], row[3 * J:4 * J], row[4 * J:]
+        s11, s = qq[-4], qq[-1]
+        if not (s > 0.0 and s11 > 0.0 and np.all(sg > 0.0)):
+            raise ValueError(f"row {r}: sig2t, Sigma_p[1,1] and Sigma_p[2,2] must be positive")
+        m0, m1 = x1 @ qq[:F + 1], qq[F + 1]
+        th = np.sqrt(s11) * z                                                         # (Q,)
+        eta = a[None, None, :] * (th[None, :, None] - b[None, None, :])               # (1, Q, J)
+        e = np.log(h) - 0.5 * np.log(2 * np.pi) - 0.5 * z[None, :] ** 2 + np.sum(Y[:, None, :] * eta - _log1pexp(eta), axis=2)
+        g = 1.0 / sg
+        d0 = lam[None, :] - lt
+        P, R0, D0, L = np.sum(g), np.sum(g * d0, axis=1)[:, None], np.sum(g * d0 * d0, axis=1)[:, None], np.sum(np.log(sg))
+        m = m0[:, None] + m1 * th[None, :]                                            # (N, Q)
+        bU, bL, rP = R0 - q / s, R0 + (1.0 - q) / s, np.sqrt(P)
+        up = bU * bU / (2.0 * P) + q * m / s + _qmarg_log_ndtr(-(m - bU / P) * rP)
+        lo = bL * bL / (2.0 * P) - (1.0 - q) * m / s + _qmarg_log_ndtr((m - bL / P) * rP)
+        e = e - 0.5 * J * np.log(2 * np.pi) - 0.5 * L - 0.5 * D0 + np.log(q * (1.0 - q) / s) + 0.5 * (np.log(2 * np.pi) - np.log(P)) + np.logaddexp(up, lo)
+        out[r], outS[r] = logsumexp(e, axis=1), np.sum(np.exp(e - np.max(e, axis=1, keepdims=True)), axis=1)
+    return (out, outS) if with_S else out
+
+
+def getWaicMarginalQr(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, pointwise=False) -> OutputWaic:
+    """getWaicMarginal for GibbsRtIrtLatentQr (= GibbsRtIrtQuantile): the marginal WAIC with every subject's theta, zeta and quantile weight nu integrated out, at the
+    sampler's qRt, computed on the device (erm_get_quantile_marginal_waic / erm_farm_get_quantile_marginal_waic).  unit = "subject-marginal", so compareWaic takes
+    it against a GibbsRtIrtLatent fit of the same data, or against another qRt."""
+    Q = _qmarginal_check(MCMC, nodes, "getWaicMarginalQr")
+    r = _marginal_source(MCMC, "getWaicMarginalQr").quantile_marginal_waic(Q, pointwise=pointwise)
+    w, lppd_u, p_u = r if pointwise else (r, None, None)
+    return OutputWaic(elpd=w["elpd"], pWaic=w["pWaic"], WAIC=w["WAIC"], se=w["se"], nHighVar=w["nHighVar"], lppd=w["lppd"], unit=MARGINAL_UNIT, nUnits=w["nUnits"],
+                      nRows=w["nRows"], lppd_u=lppd_u, p_u=p_u, nNodes=w["nNodes"], nCoarse=w["nCoarse"])
+
+
+def getLooMarginalQr(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, pointwise=False) -> OutputLoo:
+    """getLooMarginal for GibbsRtIrtLatentQr: PSIS-LOO on the marginal log-likelihoods of getWaicMarginalQr, computed on the device
+    (erm_get_quantile_marginal_loo / erm_farm_get_quantile_marginal_loo).  Needs 25 .. 8192 post-burn-in rows."""
+    Q = _qmarginal_check(MCMC, nodes, "getLooMarginalQr")
+    _lib.psis_rows(_loo_rows(MCMC))
+    return _loo_output(_marginal_source(MCMC, "getLooMarginalQr").quantile_marginal_loo(Q, pointwise=pointwise), pointwise)
+
+
+def _qmarginal_loglik_host(MCMC, nodes, rows, who):
+    Q = _qmarginal_check(MCMC, nodes, who)
+    D = MCMC.Data
+    if D is None:
+        raise ValueError("Data is required")
+    rows = marginalRows(MCMC) if rows is None else rows
+    X = np.asarray(D.X, dtype=np.float64) if MCMC.Cond.nFeat > 0 else None
+    L, S = quantileMarginalLogLikHost(MCMC._model, D.Y, D.logT, X, rows, MCMC.Cond.qRt, Q, with_S=True)
+    return L, Q, int(np.sum(np.any(S < 2.0, axis=0)))
+
+
+def getWaicMarginalQrHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) -> OutputWaic:
+    """getWaicMarginalQr evaluated with numpy / scipy on the host (the test twin of the device path)."""
+    L, Q, n_coarse = _qmarginal_loglik_host(MCMC, nodes, rows, "getWaicMarginalQr")
+    return waicFromLogLik(L, nNodes=Q, nCoarse=n_coarse)
+
+
+def getLooMarginalQrHost(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, rows=None) -> OutputLoo:
+    """getLooMarginalQr evaluated with numpy on the host: quantileMarginalLogLikHost, then psisLooHost."""
+    L, Q, n_coarse = _qmarginal_loglik_host(MCMC, nodes, rows, "getLooMarginalQr")
+    out = psisLooHost(L)
+    out.unit, out.nNodes, out.nCoarse = MARGINAL_UNIT, Q, n_coarse
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getScores, scoreRespondents, getPlausibleValues, drawPlausibleValues, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getWaicMarginalQr, getLooMarginalQr, quantileMarginalLogLik, getScores, scoreRespondents, getPlausibleValues, drawPlausibleValues, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -432,6 +432,69 @@ function getLooMarginal(M::GibbsAMD; nodes::Integer = 61, pointwise::Bool = fals
         end
     end
     return looTuple(out, pw)
+end
+
+"""
+    getWaicMarginalQr(MCMC; nodes = 61, pointwise = false) -> the named tuple of `getWaicMarginal`
+
+The marginal WAIC of `GibbsRtIrtLatentQr` (= `GibbsRtIrtQuantile`): every subject's θ, ζ and quantile weight ν integrated out, at the sampler's `qRt`
+(`erm_get_quantile_marginal_waic`; after `sample!(MCMC; devices=...)` `erm_farm_get_quantile_marginal_waic`).  With ν gone ζ given θ is asymmetric Laplace, and
+its integral against the Gaussian response times is two normal-CDF terms.  The unit is the one of `getWaicMarginal`, so a `GibbsRtIrtLatent` fit and a
+`GibbsRtIrtLatentQr` fit of the same data -- or two levels `qRt` -- can be compared subject by subject.  Not for `GibbsRtIrtCrossQr`.
+"""
+function getWaicMarginalQr(M::GibbsAMD; nodes::Integer = 61, pointwise::Bool = false)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    out = zeros(10)
+    lppd_u, p_u = pointwise ? (zeros(M.Cond.nSubj), zeros(M.Cond.nSubj)) : (Float64[], Float64[])
+    pl, pp = pointwise ? (pointer(lppd_u), pointer(p_u)) : (Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL))
+    GC.@preserve lppd_u p_u begin
+        if farmed
+            check(ccall((:erm_farm_get_quantile_marginal_waic, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), M.farm, nodes, out, pl, pp))
+        else
+            check(ccall((:erm_get_quantile_marginal_waic, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), M.handle, nodes, out, pl, pp))
+        end
+    end
+    res = (elpd = out[1], pWaic = out[2], WAIC = out[3], se = out[4], lppd = out[5], nUnits = Int(out[6]), nRows = Int(out[7]), nHighVar = Int(out[8]),
+           nNodes = Int(out[9]), nCoarse = Int(out[10]))
+    return pointwise ? merge(res, (lppd_u = lppd_u, p_u = p_u)) : res
+end
+
+"""
+    getLooMarginalQr(MCMC; nodes = 61, pointwise = false) -> the named tuple of `getLooMarginal`
+
+The marginal PSIS-LOO of `GibbsRtIrtLatentQr` on the marginal log-likelihoods of `getWaicMarginalQr` (`erm_get_quantile_marginal_loo`,
+`erm_farm_get_quantile_marginal_loo`).  Needs 25 .. 8192 post-burn-in rows.
+"""
+function getLooMarginalQr(M::GibbsAMD; nodes::Integer = 61, pointwise::Bool = false)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    out = zeros(12)
+    pw = pointwise ? zeros(M.Cond.nSubj, 4) : zeros(0, 4)
+    pp = pointwise ? pointer(pw) : Ptr{Float64}(C_NULL)
+    GC.@preserve pw begin
+        if farmed
+            check(ccall((:erm_farm_get_quantile_marginal_loo, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.farm, nodes, out, pp))
+        else
+            check(ccall((:erm_get_quantile_marginal_loo, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.handle, nodes, out, pp))
+        end
+    end
+    return looTuple(out, pw)
+end
+
+"""
+    quantileMarginalLogLik(Y, logT, X, rows, qRt; nodes = 61, device = 0) -> l
+
+`marginalLogLik` for `GibbsRtIrtLatentQr` rows (Latent's layout) at the quantile level `qRt`, ν integrated out (`erm_quantile_marginal_loglik`).
+"""
+function quantileMarginalLogLik(Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}, qRt::Real; nodes::Integer = 61, device::Integer = 0)
+    N, J = size(Y)
+    R = size(rows, 2)
+    l = zeros(N, R)
+    check(ccall((:erm_quantile_marginal_loglik, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                device, MODEL_LATENTQR, N, J, size(X, 2), Y, logT, X, rows, R, qRt, nodes, l, C_NULL, C_NULL, C_NULL))
+    return l
 end
 
 """

@@ -222,7 +222,8 @@ int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u);
  * trace, which is always kept, in fp64, in both trace modes -- so everything is computed AFTER the run from resident state: no pass behind the sweep, no erm_set_pointwise,
  * no change to any schedule, and the calls only read the engine (the chain, the traces and the accumulators of erm_get_waic are unchanged by them).
  * Served: GibbsMlIrt, GibbsRtIrt, GibbsRtIrtNull, GibbsRtIrtCross, GibbsRtIrtLatent.  The two quantile models are refused with ERM_ERR_ARG: with nu integrated out the
- * response-time term is no longer Gaussian in zeta and the zeta integral has no closed form.
+ * response-time term is no longer Gaussian in zeta.  GibbsRtIrtLatentQr has entries of its own, erm_get_quantile_marginal_waic below; for GibbsRtIrtCrossQr the
+ * zeta integral has no closed form.
  * Definition, for subject i at row s; items j = 1..J, y_j in {0,1}, t_j = logT_ij, x = the subject's covariates, S = Sigma_p with S12 read as (Sigma_p[1] + Sigma_p[2]) / 2.
  *   Population law -- the structural term of the model's own getLogLikelihood*:  theta ~ N(mu, S11'),  zeta | theta ~ N(m0 + m1 theta, v)
  *     MlIrt         mu = beta0 + x beta, S11' = 1; no zeta, no response times
@@ -261,6 +262,40 @@ int erm_get_pointwise(erm_handle h, double* lppd_u, double* p_u);
 int erm_get_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);
 int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                         int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u);
+
+/* Marginal WAIC and PSIS-LOO of GibbsRtIrtLatentQr (= GibbsRtIrtQuantile): the unit is a subject with theta_i, zeta_i AND the quantile weight nu_i integrated out,
+ * so a Latent fit and a LatentQr fit of the same data -- or two levels q_rt -- are compared in the same unit, "subject-marginal".  Entries of their own, because
+ * every entry above refuses the quantile models; computed after the run from resident state, exactly as erm_get_marginal_waic is.
+ * Served: LatentQr only.  A model without quantile weights: ERM_ERR_ARG, the message names erm_get_marginal_waic.  CrossQr: ERM_ERR_ARG -- with nu_ij integrated out
+ * every cell's response time is asymmetric Laplace in zeta, so -log p(t | theta, zeta) is piecewise linear in zeta with J kinks that move with theta; a fixed zeta rule
+ * is second order at best there, and the exact route sorts J break points per (subject, row, node).
+ * Definition, for subject i at row s (a LatentQr row has Latent's layout: a b lambda sig2t | beta0 beta_x[F] beta_theta | vec(Sigma_p)); q = q_rt,
+ * k1 = (1 - 2q) / (q (1 - q)), k2 = 2 / (q (1 - q)), s = Sigma_p[2,2], m = m0 + m1 theta with m0 = beta0 + x beta_x, m1 = beta_theta.
+ *   nu.     The model's own getLogLikelihoodRtIrtLatentQr has zeta_i | theta_i, nu_i ~ N(m + k1 nu_i, s k2 nu_i).  The conditional drawQrWeightsLatentQr draws from
+ *           (src/Draw.pl.jl:325-343: 1 / nu ~ InverseGaussian(B / A, B^2), B^2 = (2 k2 + k1^2) / (s k2)) is the one this likelihood gives under
+ *           nu_i ~ Exponential(mean s): that is the prior the sampler implies, and the one integrated over here.  It leaves zeta | theta asymmetric Laplace:
+ *             log p(zeta | theta) = log(q (1 - q) / s) - u (q - [u < 0]),  u = (zeta - m) / s.
+ *   theta.  theta ~ N(0, Sigma_p[1,1]), the law drawSubjAbilityNull uses, exactly as for Latent; the node rule (Q odd, z_q = -6 + q h, theta_q = sd z_q,
+ *           e_q = log h - 1/2 log 2 pi - 1/2 z_q^2 + B(theta_q) + T(theta_q), l = M + log S, COARSE if S < 2 at some row) and B(theta) are erm_get_marginal_waic's, unchanged.
+ *   zeta.   The response times are Gaussian in zeta, so zeta is integrated out in closed form.  g_j = 1 / sig2t_j, d0_j = lambda_j - t_j,
+ *           P = sum g_j, R0 = sum g_j d0_j, D0 = sum g_j d0_j^2, L = sum log sig2t_j;  bU = R0 - q / s,  bL = R0 + (1 - q) / s,
+ *             up = bU^2 / (2 P) + q m / s       + logPhi(-(m - bU / P) sqrt(P))          (the part zeta >= m)
+ *             lo = bL^2 / (2 P) - (1 - q) m / s + logPhi( (m - bL / P) sqrt(P))          (the part zeta <  m)
+ *             T(theta) = -(J/2) log 2 pi - L / 2 - D0 / 2 + log(q (1 - q) / s) + 1/2 log(2 pi / P) + logaddexp(up, lo).
+ *           logPhi, the log of the normal distribution function, in three arms, the same on host and device:  x >= 0: log1p(-erfc(x / sqrt 2) / 2);
+ *           -36 <= x < 0: log(erfc(-x / sqrt 2) / 2);  x < -36: -x^2 / 2 - log(-x) - 1/2 log 2 pi + log1p(-r + 3 r^2 - 15 r^3 + ... + 2027025 r^8), r = 1 / x^2
+ *           (eight terms of the asymptotic series by Horner's rule; the ninth is below 4e-21).  logaddexp(a, b) = max(a, b) + log1p(exp(-|a - b|)).
+ *           T needs s > 0, P > 0 and 0 < q < 1.  bU^2 / (2 P) cancels against logPhi when s is tiny: at J = 1, s = 0.001 the float64 value is good to about 1e-11.
+ *   All else -- the WAIC over the post-burn-in rows, PSIS-LOO on l, fp64 whatever the engine's precision, independence of the launch -- as defined above.
+ * erm_get_quantile_marginal_waic / erm_farm_get_quantile_marginal_waic: the outputs, n_nodes, the row limits and the refusals (a shard, a failed run, no data set, too
+ *   few rows) of erm_get_marginal_waic / erm_farm_get_marginal_waic, at the engine's (the farm's) q_rt.
+ * erm_get_quantile_marginal_loo / erm_farm_get_quantile_marginal_loo: those of erm_get_marginal_loo / erm_farm_get_marginal_loo below (25 .. 8192 rows, chunked scratch).
+ * erm_quantile_marginal_loglik: erm_marginal_loglik with the caller's q_rt; validated as a Latent table is, and also: q_rt outside (0, 1): ERM_ERR_ARG; a row with
+ *   Sigma_p[2,2] <= 0: ERM_ERR_ARG, "row r: Sigma_p[2,2] must be positive". */
+int erm_get_quantile_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);
+int erm_get_quantile_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw);
+int erm_quantile_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
+                                 const double* rows, int64_t n_rows, double q_rt, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u);
 
 /* Scores of respondents: the posterior mean and standard deviation of every subject's theta_i and zeta_i, their covariance, and what the rows were worth -- the
  * standard errors and reliabilities an IRT model is fitted for -- from the item-level trace alone.  Given a row of the item-level trace, a subject's (theta, zeta)
@@ -471,6 +506,8 @@ int erm_farm_get_mean(erm_farm_handle f, erm_state* out);
 int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Dbar over the rows of all chains, Dhat at the joint Post.mean (the same reduction as erm_farm_get_mean, evaluated on the first device) */
 int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* the marginal WAIC over the rows of all chains: see erm_get_marginal_waic */
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4);                          /* the scores over the rows of all chains: see erm_get_scores */
+int erm_farm_get_quantile_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* LatentQr: see erm_get_quantile_marginal_waic */
+int erm_farm_get_quantile_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* LatentQr: see erm_get_quantile_marginal_waic */
 int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* the marginal PSIS-LOO over the rows of all chains: see erm_get_marginal_loo */
 int erm_farm_get_plausible_values(erm_farm_handle f, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4);   /* plausible values over the rows of all chains: see erm_get_plausible_values */
 int erm_farm_set_seed(erm_farm_handle f, uint64_t seed);
