@@ -152,7 +152,6 @@ def load():
     lib.erm_get_mean.argtypes = [H, C.POINTER(erm_state)]
     lib.erm_post_count.argtypes = [H]
     lib.erm_post_count.restype = C.c_int64
-    lib.erm_get_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p]
     lib.erm_simulate_data.argtypes = [H, C.POINTER(erm_state), C.c_uint64, C.c_int]
     lib.erm_get_truth.argtypes = [H, C.c_void_p, C.c_void_p]
     lib.erm_get_data.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -185,7 +184,6 @@ def load():
     lib.erm_farm_used_rccl.argtypes = [H]
     lib.erm_farm_get_timing.argtypes = [H, C.POINTER(erm_farm_timing), C.c_void_p]
     lib.erm_get_dic.argtypes = [H, C.c_void_p]
-    lib.erm_get_convergence.argtypes = [H, C.c_int, C.c_void_p]
     lib.erm_debug_convergence.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erm_set_pointwise.argtypes = [H, C.c_int]
     lib.erm_get_waic.argtypes = [H, C.c_void_p]
@@ -200,35 +198,22 @@ def load():
     lib.erm_farm_get_dic.argtypes = [H, C.c_void_p]
     lib.erm_farm_set_seed.argtypes = [H, C.c_uint64]
     lib.erm_debug_invwishart.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]
-    lib.erm_get_rank_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_get_rank_convergence.argtypes = [H, C.c_int, C.c_void_p]
     lib.erm_debug_rank_diagnostics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_convergence.argtypes = [H, C.c_int, C.c_void_p]
-    lib.erm_farm_get_rank_diagnostics.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_rank_convergence.argtypes = [H, C.c_int, C.c_void_p]
     lib.erm_debug_diagnostics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.erm_get_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_marginal_loglik.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_get_scores.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_scores.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.erm_score.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
-                              C.c_void_p, C.c_void_p]
-    lib.erm_get_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.erm_psis_loo.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_get_plausible_values.argtypes = [H, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_plausible_values.argtypes = [H, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_plausible_values.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
-                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_get_quantile_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_quantile_marginal_waic.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.erm_get_quantile_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.erm_farm_get_quantile_marginal_loo.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.erm_quantile_marginal_loglik.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double,
-                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    I32, VP = C.c_int32, C.c_void_p
+    stems = [fam.stem for fam in MARGINAL_FAMILIES.values()]
+    pairs = [("diagnostics", [C.c_int, VP, VP]), ("convergence", [C.c_int, VP]), ("rank_diagnostics", [C.c_int, VP, VP, VP]), ("rank_convergence", [C.c_int, VP]),
+             ("scores", [I32, VP, VP]), ("plausible_values", [I32, I32, C.c_uint64, VP, VP, VP, VP])]
+    pairs += [(stem + "waic", [I32, VP, VP, VP]) for stem in stems] + [(stem + "loo", [I32, VP, VP]) for stem in stems]
+    for prefix in ("erm_get_", "erm_farm_get_"):          # every pair that _Diagnostics and _ItemPasses resolve through _get_prefix
+        for name, args in pairs:
+            getattr(lib, prefix + name).argtypes = [H] + args
+    head = [C.c_int, C.c_int, C.c_int64, I32, I32, VP, VP, VP, VP, C.c_int64]      # the caller-data entries: device, model, N, J, F, Y, logT, X, rows, R (_caller_head)
+    for fam in MARGINAL_FAMILIES.values():
+        getattr(lib, fam.loglik).argtypes = head + [C.c_double] * len(fam.scalars) + [I32, VP, VP, VP, VP]
+    lib.erm_score.argtypes = head + [I32, I32, VP, VP]
+    lib.erm_psis_loo.argtypes = [C.c_int, VP, C.c_int64, C.c_int64, VP, VP, VP]
+    lib.erm_plausible_values.argtypes = head + [I32, I32, C.c_uint64, VP, VP, VP, VP]
     _lib = lib
     return lib
 
@@ -241,6 +226,14 @@ def check(rc: int):
 MARGINAL_MODELS = (MODEL_MLIRT, MODEL_RTIRT, MODEL_NULL, MODEL_CROSS, MODEL_LATENT)      # the models erm_get_marginal_waic serves (no quantile weights)
 QUANTILE_MARGINAL_MODELS = (MODEL_LATENTQR,)      # the model erm_get_quantile_marginal_waic serves (nu integrated out with theta and zeta)
 MARGINAL_NODES = 61
+# The two families of the marginal WAIC and PSIS-LOO (FAMILY_GAUSSIAN / FAMILY_QUANTILE of csrc/erm_item_pass.hpp): the models a family serves, the stem of its
+# Engine / Farm methods and of its erm_get_* / erm_farm_get_* symbols (stem + "waic" | "loo"), its caller-data symbol, and the scalars (doubles) that symbol takes
+# between the rows and the node count.
+MarginalFamily = namedtuple("MarginalFamily", "models stem loglik scalars")
+MARGINAL_FAMILIES = MappingProxyType({
+    "gaussian": MarginalFamily(MARGINAL_MODELS, "marginal_", "erm_marginal_loglik", ()),
+    "quantile": MarginalFamily(QUANTILE_MARGINAL_MODELS, "quantile_marginal_", "erm_quantile_marginal_loglik", ("q_rt",)),
+})
 
 
 def marginal_nodes(nodes):
@@ -423,24 +416,29 @@ class _ItemPasses:
     def _pass(self, name: str):
         return getattr(self._lib, self._get_prefix + name)
 
+    def _marginal(self, family: str, product: str, nodes, pointwise):
+        """The "waic" or "loo" entry of a family of MARGINAL_FAMILIES."""
+        call = {"waic": _marginal_call, "loo": _loo_call}[product]
+        return call(self._pass(MARGINAL_FAMILIES[family].stem + product), self._h, nodes, self.cfg.n_subj, pointwise)
+
     def marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
         """erm_get_marginal_waic / erm_farm_get_marginal_waic: WAIC with every subject's theta and zeta integrated out, computed on the device from the resident
         item trace after the run.  The totals (erm_get_waic's, with nNodes and nCoarse); with pointwise=True (totals, lppd_i, p_i)."""
-        return _marginal_call(self._pass("marginal_waic"), self._h, nodes, self.cfg.n_subj, pointwise)
+        return self._marginal("gaussian", "waic", nodes, pointwise)
 
     def marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
         """erm_get_marginal_loo / erm_farm_get_marginal_loo: Pareto-smoothed leave-one-subject-out on the marginal log-likelihoods, computed on the device from the
         resident item trace after the run.  Returns a dict of out12; pointwise=True adds elpd_u, p_u, khat, nEff [n_subj]."""
-        return _loo_call(self._pass("marginal_loo"), self._h, nodes, self.cfg.n_subj, pointwise)
+        return self._marginal("gaussian", "loo", nodes, pointwise)
 
     def quantile_marginal_waic(self, nodes=MARGINAL_NODES, pointwise=False):
         """erm_get_quantile_marginal_waic / erm_farm_get_quantile_marginal_waic: marginal_waic for a LatentQr engine or farm, with the quantile weights integrated
         out too, at its q_rt.  The same outputs."""
-        return _marginal_call(self._pass("quantile_marginal_waic"), self._h, nodes, self.cfg.n_subj, pointwise)
+        return self._marginal("quantile", "waic", nodes, pointwise)
 
     def quantile_marginal_loo(self, nodes=MARGINAL_NODES, pointwise=False):
         """erm_get_quantile_marginal_loo / erm_farm_get_quantile_marginal_loo: marginal_loo for a LatentQr engine or farm.  The same outputs."""
-        return _loo_call(self._pass("quantile_marginal_loo"), self._h, nodes, self.cfg.n_subj, pointwise)
+        return self._marginal("quantile", "loo", nodes, pointwise)
 
     def scores(self, nodes=MARGINAL_NODES):
         """erm_get_scores / erm_farm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on
@@ -813,33 +811,30 @@ def _caller_head(device, model, arrays, dims):
     return (int(device), int(model), N, J, F, *(None if a is None else a.ctypes.data for a in arrays), R)
 
 
-def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
-    """erm_marginal_loglik: the marginal WAIC's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
-    Engine.item_trace() returns them.  Returns a dict: l [N, R] (every l_i^(s)), and -- with want_waic, which needs R >= 2 -- totals, lppd [N], p [N]."""
+def _family_loglik(family, model, Y, logT, X, rows, scalars, nodes, want_l, want_waic, device):
+    """The caller-data entry of a family of MARGINAL_FAMILIES, with the family's scalars in the table's order."""
     arrays, (N, J, F, R) = _caller_data(model, Y, logT, X, rows)
     l = np.empty((N, R), dtype=np.float64, order="F") if want_l else None
     out = np.empty(10, dtype=np.float64) if want_waic else None
     lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
     ptr = lambda a: None if a is None else a.ctypes.data
-    check(load().erm_marginal_loglik(*_caller_head(device, model, arrays, (N, J, F, R)), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
+    fn = getattr(load(), MARGINAL_FAMILIES[family].loglik)
+    check(fn(*_caller_head(device, model, arrays, (N, J, F, R)), *(float(s) for s in scalars), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
     res = dict(l=l)
     if want_waic:
         res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
     return res
+
+
+def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
+    """erm_marginal_loglik: the marginal WAIC's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
+    Engine.item_trace() returns them.  Returns a dict: l [N, R] (every l_i^(s)), and -- with want_waic, which needs R >= 2 -- totals, lppd [N], p [N]."""
+    return _family_loglik("gaussian", model, Y, logT, X, rows, (), nodes, want_l, want_waic, device)
 
 
 def quantile_marginal_loglik(model, Y, logT, X, rows, q_rt, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
     """erm_quantile_marginal_loglik: marginal_loglik for LatentQr rows (Latent's layout) at the quantile level q_rt, nu integrated out.  The same dict."""
-    arrays, (N, J, F, R) = _caller_data(model, Y, logT, X, rows)
-    l = np.empty((N, R), dtype=np.float64, order="F") if want_l else None
-    out = np.empty(10, dtype=np.float64) if want_waic else None
-    lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
-    ptr = lambda a: None if a is None else a.ctypes.data
-    check(load().erm_quantile_marginal_loglik(*_caller_head(device, model, arrays, (N, J, F, R)), float(q_rt), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
-    res = dict(l=l)
-    if want_waic:
-        res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
-    return res
+    return _family_loglik("quantile", model, Y, logT, X, rows, (q_rt,), nodes, want_l, want_waic, device)
 
 
 def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", device=0):

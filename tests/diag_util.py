@@ -1,4 +1,4 @@
-"""An independent reference for the convergence diagnostics (erm_get_diagnostics / erm_get_convergence, gibbs.ess_rhat): split-R-hat and the effective sample
+"""An independent reference for the convergence diagnostics (erm_get_diagnostics / erm_get_convergence, twins.ess_rhat): split-R-hat and the effective sample
 size by Geyer's initial monotone sequence, written from the definition in include/ertirt.h and above `diag_kernel` -- nothing is imported from the package.
 
 The definition.  The post-burn-in draws of a column are x[i, l], i = 0 .. Tn - 1, for the chains l = 0 .. C - 1.  With n = floor(Tn / 2), every chain is split

@@ -1,4 +1,4 @@
-"""An independent reference for the rank-normalised convergence diagnostics (erm_get_rank_diagnostics / erm_debug_rank_diagnostics, gibbs.rank_ess_rhat): bulk-ESS,
+"""An independent reference for the rank-normalised convergence diagnostics (erm_get_rank_diagnostics / erm_debug_rank_diagnostics, twins.rank_ess_rhat): bulk-ESS,
 tail-ESS and rank-normalised split-R-hat of Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021), written from the definition in include/ertirt.h -- nothing is
 imported from the package.  The transforms are numpy / scipy; the estimator behind them is diag_util.reference, the long-double one.
 

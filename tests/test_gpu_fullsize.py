@@ -234,7 +234,7 @@ def test_fullsize_f32_chain_within_three_mc_standard_errors_of_the_oracle_chain(
         tr = pu.OracleProblem("rtirt", Y, logT, X, init, qRt=0.5).run(T)
     finally:
         pu.oracle().orc_set_threads(1)
-    ess_rhat = pu.ge.load_package().gibbs.ess_rhat
+    ess_rhat = pu.ge.load_package().twins.ess_rhat
     orc_item = np.column_stack([tr["ra"][:, N:], tr["rt"][:, N:]])          # a, b | lambda, sig2t
     dev_item = dev["item"][:, :4 * J]
     post = orc_item[T // 2:]

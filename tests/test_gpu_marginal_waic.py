@@ -18,6 +18,7 @@ import pytest
 import marginal_util as mu
 import parity_util as pu
 import waic_util as wu
+from item_pass_util import _bytes, _engine, _farm, _kernel_x, _pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -26,19 +27,11 @@ LPPD_FLOOR = 1e-3
 TOTALS = ("elpd", "pWaic", "WAIC", "se", "lppd")
 
 
-def _pkg():
-    return pu.ge.load_package()
-
-
-def _kernel_x(model, X):
-    return X if model in ("mlirt", "rtirt", "latent") else None
-
-
 def _assert_equals_twin(model, Y, logT, X, rows, Q, what=""):
     pkg = _pkg()
     dev = pkg._lib.marginal_loglik(mu.CODE[model], Y, logT, X, rows, nodes=Q)
     Lh, S = pkg.marginalLogLikHost(mu.CODE[model], Y, logT, _kernel_x(model, X), rows, Q, with_S=True)
-    host = pkg.gibbs.waicFromLogLik(Lh)
+    host = pkg.twins.waicFromLogLik(Lh)
     el = np.max(np.abs(dev["l"].T - Lh) / np.abs(Lh))
     elp = np.max(np.abs(dev["lppd"] - host.lppd_u) / np.maximum(np.abs(host.lppd_u), LPPD_FLOOR))
     ep = np.max(np.abs(dev["p"] - host.p_u) / np.abs(host.p_u))
@@ -107,19 +100,6 @@ def test_a_subjects_result_depends_on_its_own_data_only(model):
 
 
 # ------------------------------------------------------------------------------------------------------------ the engine entry
-def _engine(model, Y, logT, X, init, *, n_iter, n_chain=1, n_burnin, precision="f64", full=True, unit=None, onepl=False):
-    L = _pkg()._lib
-    N, J = Y.shape
-    eng = L.Engine(model=pu.MODELS[model], n_item=J, n_subj=N, n_feat=0 if X is None else X.shape[1], n_iter=n_iter, n_chain=n_chain, n_burnin=n_burnin,
-                   one_pl=int(onepl), cov2one=int(model not in ("latentqr", "latent")), q_rt=0.85, seed=1234, precision={"f32": 0, "f64": 1}[precision],
-                   trace_mode=1 if full else 0)
-    eng.set_data(Y, logT, X)
-    if unit is not None:
-        eng.set_pointwise(unit)
-    eng.set_state(**{("lambda_" if k == "lam" else k): v for k, v in init.items()})
-    return eng
-
-
 def _assert_result_equals_loglik(got, model, data, rows, Q=61, what=""):
     """(totals, lppd, p) of an engine or farm entry against erm_marginal_loglik on the same data and rows."""
     L = _pkg()._lib
@@ -134,11 +114,6 @@ def _assert_result_equals_loglik(got, model, data, rows, Q=61, what=""):
         assert abs(w[k] - ref["totals"][k]) <= TOL * abs(ref["totals"][k]), k
     for k in ("nUnits", "nRows", "nNodes", "nHighVar", "nCoarse"):
         assert w[k] == ref["totals"][k], k
-
-
-def _bytes(r):
-    w, lppd, p = r
-    return repr(sorted(w.items())).encode() + lppd.tobytes() + p.tobytes()
 
 
 @pytest.mark.parametrize("full", [True, False], ids=["full", "summary"])
@@ -183,19 +158,6 @@ def test_engine_entry_only_reads_the_engine():
 
 
 # ------------------------------------------------------------------------------------------------------------ the farm
-def _farm(model, devices, Y, logT, X, init, *, n_iter, n_burnin, precision="f64"):
-    L = _pkg()._lib
-    N, J = Y.shape
-    farm = L.Farm(devices, model=pu.MODELS[model], n_item=J, n_subj=N, n_feat=0 if X is None else X.shape[1], n_iter=n_iter, n_chain=1, n_burnin=n_burnin,
-                  cov2one=int(model not in ("latentqr", "latent")), q_rt=0.85, seed=1234, precision={"f32": 0, "f64": 1}[precision], trace_mode=0)
-    farm.set_data(Y, logT, X)
-    g = np.random.default_rng(3)
-    for l in range(len(devices)):
-        st = {("lambda_" if k == "lam" else k): (v if l == 0 or k not in ("theta", "zeta") else g.standard_normal(N)) for k, v in init.items()}
-        farm.set_state(l, **st)
-    return farm
-
-
 @pytest.mark.parametrize("nch", [2, 3])
 def test_farm_equals_loglik_on_the_chain_major_rows(nch):
     Y, logT, X, init, tp = pu.make_problem("rtirt", 600, 9, 3, seed=47)

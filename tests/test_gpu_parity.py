@@ -137,7 +137,7 @@ def test_f32_chain_stays_coupled(model):
     T = 80
     res = pu.run_pair(model, N=1500, J=20, nsweeps=T, precision="f32")
     N = 1500
-    ess_rhat = pu.ge.load_package().gibbs.ess_rhat
+    ess_rhat = pu.ge.load_package().twins.ess_rhat
 
     def check(dev, orc):
         post = orc[T // 2:]

@@ -18,7 +18,7 @@ import pytest
 import marginal_util as mu
 import parity_util as pu
 import pv_util as pvu
-from test_gpu_marginal_waic import _engine, _farm
+from item_pass_util import _bytes, _engine, _farm, _pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -27,16 +27,8 @@ ARRAYS = ("theta", "zeta", "node", "coarse")
 COUNTS = ("nSubj", "nRows", "nNodes", "nCoarse")
 
 
-def _pkg():
-    return pu.ge.load_package()
-
-
 def _get(o, c):
     return np.asarray(o[c] if isinstance(o, dict) else getattr(o, c))
-
-
-def _bytes(r):
-    return repr([(k, r[k]) for k in COUNTS + ("seed",)]).encode() + b"".join(np.ascontiguousarray(r[c]).tobytes() for c in ARRAYS)
 
 
 def _assert_equal_draws(dev, ref, rt, what):

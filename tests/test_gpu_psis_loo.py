@@ -10,12 +10,16 @@
   6. the call only reads the engine.
   7. every refusal returns its code and a word of its own.
   8. an aberrant respondent has the largest k^, and no untouched respondent is flagged."""
+import functools
+
 import numpy as np
 import pytest
 
 import marginal_util as mu
 import parity_util as pu
 import psis_util as ps
+import item_pass_util as ipu
+from item_pass_util import _bytes, _farm, _kernel_x, _pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +32,7 @@ MARGINAL_TOL = 1e-10                          # tests/test_gpu_marginal_waic.py:
 TOTALS = ("elpd", "pLoo", "LOOIC", "se", "lppd")
 COUNTS = ("nUnits", "nRows", "nBadK", "nHighK", "tailLen", "nNodes", "nCoarse")
 COLS = (("elpd_u", "elpd_u"), ("p_u", "p_u"), ("khat", "khat"), ("nEff", "nEff"))
-
-
-def _pkg():
-    return pu.ge.load_package()
+_engine = functools.partial(ipu._engine, full=False)          # these tests run in summary mode
 
 
 def _bound():
@@ -98,24 +99,6 @@ def test_packing_does_not_change_a_bit(S, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------ the engine entry
-def _engine(model, Y, logT, X, init, *, n_iter, n_burnin, precision="f64", n_chain=1, full=False):
-    L = _pkg()._lib
-    N, J = Y.shape
-    eng = L.Engine(model=pu.MODELS[model], n_item=J, n_subj=N, n_feat=0 if X is None else X.shape[1], n_iter=n_iter, n_chain=n_chain, n_burnin=n_burnin,
-                   cov2one=int(model not in ("latentqr", "latent")), q_rt=0.85, seed=1234, precision={"f32": 0, "f64": 1}[precision], trace_mode=int(full))
-    eng.set_data(Y, logT, X)
-    eng.set_state(**{("lambda_" if k == "lam" else k): v for k, v in init.items()})
-    return eng
-
-
-def _bytes(r):
-    return repr([(k, r[k]) for k in TOTALS + COUNTS]).encode() + b"".join(np.ascontiguousarray(r[d]).tobytes() for d, _ in COLS)
-
-
-def _kernel_x(model, X):
-    return X if model in ("mlirt", "rtirt", "latent") else None
-
-
 def _via_loglik(model, data, rows, Q=61):
     """erm_psis_loo on the l erm_marginal_loglik returns for the data and the rows, with the node count and the coarse count of the marginal kernel's totals."""
     L = _pkg()._lib
@@ -162,19 +145,6 @@ def test_chunks_equal_one_chunk_bit_for_bit(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------ the farm
-def _farm(model, devices, Y, logT, X, init, *, n_iter, n_burnin):
-    L = _pkg()._lib
-    N, J = Y.shape
-    farm = L.Farm(devices, model=pu.MODELS[model], n_item=J, n_subj=N, n_feat=0 if X is None else X.shape[1], n_iter=n_iter, n_chain=1, n_burnin=n_burnin,
-                  cov2one=int(model not in ("latentqr", "latent")), q_rt=0.85, seed=1234, precision=1, trace_mode=0)
-    farm.set_data(Y, logT, X)
-    g = np.random.default_rng(3)
-    for l in range(len(devices)):
-        st = {("lambda_" if k == "lam" else k): (v if l == 0 or k not in ("theta", "zeta") else g.standard_normal(N)) for k, v in init.items()}
-        farm.set_state(l, **st)
-    return farm
-
-
 def test_farm_of_one_chain_equals_its_engine_and_two_chains_the_chain_major_table():
     Y, logT, X, init, tp = pu.make_problem("rtirt", 300, 9, 3, seed=75)
     one = _farm("rtirt", [0], Y, logT, X, init, n_iter=60, n_burnin=30)

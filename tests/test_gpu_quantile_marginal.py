@@ -21,25 +21,21 @@ import pytest
 
 import parity_util as pu
 import qmarginal_util as qu
+from item_pass_util import _bytes, _engine, _farm, _pkg
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-10
 LPPD_FLOOR = 1e-3
 TOTALS = ("elpd", "pWaic", "WAIC", "se", "lppd")
-LOO_KEYS = ("elpd", "pLoo", "LOOIC", "se", "lppd", "nUnits", "nRows", "nBadK", "nHighK", "tailLen", "nNodes", "nCoarse")
-LOO_COLS = ("elpd_u", "p_u", "khat", "nEff")
-
-
-def _pkg():
-    return pu.ge.load_package()
+_loo_bytes = _bytes          # the dict of a LOO entry: its twelve totals and four columns
 
 
 def _assert_equals_twin(Y, logT, X, rows, q, Q, what=""):
     pkg = _pkg()
     dev = pkg._lib.quantile_marginal_loglik(qu.CODE, Y, logT, X, rows, q, nodes=Q)
     Lh, S = pkg.quantileMarginalLogLikHost(qu.CODE, Y, logT, X, rows, q, Q, with_S=True)
-    host = pkg.gibbs.waicFromLogLik(Lh)
+    host = pkg.twins.waicFromLogLik(Lh)
     el = np.max(np.abs(dev["l"].T - Lh) / np.abs(Lh))
     elp = np.max(np.abs(dev["lppd"] - host.lppd_u) / np.maximum(np.abs(host.lppd_u), LPPD_FLOOR))
     ep = np.max(np.abs(dev["p"] - host.p_u) / np.abs(host.p_u))
@@ -88,16 +84,6 @@ def test_a_subjects_result_depends_on_its_own_data_only():
 
 
 # ------------------------------------------------------------------------------------------------------------ the engine entries
-def _engine(model, Y, logT, X, init, *, n_iter, n_chain=1, n_burnin, precision="f64", full=True, q_rt=0.85):
-    L = _pkg()._lib
-    N, J = Y.shape
-    eng = L.Engine(model=pu.MODELS[model], n_item=J, n_subj=N, n_feat=0 if X is None else X.shape[1], n_iter=n_iter, n_chain=n_chain, n_burnin=n_burnin,
-                   cov2one=int(model not in ("latentqr", "latent")), q_rt=q_rt, seed=1234, precision={"f32": 0, "f64": 1}[precision], trace_mode=1 if full else 0)
-    eng.set_data(Y, logT, X)
-    eng.set_state(**{("lambda_" if k == "lam" else k): v for k, v in init.items()})
-    return eng
-
-
 def _assert_result_equals_loglik(got, data, rows, q, Q=61, what=""):
     """(totals, lppd, p) of an engine or farm entry against erm_quantile_marginal_loglik on the same data, rows and level; returns that call's result."""
     L = _pkg()._lib
@@ -113,15 +99,6 @@ def _assert_result_equals_loglik(got, data, rows, q, Q=61, what=""):
     for k in ("nUnits", "nRows", "nNodes", "nHighVar", "nCoarse"):
         assert w[k] == ref["totals"][k], k
     return ref
-
-
-def _bytes(r):
-    w, lppd, p = r
-    return repr(sorted(w.items())).encode() + lppd.tobytes() + p.tobytes()
-
-
-def _loo_bytes(r):
-    return repr([(k, r[k]) for k in LOO_KEYS]).encode() + b"".join(np.ascontiguousarray(r[c]).tobytes() for c in LOO_COLS)
 
 
 def _loo_via_loglik(data, rows, q, Q=61):
@@ -184,19 +161,6 @@ def test_engine_entry_reads_the_engines_own_level():
 
 
 # ------------------------------------------------------------------------------------------------------------ the farm
-def _farm(model, devices, Y, logT, X, init, *, n_iter, n_burnin, q_rt=0.85):
-    L = _pkg()._lib
-    N, J = Y.shape
-    farm = L.Farm(devices, model=pu.MODELS[model], n_item=J, n_subj=N, n_feat=0 if X is None else X.shape[1], n_iter=n_iter, n_chain=1, n_burnin=n_burnin,
-                  cov2one=int(model not in ("latentqr", "latent")), q_rt=q_rt, seed=1234, precision=1, trace_mode=0)
-    farm.set_data(Y, logT, X)
-    g = np.random.default_rng(3)
-    for l in range(len(devices)):
-        st = {("lambda_" if k == "lam" else k): (v if l == 0 or k not in ("theta", "zeta") else g.standard_normal(N)) for k, v in init.items()}
-        farm.set_state(l, **st)
-    return farm
-
-
 def test_farm_equals_loglik_on_the_chain_major_rows():
     Y, logT, X, init, tp = pu.make_problem("latentqr", 200, 7, 3, seed=47)
     farm = _farm("latentqr", [0, 0], Y, logT, X, init, n_iter=20, n_burnin=6)

@@ -14,11 +14,11 @@ pytestmark = pytest.mark.gpu
 
 def mcse(draws):
     """Monte-Carlo standard error of the mean of each column of `draws` (iterations x parameters): sd / sqrt(ESS), ESS by the package's
-    split-chain Geyer estimator (gibbs.ess_rhat, itself pinned by known-answer tests in tests/test_host_api.py)."""
+    split-chain Geyer estimator (twins.ess_rhat, itself pinned by known-answer tests in tests/test_host_api.py)."""
     pkg = pu.ge.load_package()
     out = np.empty(draws.shape[1])
     for k in range(draws.shape[1]):
-        ess, _ = pkg.gibbs.ess_rhat(draws[:, k])
+        ess, _ = pkg.twins.ess_rhat(draws[:, k])
         out[k] = draws[:, k].std(ddof=1) / np.sqrt(min(max(ess, 1.0), draws.shape[0]))
     return out
 

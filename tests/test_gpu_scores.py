@@ -20,7 +20,7 @@ import marginal_util as mu
 import parity_util as pu
 import score_util as su
 import waic_util as wu
-from test_gpu_marginal_waic import _engine, _farm
+from item_pass_util import _bytes, _engine, _farm, _kernel_x, _pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +28,6 @@ TOL = 1e-10
 R_CPU = 0.1348          # tests/test_score_host.py::test_scores_agree_with_the_chain_for_mlirt
 WEIGHTINGS = ("equal", "likelihood")
 COLUMNS = su.COLS + ("coarse",)
-
-
-def _pkg():
-    return pu.ge.load_package()
-
-
-def _kernel_x(model, X):
-    return X if model in ("mlirt", "rtirt", "latent") else None
 
 
 def _errors(dev, ref, rt):
@@ -130,10 +122,6 @@ def test_a_subjects_scores_depend_on_its_own_data_only(model):
 
 
 # ------------------------------------------------------------------------------------------------------------ the engine entry
-def _bytes(r):
-    return repr(sorted((k, v) for k, v in r.items() if k.startswith("n"))).encode() + b"".join(np.ascontiguousarray(r[c]).tobytes() for c in COLUMNS)
-
-
 def _assert_result_equals_score(got, model, data, rows, Q=61, what=""):
     """The dict of an engine or farm entry against erm_score on the same data and rows, equal weights."""
     Y, logT, X = data

@@ -94,7 +94,7 @@ def test_marginal_elpd_prefers_2pl_on_spread_discriminations():
     for onepl in (False, True):
         M = wu.oracle_sampler("mlirt", Y, None, X, init, wu.SPREAD_ITER, onepl=onepl)
         L, S = pkg.marginalLogLikHost(0, Y, None, X, _mlirt_rows(M), 61, with_S=True)
-        fit[onepl] = pkg.gibbs.waicFromLogLik(L, nNodes=61, nCoarse=int(np.sum(np.any(S < 2.0, axis=0))))
+        fit[onepl] = pkg.twins.waicFromLogLik(L, nNodes=61, nCoarse=int(np.sum(np.any(S < 2.0, axis=0))))
         assert fit[onepl].nCoarse == 0 and fit[onepl].unit == "subject-marginal"
     cmp = pkg.compareWaic(fit[False], fit[True])
     print(f"2pl elpd {fit[False].elpd:.2f} (p {fit[False].pWaic:.2f}), 1pl elpd {fit[True].elpd:.2f} (p {fit[True].pWaic:.2f}); diff {cmp['elpd_diff']:.2f}, se_diff {cmp['se_diff']:.2f}")

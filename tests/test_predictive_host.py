@@ -18,7 +18,7 @@ import ppc_util as ppu
 import waic_util as wu
 
 pkg = pu.ge.load_package()
-G = pkg.gibbs
+G = pkg.twins
 
 
 def test_numpy_philox_equals_the_oracle_block():

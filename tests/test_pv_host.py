@@ -50,7 +50,7 @@ def _run(exe, args, text=""):
 def test_row_index(exe, K, n_rows):
     got = np.array([int(v) for v in _run(exe, ["row", K, n_rows])])
     ref = np.array([((2 * k + 1) * n_rows) // (2 * K) for k in range(K)])                 # python integers: no overflow
-    assert np.array_equal(got, ref) and np.array_equal(got, pkg.gibbs.pvRow(np.arange(K), K, n_rows))
+    assert np.array_equal(got, ref) and np.array_equal(got, pkg.twins.pvRow(np.arange(K), K, n_rows))
     assert np.all(np.diff(got) >= 0) and got[0] >= 0 and got[-1] < n_rows
     if K <= n_rows:
         assert np.unique(got).size == K                                                   # distinct
@@ -61,7 +61,7 @@ def test_row_index(exe, K, n_rows):
 def test_gumbel_key_of_a_word(exe):
     words = [0, 1, 2 ** 31, 2 ** 32 - 2, 2 ** 32 - 1, 123456789]
     got = np.array([float.fromhex(v) for v in _run(exe, ["key", *words])])
-    ref = pkg.gibbs.pvGumbel(np.array(words, dtype=np.uint64))
+    ref = pkg.twins.pvGumbel(np.array(words, dtype=np.uint64))
     assert np.max(np.abs(got - ref)) <= 1e-14 * 23.0
     assert abs(got[0] + np.log(33.0 * np.log(2.0))) <= 1e-13                              # u = 2^-33: g = -log(33 log 2) = -3.13
     assert abs(got[4] - 33.0 * np.log(2.0)) <= 1e-6 and got[4] < 22.88                    # u = 1 - 2^-33: g = 33 log 2 - O(2^-34) = 22.87
@@ -110,7 +110,7 @@ def test_finish_of_a_draw(exe):
         E, V, mu_, sd, c0, c1, u, q, Q, has_zeta, w0, w1, w2 = r
         th, ze = (float.fromhex(v) if "nan" not in v else np.nan for v in line.split())
         W = lambda w: np.array([w], dtype=np.uint64)
-        rt, rz = (float(v[0]) for v in pkg.gibbs.pvFinish(E, V, mu_, sd, c0, c1, u, q, 12.0 / (Q - 1), W(w0), W(w1), W(w2)))
+        rt, rz = (float(v[0]) for v in pkg.twins.pvFinish(E, V, mu_, sd, c0, c1, u, q, 12.0 / (Q - 1), W(w0), W(w1), W(w2)))
         assert abs(th - rt) <= 1e-14 * max(abs(rt), 1.0), r
         if not has_zeta:
             assert np.isnan(ze)
@@ -167,7 +167,7 @@ def test_twin_is_a_function_of_the_subject_the_rows_and_the_seed():
     for c in ("theta", "zeta", "node"):
         assert np.array_equal(getattr(part, c), getattr(whole, c)[4:9]), c
     assert not np.array_equal(other.theta, whole.theta) and not np.array_equal(moved.theta, part.theta)
-    assert np.array_equal(pkg.gibbs.pvRow(np.arange(5), 5, 7), [0, 2, 3, 4, 6])
+    assert np.array_equal(pkg.twins.pvRow(np.arange(5), 5, 7), [0, 2, 3, 4, 6])
 
 
 @pytest.mark.parametrize("model,J,Q,K,R", pvu.CASES)
