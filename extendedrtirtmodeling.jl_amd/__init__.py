@@ -5,7 +5,7 @@ Export list mirrors the part of /root/reference/src/ExtendedRtIrtModeling.jl:33-
 from .base import InputData, InputData4R, InputPara, OutputDic, OutputLoo, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions, setCond
 from .gibbs import (GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCross, GibbsRtIrtCrossQr, GibbsRtIrtLatent, GibbsRtIrtLatentQr, GibbsRtIrtNull,
                     GibbsRtIrtQuantile, checkConvergence, coef, compareLoo, compareWaic, drawPlausibleValues, getDic, getDicHost, getLogLikelihood,
-                    getLooMarginal, getLooMarginalQr, getPlausibleValues, getPpc, getScores, getWaic, getWaicMarginal, getWaicMarginalQr, precis, psisLoo,
+                    getLooMarginal, getLooMarginalQr, getPlausibleValues, getPpc, getScores, getWaic, getWaicMarginal, getWaicMarginalQr, observedMask, precis, psisLoo,
                     sample, sample_b, scoreRespondents, simulateData)
 from .twins import (ess_rhat, getLooMarginalHost, getLooMarginalQrHost, getPpcHost, getWaicHost, getWaicMarginalHost, getWaicMarginalQrHost,
                     marginalLogLikHost, plausibleValuesHost, pointwiseLogLikHost, psisLooHost, quantileMarginalLogLikHost, rank_ess_rhat, scoresHost)
@@ -28,7 +28,7 @@ __all__ = [
     "setTrueParaMlIrt", "setTrueParaRtIrt", "setTrueParaRtIrtCross", "setTrueParaRtIrtLatent",
     "getBias", "getRmse", "getDic", "getDicHost", "getWaic", "getWaicHost", "compareWaic", "pointwiseLogLikHost",
     "getWaicMarginal", "getWaicMarginalHost", "marginalLogLikHost", "OutputWaic", "getScores", "scoreRespondents", "scoresHost", "OutputScores",
-    "getPlausibleValues", "drawPlausibleValues", "plausibleValuesHost", "OutputPv", "getLooMarginal", "getLooMarginalHost",
+    "getPlausibleValues", "drawPlausibleValues", "plausibleValuesHost", "OutputPv", "observedMask", "getLooMarginal", "getLooMarginalHost",
     "getWaicMarginalQr", "getWaicMarginalQrHost", "getLooMarginalQr", "getLooMarginalQrHost", "quantileMarginalLogLikHost",
     "psisLoo", "psisLooHost", "compareLoo", "OutputLoo", "getPpc", "getPpcHost", "OutputPpc", "checkConvergence", "ess_rhat", "rank_ess_rhat",
     "simulateData", "getLogLikelihood", "sample_b", "sample",

@@ -72,6 +72,7 @@ EXPORTS = [
     "erm_get_plausible_values", "erm_farm_get_plausible_values", "erm_plausible_values",
     "erm_get_quantile_marginal_waic", "erm_farm_get_quantile_marginal_waic", "erm_get_quantile_marginal_loo", "erm_farm_get_quantile_marginal_loo",
     "erm_quantile_marginal_loglik",
+    "erm_marginal_loglik_masked", "erm_score_masked", "erm_plausible_values_masked",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -214,6 +215,10 @@ def load():
     lib.erm_score.argtypes = head + [I32, I32, VP, VP]
     lib.erm_psis_loo.argtypes = [C.c_int, VP, C.c_int64, C.c_int64, VP, VP, VP]
     lib.erm_plausible_values.argtypes = head + [I32, I32, C.c_uint64, VP, VP, VP, VP]
+    mhead = head[:8] + [VP] + head[8:]      # the masked entries: obs between X and rows, n_obs last
+    lib.erm_marginal_loglik_masked.argtypes = mhead + [I32, VP, VP, VP, VP, VP]
+    lib.erm_score_masked.argtypes = mhead + [I32, I32, VP, VP, VP]
+    lib.erm_plausible_values_masked.argtypes = mhead + [I32, I32, C.c_uint64, VP, VP, VP, VP, VP]
     _lib = lib
     return lib
 
@@ -805,31 +810,50 @@ def _caller_data(model, Y, logT, X, rows):
     return (Yf, lt, xx, rr), (N, J, F, rr.shape[0])
 
 
-def _caller_head(device, model, arrays, dims):
-    """The leading arguments of the three entries: device, model, N, J, F, Y, logT, X, rows, R (the arrays stay the caller's to keep alive)."""
+def _caller_head(device, model, arrays, dims, obs=None):
+    """The leading arguments of the three entries: device, model, N, J, F, Y, logT, X, rows, R (the arrays stay the caller's to keep alive); with obs (_caller_obs),
+    those of their masked siblings: obs stands between X and rows."""
     N, J, F, R = dims
-    return (int(device), int(model), N, J, F, *(None if a is None else a.ctypes.data for a in arrays), R)
+    ptr = [None if a is None else a.ctypes.data for a in arrays]
+    if obs is not None:
+        ptr.insert(3, obs.ctypes.data)
+    return (int(device), int(model), N, J, F, *ptr, R)
 
 
-def _family_loglik(family, model, Y, logT, X, rows, scalars, nodes, want_l, want_waic, device):
-    """The caller-data entry of a family of MARGINAL_FAMILIES, with the family's scalars in the table's order."""
+def _caller_obs(obs, N, J):
+    """The observed mask as the masked entries take it: uint8 [N, J] column-major, and n_obs (N,) int32 for them to fill.  The values are the library's to check."""
+    O = np.asfortranarray(np.asarray(obs).astype(np.uint8))
+    if O.shape != (N, J):
+        raise ValueError("obs does not match Y")
+    return O, np.empty(N, dtype=np.int32)
+
+
+def _family_loglik(family, model, Y, logT, X, rows, scalars, nodes, want_l, want_waic, device, obs=None):
+    """The caller-data entry of a family of MARGINAL_FAMILIES, with the family's scalars in the table's order; obs: the Gaussian family's masked sibling."""
     arrays, (N, J, F, R) = _caller_data(model, Y, logT, X, rows)
     l = np.empty((N, R), dtype=np.float64, order="F") if want_l else None
     out = np.empty(10, dtype=np.float64) if want_waic else None
     lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
     ptr = lambda a: None if a is None else a.ctypes.data
-    fn = getattr(load(), MARGINAL_FAMILIES[family].loglik)
-    check(fn(*_caller_head(device, model, arrays, (N, J, F, R)), *(float(s) for s in scalars), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
-    res = dict(l=l)
+    if obs is None:
+        fn = getattr(load(), MARGINAL_FAMILIES[family].loglik)
+        check(fn(*_caller_head(device, model, arrays, (N, J, F, R)), *(float(s) for s in scalars), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
+        res = dict(l=l)
+    else:
+        O, n_obs = _caller_obs(obs, N, J)
+        check(load().erm_marginal_loglik_masked(*_caller_head(device, model, arrays, (N, J, F, R), O), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p),
+                                                n_obs.ctypes.data))
+        res = dict(l=l, nObs=n_obs)
     if want_waic:
         res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
     return res
 
 
-def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
+def marginal_loglik(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0, obs=None):
     """erm_marginal_loglik: the marginal WAIC's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
-    Engine.item_trace() returns them.  Returns a dict: l [N, R] (every l_i^(s)), and -- with want_waic, which needs R >= 2 -- totals, lppd [N], p [N]."""
-    return _family_loglik("gaussian", model, Y, logT, X, rows, (), nodes, want_l, want_waic, device)
+    Engine.item_trace() returns them.  Returns a dict: l [N, R] (every l_i^(s)), and -- with want_waic, which needs R >= 2 -- totals, lppd [N], p [N].
+    obs [N, J], 0/1 (None: complete, the call above): erm_marginal_loglik_masked on incomplete patterns; the dict then has nObs [N]."""
+    return _family_loglik("gaussian", model, Y, logT, X, rows, (), nodes, want_l, want_waic, device, obs)
 
 
 def quantile_marginal_loglik(model, Y, logT, X, rows, q_rt, *, nodes=MARGINAL_NODES, want_l=True, want_waic=True, device=0):
@@ -837,21 +861,32 @@ def quantile_marginal_loglik(model, Y, logT, X, rows, q_rt, *, nodes=MARGINAL_NO
     return _family_loglik("quantile", model, Y, logT, X, rows, (q_rt,), nodes, want_l, want_waic, device)
 
 
-def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", device=0):
+def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", device=0, obs=None):
     """erm_score: the scores' kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as Engine.item_trace()
-    returns them, R >= 1; weighting "equal" | "likelihood".  Returns Engine.scores' dict."""
+    returns them, R >= 1; weighting "equal" | "likelihood".  Returns Engine.scores' dict.  obs [N, J], 0/1 (None: complete, erm_score): erm_score_masked on
+    incomplete patterns; the dict then has nObs [N]."""
     arrays, dims = _caller_data(model, Y, logT, X, rows)
     N = dims[0]
     sc, out = np.empty((len(SCORE_COLUMNS), N), dtype=np.float64), np.empty(4, dtype=np.float64)
-    check(load().erm_score(*_caller_head(device, model, arrays, dims), marginal_nodes(nodes), score_weighting(weighting), sc.ctypes.data, out.ctypes.data))
-    return _score_result(sc, out)
+    if obs is None:
+        check(load().erm_score(*_caller_head(device, model, arrays, dims), marginal_nodes(nodes), score_weighting(weighting), sc.ctypes.data, out.ctypes.data))
+        return _score_result(sc, out)
+    O, n_obs = _caller_obs(obs, N, dims[1])
+    check(load().erm_score_masked(*_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes), score_weighting(weighting), sc.ctypes.data, out.ctypes.data,
+                                  n_obs.ctypes.data))
+    return dict(_score_result(sc, out), nObs=n_obs)
 
 
-def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES, device=0):
+def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES, device=0, obs=None):
     """erm_plausible_values: the plausible values' kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
-    Engine.item_trace() returns them, R >= 1.  Returns Engine.plausible_values' dict."""
+    Engine.item_trace() returns them, R >= 1.  Returns Engine.plausible_values' dict.  obs [N, J], 0/1 (None: complete, erm_plausible_values):
+    erm_plausible_values_masked on incomplete patterns; the dict then has nObs [N]."""
     arrays, dims = _caller_data(model, Y, logT, X, rows)
-    return _pv_call(load().erm_plausible_values, dims[0], K, seed, *_caller_head(device, model, arrays, dims), marginal_nodes(nodes))
+    if obs is None:
+        return _pv_call(load().erm_plausible_values, dims[0], K, seed, *_caller_head(device, model, arrays, dims), marginal_nodes(nodes))
+    O, n_obs = _caller_obs(obs, dims[0], dims[1])
+    fn = lambda *a: load().erm_plausible_values_masked(*a, n_obs.ctypes.data)
+    return dict(_pv_call(fn, dims[0], K, seed, *_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes)), nObs=n_obs)
 
 
 def psis_loo(l, *, want_lw=False, device=0):

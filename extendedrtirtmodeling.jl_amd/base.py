@@ -148,9 +148,10 @@ class OutputScores:
     coarse (the theta rule was too coarse for the subject at some row: raise nodes); nRows, nNodes, nCoarse.  relTheta / relZeta: the EAP reliability
     Var_i(score_i) / (Var_i(score_i) + mean_i sd_i^2)."""
 
-    def __init__(self, theta=None, thetaSd=None, zeta=None, zetaSd=None, cov=None, rowEss=None, coarse=None, nRows=None, nNodes=None, nCoarse=None, weighting="equal"):
+    def __init__(self, theta=None, thetaSd=None, zeta=None, zetaSd=None, cov=None, rowEss=None, coarse=None, nRows=None, nNodes=None, nCoarse=None, weighting="equal", nObs=None):
         self.theta, self.thetaSd, self.zeta, self.zetaSd, self.cov, self.rowEss, self.coarse = theta, thetaSd, zeta, zetaSd, cov, rowEss, coarse
         self.nRows, self.nNodes, self.nCoarse, self.weighting = nRows, nNodes, nCoarse, weighting
+        self.nObs = nObs          # scoreRespondents(..., obs=): the observed cells per subject (None without a mask)
 
     @staticmethod
     def _rel(m, sd):
@@ -178,9 +179,10 @@ class OutputPv:
     coarse for the subject at some row it used (raise nodes); nRows, nNodes, nCoarse and the seed of the draws.  Column k over the subjects is one imputed data set:
     analyse each of the K and pool the results by Rubin's rules."""
 
-    def __init__(self, theta=None, zeta=None, node=None, coarse=None, nRows=None, nNodes=None, nCoarse=None, seed=None):
+    def __init__(self, theta=None, zeta=None, node=None, coarse=None, nRows=None, nNodes=None, nCoarse=None, seed=None, nObs=None):
         self.theta, self.zeta, self.node, self.coarse = theta, zeta, node, coarse
         self.nRows, self.nNodes, self.nCoarse, self.seed = nRows, nNodes, nCoarse, seed
+        self.nObs = nObs          # drawPlausibleValues(..., obs=): the observed cells per subject (None without a mask)
 
     def __repr__(self):
         shape = None if self.theta is None else np.shape(self.theta)

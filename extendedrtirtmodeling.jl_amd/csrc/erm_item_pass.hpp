@@ -1,7 +1,8 @@
 // erm_item_pass.hpp -- the host path of the passes that run after sampling from a data set and a table of item-trace rows: the marginal WAIC, the
 // marginal PSIS-LOO, the scores and the plausible values.  Each of erm_get_* / erm_farm_get_* (four each) and erm_marginal_loglik / erm_score / erm_plausible_values
 // is its own argument checks, ONE source maker (item_source) and ONE product call (item_waic / item_loo / item_scores / item_pv).  The five entries of LatentQr's
-// marginal WAIC and LOO (erm_get_quantile_marginal_* and erm_quantile_marginal_loglik) are the same makers and products for FAMILY_QUANTILE.
+// marginal WAIC and LOO (erm_get_quantile_marginal_* and erm_quantile_marginal_loglik) are the same makers and products for FAMILY_QUANTILE, and the
+// three masked entries (erm_marginal_loglik_masked / erm_score_masked / erm_plausible_values_masked) the caller-data maker with an observed mask.
 //
 // The first half is plain C++: the facts of a pass as one table, the refusals built from it and the chunk rule; g++ compiles this half with
 // -fsanitize=undefined -ftrapv into tests/item_pass_check (tests/test_item_pass_host.py).
@@ -11,6 +12,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include "erm_obs.hpp"
 
 namespace erm {
 
@@ -55,8 +57,10 @@ namespace {      // (as ertirt.hip's own: EngineBase names ItemSource)
 
 // ---- what marginal_kernel, score_kernel and pv_kernel share of a launch.  Everything a launch is given lives on the current device.
 // a data set as the kernels read it: row-major, C and X in the element type of `elem` bytes (float or double)
-// (q_rt: the quantile level, read for LatentQr only)
-struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; size_t elem; double q_rt; };
+// (q_rt: the quantile level, read for LatentQr only).  off != NULL: an incomplete data set (DESIGN.md 7m, fp64 only) -- Y, C and idx are erm_obs.hpp's compacted
+// cell lists, subject i's at the positions off[i] .. off[i + 1]; the tile kernels' MASKED instantiations read it
+struct MargData { const uint8_t* Y; const void* C; const void* X; const double* cm; int64_t N; int J, Fk, model; size_t elem; double q_rt;
+                  const uint16_t* idx = nullptr; const int64_t* off = nullptr; };
 static int marg_refuse_crossqr()
 {
     return fail(ERM_ERR_ARG, "CrossQr is not served: with the quantile weights nu_ij integrated out every cell's response time is asymmetric Laplace in zeta, "
@@ -88,6 +92,7 @@ static MargArgs marg_args(const MargData& D, const double* rows, int64_t n_rows,
 {
     MargArgs a{};
     a.Y = D.Y; a.C = D.C; a.X = D.X; a.cm = D.cm; a.rows = rows; a.n_rows = n_rows; a.ld = item_trace_width(D.model, D.J, D.Fk); a.N = D.N; a.J = D.J; a.F = D.Fk; a.Q = Q; a.q = D.q_rt;
+    a.idx = D.idx; a.off = reinterpret_cast<const long long*>(D.off);
     return a;
 }
 static size_t marg_lds(const MargArgs& a) { return (size_t)2 * marg_row_lds(a.ld, a.J) * sizeof(double); }
@@ -108,11 +113,23 @@ static int marg_dispatch(const MargData& D, Launch&& launch)
 static MargData marg_chunk(const MargData& D, int64_t c0, int64_t nc)
 {
     MargData Dc = D;
+    Dc.N = nc;
+    Dc.X = D.X ? static_cast<const char*>(D.X) + (size_t)c0 * D.Fk * D.elem : nullptr;
+    if (D.off) { Dc.off = D.off + c0; return Dc; }        // an incomplete data set: the offsets are absolute, so the lists stay where they are
     Dc.Y = D.Y + (size_t)c0 * D.J;
     Dc.C = D.C ? static_cast<const char*>(D.C) + (size_t)c0 * D.J * D.elem : nullptr;
-    Dc.X = D.X ? static_cast<const char*>(D.X) + (size_t)c0 * D.Fk * D.elem : nullptr;
-    Dc.N = nc;
     return Dc;
+}
+// the instantiation for a data set's completeness as well: launch(model constant, real(), masked constant); the compacted lists are fp64
+template <typename Launch>
+static int marg_dispatch_obs(const MargData& D, Launch&& launch)
+{
+    if (!D.off) return marg_dispatch(D, [&](auto M, auto real) { return launch(M, real, std::false_type{}); });
+    if (D.elem != sizeof(double)) return fail(ERM_ERR_STATE, "an incomplete data set is fp64");
+    return marg_dispatch(D, [&](auto M, auto real) -> int {
+        if constexpr (std::is_same_v<decltype(real), double>) return launch(M, real, std::true_type{});
+        else return fail(ERM_ERR_STATE, "an incomplete data set is fp64");
+    });
 }
 // one launch of a tile kernel with the arguments a (and the kernel's own), waited for
 template <typename... P, typename... A>
@@ -132,7 +149,7 @@ static int marginal_launch(const MargData& D, const double* rows, int64_t n_rows
     a.l_out = l_dev; a.acc_ms = acc_ms; a.acc_w = acc_w; a.coarse = coarse;
     if (D.model == ERM_MODEL_LATENTQR)      // the one kernel LatentQr has (a source of FAMILY_QUANTILE; marg_dispatch's kernels refuse the model)
         return D.elem == sizeof(float) ? marg_tile_launch(&marginal_kernel<LATENTQR, float>, a, stream) : marg_tile_launch(&marginal_kernel<LATENTQR, double>, a, stream);
-    return marg_dispatch(D, [&](auto M, auto real) { return marg_tile_launch(&marginal_kernel<decltype(M)::value, decltype(real)>, a, stream); });
+    return marg_dispatch_obs(D, [&](auto M, auto real, auto masked) { return marg_tile_launch(&marginal_kernel<decltype(M)::value, decltype(real), decltype(masked)::value>, a, stream); });
 }
 
 // The coarse flags of a pass: flags()[i] = 1 if subject i's grid was too coarse at any row, written by the tile kernels (a chunk's at flags() + c0), and their
@@ -212,7 +229,7 @@ static void psis_out12(const double* s8, int64_t N, int64_t S, int Q, int64_t n_
 // buffers the source owns (caller data: all four; a farm: its table of rows; an engine: none, everything is read in place).
 struct ItemSource {
     MargData D{}; const double* rows = nullptr; int64_t n_rows = 0; hipStream_t stream = nullptr;
-    DevBuf dY, dC, dX, dRows;
+    DevBuf dY, dC, dX, dRows, dIdx, dOff;
 };
 // an engine's resident data set and its own post-burn-in rows, read in place (EngineBase::item_source: the refusals of a shard, a poisoned state, no data set and
 // too few rows, in this order, after the model's)
@@ -250,8 +267,11 @@ static int item_source(erm_farm_handle f, int pass, ItemSource& S, int family = 
 // caller-supplied data and rows (erm_marginal_loglik, erm_score, erm_plausible_values): validated on the host, then uploaded to `device` row-major in fp64, as the
 // kernels read an engine's, for the NULL stream.  min_rows / rows_msg: the fewest rows the caller's outputs need.  FAMILY_QUANTILE (the model is LatentQr): q_rt is
 // the quantile level, and every row's Sigma_p[2,2], the scale of zeta's law, must be positive.
+// obs != NULL (the masked entries): the observed mask, column-major as Y.  The walk that validates the cells compacts them into erm_obs.hpp's lists,
+// which are uploaded in the place of the row-major Y and logT; Y and logT are read, and validated, at observed cells only; n_obs [n_subj] (may be NULL) receives n_i.
 static int item_source(const char* what, int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
-                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, ItemSource& S, int family = FAMILY_GAUSSIAN, double q_rt = 0.0)
+                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, ItemSource& S, int family = FAMILY_GAUSSIAN, double q_rt = 0.0,
+                       const uint8_t* obs = nullptr, int32_t* n_obs = nullptr)
 {
     const ModelTraits mt = model_traits(model);
     if (n_subj <= 0 || n_subj >= (1LL << 32) || n_item <= 0 || n_item > 896 || n_feat < 0 || n_feat > MARG_MAXF) return fail(ERM_ERR_ARG, "n_subj, n_item (1 .. 896) or n_feat (0 .. " + std::to_string(MARG_MAXF) + ") out of range");
@@ -265,9 +285,23 @@ static int item_source(const char* what, int device, int model, int64_t n_subj, 
     const size_t NJ = (size_t)N * J;
     // ---- the inputs: a NaN anywhere, then rows outside the model's domain
     for (size_t e = 0; e < (size_t)n_rows * wi; ++e) if (rows[e] != rows[e]) return fail(ERM_ERR_NONFINITE, "NaN in row " + std::to_string(e / (size_t)wi));
-    if (mt.rt) for (size_t e = 0; e < NJ; ++e) if (logT[e] != logT[e]) return fail(ERM_ERR_NONFINITE, "NaN in logT");
+    std::vector<int64_t> off;
+    std::vector<uint16_t> idx; std::vector<uint8_t> yl; std::vector<double> tl;
+    int bad_cells = OBS_OK;
+    if (obs) {
+        off.resize((size_t)N + 1);
+        std::vector<int64_t> cur((size_t)N);
+        int64_t bad = 0;
+        if (obs_offsets(obs, N, J, off.data(), &bad) != OBS_OK) return fail(ERM_ERR_ARG, "obs must be 0/1 (subject " + std::to_string(bad % N) + ", item " + std::to_string(bad / N) + ")");
+        const size_t total = (size_t)off[(size_t)N];
+        idx.resize(total); yl.resize(total); if (mt.rt) tl.resize(total);
+        bad_cells = obs_compact(Y, mt.rt ? logT : nullptr, obs, N, J, off.data(), cur.data(), idx.data(), yl.data(), mt.rt ? tl.data() : nullptr, &bad);
+        if (bad_cells == OBS_NAN_LOGT) return fail(ERM_ERR_NONFINITE, "NaN in logT at an observed cell");
+    }
+    else if (mt.rt) for (size_t e = 0; e < NJ; ++e) if (logT[e] != logT[e]) return fail(ERM_ERR_NONFINITE, "NaN in logT");
     for (size_t e = 0; e < (size_t)N * Fk; ++e) if (X[e] != X[e]) return fail(ERM_ERR_NONFINITE, "NaN in X");
-    for (size_t e = 0; e < NJ; ++e) if (Y[e] > 1) return fail(ERM_ERR_ARG, "Y must be 0/1");
+    if (bad_cells == OBS_BAD_Y) return fail(ERM_ERR_ARG, "Y must be 0/1 at every observed cell");
+    if (!obs) for (size_t e = 0; e < NJ; ++e) if (Y[e] > 1) return fail(ERM_ERR_ARG, "Y must be 0/1");
     if (mt.rt) for (int64_t r = 0; r < n_rows; ++r) {
         const double* row = rows + (size_t)r * wi;
         for (int j = 0; j < J; ++j) if (!(row[3 * J + j] > 0.0)) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": sig2t must be positive");
@@ -277,14 +311,28 @@ static int item_source(const char* what, int device, int model, int64_t n_subj, 
         if (marg_law(model, 0.0, 0.0, 0.0, Sp).v < 0.0) return fail(ERM_ERR_ARG, "row " + std::to_string(r) + ": the conditional variance of zeta given theta is negative (Sigma_p is not positive semi-definite)");
     }
     HIPCHK(hipSetDevice(device));
-    // ---- upload: the data set row-major in fp64, as the kernel reads an engine's
-    {
+    // ---- upload: the data set row-major in fp64, as the kernel reads an engine's -- or its compacted lists (one spare element: an empty list still has a base)
+    if (obs) {
+        const size_t total = idx.size();
+        if (int rc = S.dOff.try_alloc(off.size() * sizeof(int64_t), what)) return rc;
+        if (int rc = S.dIdx.try_alloc((total + 1) * sizeof(uint16_t), what)) return rc;
+        if (int rc = S.dY.try_alloc(total + 1, what)) return rc;
+        if (mt.rt) if (int rc = S.dC.try_alloc((total + 1) * sizeof(double), what)) return rc;
+        H2D(S.dOff.p, off.data(), off.size() * sizeof(int64_t));
+        if (total > 0) {
+            H2D(S.dIdx.p, idx.data(), total * sizeof(uint16_t));
+            H2D(S.dY.p, yl.data(), total);
+            if (mt.rt) H2D(S.dC.p, tl.data(), total * sizeof(double));
+        }
+        if (n_obs) for (int64_t i = 0; i < N; ++i) n_obs[i] = (int32_t)(off[(size_t)i + 1] - off[(size_t)i]);
+    }
+    else {
         std::vector<uint8_t> y(NJ);
         cols_to_rows(Y, y.data(), N, (int64_t)J);
         if (int rc = S.dY.try_alloc(NJ, what)) return rc;
         H2D(S.dY.p, y.data(), NJ);
     }
-    if (mt.rt) {
+    if (mt.rt && !obs) {
         std::vector<double> c(NJ);
         cols_to_rows(logT, c.data(), N, (int64_t)J);
         if (int rc = S.dC.try_alloc(NJ * sizeof(double), what)) return rc;
@@ -298,7 +346,7 @@ static int item_source(const char* what, int device, int model, int64_t n_subj, 
     }
     if (int rc = S.dRows.try_alloc((size_t)n_rows * wi * sizeof(double), what)) return rc;
     H2D(S.dRows.p, rows, (size_t)n_rows * wi * sizeof(double));
-    S.D = MargData{S.dY.as<uint8_t>(), S.dC.p, S.dX.p, nullptr, N, J, Fk, model, sizeof(double), q_rt};
+    S.D = MargData{S.dY.as<uint8_t>(), S.dC.p, S.dX.p, nullptr, N, J, Fk, model, sizeof(double), q_rt, S.dIdx.as<uint16_t>(), S.dOff.as<int64_t>()};
     S.rows = S.dRows.as<double>(); S.n_rows = n_rows;
     return 0;
 }
@@ -367,11 +415,11 @@ static int item_scores(const ItemSource& S, int Q, int weighting, double* score,
     if (int rc = coarse.alloc(N, what)) return rc;
     MargArgs a = marg_args(S.D, S.rows, S.n_rows, Q);
     a.coarse = coarse.flags();
-    auto launch = [&](auto M, auto real) -> int {
-        if (weighting == SCORE_LIKELIHOOD) return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), true>, a, S.stream, dScore.as<double>());
-        return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), false>, a, S.stream, dScore.as<double>());
+    auto launch = [&](auto M, auto real, auto masked) -> int {
+        if (weighting == SCORE_LIKELIHOOD) return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), true, decltype(masked)::value>, a, S.stream, dScore.as<double>());
+        return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), false, decltype(masked)::value>, a, S.stream, dScore.as<double>());
     };
-    if (int rc = marg_dispatch(S.D, launch)) return rc;
+    if (int rc = marg_dispatch_obs(S.D, launch)) return rc;
     unsigned long long nc = 0;
     if (int rc = coarse.count(S.stream, &nc)) return rc;
     HIPCHK(hipMemcpy(score, dScore.p, (size_t)N * SCORE_COLS * sizeof(double), hipMemcpyDeviceToHost));
@@ -396,7 +444,7 @@ static int item_pv(const ItemSource& S, int Q, int64_t K, uint64_t seed, double*
         MargArgs a = marg_args(marg_chunk(S.D, c0, nc), S.rows, S.n_rows, Q);
         a.coarse = flags.flags() + c0;
         const PvArgs p{(long long)K, (unsigned long long)seed, (long long)c0, dPv.as<double>(), dNode.as<int>()};
-        if (int rc = marg_dispatch(S.D, [&](auto M, auto real) { return marg_tile_launch(&pv_kernel<decltype(M)::value, decltype(real)>, a, S.stream, p); })) return rc;
+        if (int rc = marg_dispatch_obs(S.D, [&](auto M, auto real, auto masked) { return marg_tile_launch(&pv_kernel<decltype(M)::value, decltype(real), decltype(masked)::value>, a, S.stream, p); })) return rc;
         HIPCHK(hipMemcpy2D(pv + c0, (size_t)N * sizeof(double), dPv.p, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), (size_t)(2 * K), hipMemcpyDeviceToHost));
         if (node) HIPCHK(hipMemcpy2D(node + c0, (size_t)N * sizeof(int), dNode.p, (size_t)nc * sizeof(int), (size_t)nc * sizeof(int), (size_t)K, hipMemcpyDeviceToHost));
     }

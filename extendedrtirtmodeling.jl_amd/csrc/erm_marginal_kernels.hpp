@@ -39,7 +39,17 @@ struct MargArgs {
     double2* acc_ms; double2* acc_w;                      // [N] or nullptr
     unsigned int* coarse;                                 // [N]: 1 if S < MARG_COARSE_S at any row; or nullptr
     double q;                                             // LatentQr: the quantile level q_rt of qmarg_T (erm_qmarginal.hpp); unread otherwise
+    // the MASKED instantiations (erm_obs.hpp's compacted cell lists), unread otherwise: subject i's list is the positions off[i] .. off[i + 1] of
+    // idx (the item), Y (the response) and C (the log-time, fp64), rising in the item
+    const unsigned short* idx; const long long* off;
 };
+// where subject i's cells start in Y / C (and idx), and how many there are: the row i of [N][J], or the list of erm_obs.hpp
+template <bool MASKED>
+__device__ __forceinline__ size_t marg_cells(const MargArgs& A, long long i, int& n)
+{
+    if constexpr (MASKED) { const long long o = A.off[i]; n = (int)(A.off[i + 1] - o); return (size_t)o; }
+    else { n = A.J; return (size_t)i * A.J; }
+}
 // doubles of LDS per half of the row buffer: the row | g [J] | log sig2t [J]
 __host__ __device__ constexpr long long marg_row_lds(long long ld, int J) { return ld + 2 * (long long)J; }
 
@@ -83,9 +93,11 @@ __device__ __forceinline__ MargLaw marg_stage_law(const double* sa, int J, int F
     w.v = fmax(w.v, 0.0);
     return w;
 }
-// item sums: lane s, items s, s + 8, ... in order; then the butterfly
-template <int MODEL, typename real>
-__device__ __forceinline__ void marg_item_sums(const MargArgs& A, const double* sa, const uint8_t* Yi, const real* Ci, int s, MargSums& ms, double& A1, double& A0)
+// item sums: lane s, items s, s + 8, ... in order; then the butterfly.  MASKED: lane s, the list positions s, s + 8, ... of the subject's n observed cells (Yi, Ci
+// and Ii are the list's); the trip count is the subject's own, the butterfly stands after the loop and every lane reaches it
+template <int MODEL, typename real, bool MASKED = false>
+__device__ __forceinline__ void marg_item_sums(const MargArgs& A, const double* sa, const uint8_t* Yi, const real* Ci, int s, MargSums& ms, double& A1, double& A0,
+                                               const unsigned short* Ii = nullptr, int n = 0)
 {
     constexpr bool RT = MODEL != MLIRT;
     constexpr ModelTraits MT = model_traits(MODEL);
@@ -93,6 +105,16 @@ __device__ __forceinline__ void marg_item_sums(const MargArgs& A, const double* 
     const double* q = sa + 4 * J;
     ms = MargSums{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     A1 = 0.0; A0 = 0.0;
+    if constexpr (MASKED) {
+        for (int k = s; k < n; k += MARG_LANES) {
+            const int j = Ii[k];
+            if (Yi[k] != 0) { const double a = sa[j]; A1 += a; A0 += a * sa[J + j]; }
+            if constexpr (RT) {
+                const double t = (double)Ci[k] + (A.cm ? A.cm[j] : 0.0);
+                marg_sums_add(ms, sa[A.ld + j], sa[A.ld + J + j], sa[2 * J + j] - t, MT.rho ? q[j] : 0.0);
+            }
+        }
+    } else
     for (int j = s; j < J; j += MARG_LANES) {
         if (Yi[j] != 0) { const double a = sa[j]; A1 += a; A0 += a * sa[J + j]; }
         if constexpr (RT) {
@@ -110,9 +132,11 @@ __device__ __forceinline__ void marg_item_sums(const MargArgs& A, const double* 
 }
 // nodes: lane s, nodes s, s + 8, ... in chunks of MARG_CHUNK; sink(e_q, z_q) -- or sink(e_q, z_q, q) if it takes the node's index too -- receives the lane's nodes in order.
 // LatentQr takes qmarg_T at the level q_rt for marg_T: two logPhi per node beside the J evaluations of log(1 + e^eta)
-template <int MODEL, typename Sink>
+// MASKED (Ii: the subject's list of n items, rising): every node's chain runs over the list in order -- the eight lanes of a subject read the same Ii[k], a broadcast,
+// once per MARG_CHUNK chains -- and n stands for J in T.  The trip count is the subject's own; nothing inside the loop crosses lanes.
+template <int MODEL, bool MASKED = false, typename Sink>
 __device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, int s, double h, double log_h, const MargLaw& w, const MargSums& ms, double A1, double A0, Sink&& sink,
-                                                double q_rt = 0.0)
+                                                double q_rt = 0.0, const unsigned short* Ii = nullptr, int n = 0)
 {
     for (int q0 = s; q0 < Q; q0 += MARG_LANES * MARG_CHUNK) {
         double th[MARG_CHUNK], lse[MARG_CHUNK];
@@ -122,6 +146,14 @@ __device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, 
             th[c] = w.mu + w.sd * marg_node(qq < Q ? qq : Q - 1, h);      // (a slot past the last node repeats it and is dropped below)
             lse[c] = 0.0;
         }
+        if constexpr (MASKED) {
+            for (int k = 0; k < n; ++k) {
+                const int j = Ii[k];
+                const double a = sa[j], b = sa[J + j];
+#pragma unroll
+                for (int c = 0; c < MARG_CHUNK; ++c) lse[c] += marg_log1pexp(a * (th[c] - b));
+            }
+        } else
         for (int j = 0; j < J; ++j) {
             const double a = sa[j], b = sa[J + j];
 #pragma unroll
@@ -134,7 +166,7 @@ __device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, 
                 const double z = marg_node(qq, h);
                 double e = marg_log_weight(z, log_h) + (th[c] * A1 - A0 - lse[c]);
                 if constexpr (MODEL == LATENTQR) e += qmarg_T(ms, J, w, th[c], q_rt);
-                else if constexpr (MODEL != MLIRT) e += marg_T(ms, J, w, th[c]);
+                else if constexpr (MODEL != MLIRT) e += marg_T(ms, MASKED ? n : J, w, th[c]);
                 if constexpr (std::is_invocable_v<Sink, double, double, int>) sink(e, z, qq);
                 else sink(e, z);
             }
@@ -142,7 +174,10 @@ __device__ __forceinline__ void marg_lane_nodes(const double* sa, int J, int Q, 
     }
 }
 
-template <int MODEL, typename real>
+// MASKED: the same kernel over incomplete response patterns.  A subject's cells are its list (marg_cells); the item sums and the node chains run
+// over the list, so the work is proportional to the observed cells.  The subjects of a wave have different trip counts: a finished subject's lanes idle until the
+// wave's longest is done, and every butterfly and barrier stands outside those loops.  n = 0 is an ordinary case: every sum is empty and T = 0.
+template <int MODEL, typename real, bool MASKED = false>
 __global__ void __launch_bounds__(256) marginal_kernel(const MargArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -154,8 +189,11 @@ __global__ void __launch_bounds__(256) marginal_kernel(const MargArgs A)
     const long long i0 = (long long)blockIdx.x * MARG_TILE;
     const bool ok = i0 + r < A.N;
     const long long i = ok ? i0 + r : A.N - 1;            // idle lanes repeat the last subject: every lane takes part in the butterflies and the barriers
-    const uint8_t* Yi = A.Y + (size_t)i * J;
-    const real* Ci = RT ? reinterpret_cast<const real*>(A.C) + (size_t)i * J : nullptr;
+    int n;
+    const size_t at = marg_cells<MASKED>(A, i, n);
+    const uint8_t* Yi = A.Y + at;
+    const real* Ci = RT ? reinterpret_cast<const real*>(A.C) + at : nullptr;
+    const unsigned short* Ii = MASKED ? A.idx + at : nullptr;
     double x[MARG_MAXF];
     marg_load_x<MODEL, real>(A, i, x);
     marg_stage<MODEL>(A, 0, sh, tid);
@@ -170,9 +208,9 @@ __global__ void __launch_bounds__(256) marginal_kernel(const MargArgs A)
         const MargLaw w = marg_stage_law<MODEL>(sa, J, F, x);
         MargSums ms;
         double A1, A0;
-        marg_item_sums<MODEL, real>(A, sa, Yi, Ci, s, ms, A1, A0);
+        marg_item_sums<MODEL, real, MASKED>(A, sa, Yi, Ci, s, ms, A1, A0, Ii, n);
         MargMS part{0.0, 0.0};
-        marg_lane_nodes<MODEL>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double) { marg_ms_add(part, e); }, A.q);
+        marg_lane_nodes<MODEL, MASKED>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double) { marg_ms_add(part, e); }, A.q, Ii, n);
         for (int m = 1; m < MARG_LANES; m <<= 1) {
             const MargMS o{__shfl_xor(part.M, m, 64), __shfl_xor(part.S, m, 64)};
             part = marg_ms_merge(part, o);

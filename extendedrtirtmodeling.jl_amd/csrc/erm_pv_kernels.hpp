@@ -15,6 +15,7 @@
 //   4. finish      lane 0 draws the finishing block at {i, k, 0xFFFFFFFF} and stores theta, zeta and q* (pv_finish).
 // The subject index in the counter is i_base + the index within the launch: a chunk of a larger data set draws what the whole would.  Plain vector loads and
 // stores, no atomics: every output word has one writer.
+// MASKED: incomplete response patterns, as marginal_kernel's -- the subject's list of observed cells through the same helpers; the counters are unchanged.
 #pragma once
 #include "erm_score_kernels.hpp"
 #include "erm_pv.hpp"
@@ -30,7 +31,7 @@ struct PvArgs {
 };
 
 // A: marginal_kernel's arguments (l_out, acc_ms, acc_w unused; coarse [N] receives the flags: S < MARG_COARSE_S at a row the subject used)
-template <int MODEL, typename real>
+template <int MODEL, typename real, bool MASKED = false>
 __global__ void __launch_bounds__(256) pv_kernel(const MargArgs A, const PvArgs P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -42,8 +43,11 @@ __global__ void __launch_bounds__(256) pv_kernel(const MargArgs A, const PvArgs 
     const long long i0 = (long long)blockIdx.x * MARG_TILE;
     const bool ok = i0 + r < A.N;
     const long long i = ok ? i0 + r : A.N - 1;            // idle lanes repeat the last subject: every lane takes part in the butterflies and the barriers
-    const uint8_t* Yi = A.Y + (size_t)i * J;
-    const real* Ci = RT ? reinterpret_cast<const real*>(A.C) + (size_t)i * J : nullptr;
+    int n;
+    const size_t at = marg_cells<MASKED>(A, i, n);
+    const uint8_t* Yi = A.Y + at;
+    const real* Ci = RT ? reinterpret_cast<const real*>(A.C) + at : nullptr;
+    const unsigned short* Ii = MASKED ? A.idx + at : nullptr;
     double x[MARG_MAXF];
     marg_load_x<MODEL, real>(A, i, x);
     marg_stage<MODEL>(A, pv_row(0, P.K, A.n_rows), sh, tid);
@@ -58,15 +62,15 @@ __global__ void __launch_bounds__(256) pv_kernel(const MargArgs A, const PvArgs 
         const MargLaw w = marg_stage_law<MODEL>(sa, J, F, x);
         MargSums ms;
         double A1, A0;
-        marg_item_sums<MODEL, real>(A, sa, Yi, Ci, s, ms, A1, A0);
+        marg_item_sums<MODEL, real, MASKED>(A, sa, Yi, Ci, s, ms, A1, A0, Ii, n);
         ScoreMS part{0.0, 0.0, 0.0, 0.0};
         PvBest best{0.0, -1};
-        marg_lane_nodes<MODEL>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double z, int q) {
+        marg_lane_nodes<MODEL, MASKED>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double z, int q) {
             score_ms_add(part, e, z);
             uint32_t w0, w1, w2, w3;
             philox4x32_10(ci, (uint32_t)k, (uint32_t)q, c3, k0, k1, w0, w1, w2, w3);
             pv_best_add(best, e + pv_gumbel(w0), q);
-        });
+        }, 0.0, Ii, n);
         for (int m = 1; m < MARG_LANES; m <<= 1) {
             const ScoreMS o{__shfl_xor(part.M, m, 64), __shfl_xor(part.S, m, 64), __shfl_xor(part.S1, m, 64), __shfl_xor(part.S2, m, 64)};
             part = score_ms_merge(part, o);

@@ -9,6 +9,7 @@
 //   4. accumulate  the row's moments (score_row, with the zeta conditional of score_zeta from the item sums the lanes already hold) enter the subject's ScoreAcc --
 //                  eleven doubles in registers from the first row to the last; WEIGHTED chooses omega_s = exp(l_s - Lambda) over omega_s = 1.
 // One store of seven doubles per subject at the end.  Plain vector loads and stores, no atomics: every output word has one writer.
+// MASKED: incomplete response patterns, as marginal_kernel's -- the subject's list of observed cells through the same helpers.
 #pragma once
 #include "erm_marginal_kernels.hpp"
 #include "erm_score.hpp"
@@ -16,7 +17,7 @@
 namespace erm {
 
 // A: marginal_kernel's arguments (l_out, acc_ms, acc_w unused; coarse [N] receives the flags marginal_count_kernel adds); score: column-major [N][SCORE_COLS]
-template <int MODEL, typename real, bool WEIGHTED>
+template <int MODEL, typename real, bool WEIGHTED, bool MASKED = false>
 __global__ void __launch_bounds__(256) score_kernel(const MargArgs A, double* __restrict__ score)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -28,8 +29,11 @@ __global__ void __launch_bounds__(256) score_kernel(const MargArgs A, double* __
     const long long i0 = (long long)blockIdx.x * MARG_TILE;
     const bool ok = i0 + r < A.N;
     const long long i = ok ? i0 + r : A.N - 1;            // idle lanes repeat the last subject: every lane takes part in the butterflies and the barriers
-    const uint8_t* Yi = A.Y + (size_t)i * J;
-    const real* Ci = RT ? reinterpret_cast<const real*>(A.C) + (size_t)i * J : nullptr;
+    int n;
+    const size_t at = marg_cells<MASKED>(A, i, n);
+    const uint8_t* Yi = A.Y + at;
+    const real* Ci = RT ? reinterpret_cast<const real*>(A.C) + at : nullptr;
+    const unsigned short* Ii = MASKED ? A.idx + at : nullptr;
     double x[MARG_MAXF];
     marg_load_x<MODEL, real>(A, i, x);
     marg_stage<MODEL>(A, 0, sh, tid);
@@ -44,9 +48,9 @@ __global__ void __launch_bounds__(256) score_kernel(const MargArgs A, double* __
         const MargLaw w = marg_stage_law<MODEL>(sa, J, F, x);
         MargSums ms;
         double A1, A0;
-        marg_item_sums<MODEL, real>(A, sa, Yi, Ci, s, ms, A1, A0);
+        marg_item_sums<MODEL, real, MASKED>(A, sa, Yi, Ci, s, ms, A1, A0, Ii, n);
         ScoreMS part{0.0, 0.0, 0.0, 0.0};
-        marg_lane_nodes<MODEL>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double z) { score_ms_add(part, e, z); });
+        marg_lane_nodes<MODEL, MASKED>(sa, J, Q, s, h, log_h, w, ms, A1, A0, [&](double e, double z) { score_ms_add(part, e, z); }, 0.0, Ii, n);
         for (int m = 1; m < MARG_LANES; m <<= 1) {
             const ScoreMS o{__shfl_xor(part.M, m, 64), __shfl_xor(part.S, m, 64), __shfl_xor(part.S1, m, 64), __shfl_xor(part.S2, m, 64)};
             part = score_ms_merge(part, o);

@@ -2143,6 +2143,62 @@ int erm_plausible_values(int device, int model, int64_t n_subj, int32_t n_item, 
     return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
 }
 
+// ---- incomplete response patterns: the three caller-data entries with an observed mask.  obs == NULL is the complete entry itself.
+static void obs_all(int64_t n_subj, int32_t n_item, int32_t* n_obs) { if (n_obs) for (int64_t i = 0; i < n_subj; ++i) n_obs[i] = n_item; }
+int erm_marginal_loglik_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                               const double* rows, int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u, int32_t* n_obs)
+{
+    if (!obs) {
+        if (int rc = erm_marginal_loglik(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, l, out10, lppd_u, p_u)) return rc;
+        obs_all(n_subj, n_item, n_obs);
+        return 0;
+    }
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    ItemSource S;
+    if (int rc = item_source("erm_marginal_loglik_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, out10 || lppd_u || p_u ? 2 : 1,
+                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S, FAMILY_GAUSSIAN, 0.0, obs, n_obs)) return rc;
+    return item_waic(S, Q, l, out10, lppd_u, p_u);
+}
+
+int erm_score_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                     const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4, int32_t* n_obs)
+{
+    if (!obs) {
+        if (int rc = erm_score(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, weighting, score, out4)) return rc;
+        obs_all(n_subj, n_item, n_obs);
+        return 0;
+    }
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
+    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
+    ItemSource S;
+    if (int rc = item_source("erm_score_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN, 0.0,
+                             obs, n_obs)) return rc;
+    return item_scores(S, Q, weighting, score, out4);
+}
+
+int erm_plausible_values_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                                const double* rows, int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4,
+                                int32_t* n_obs)
+{
+    if (!obs) {
+        if (int rc = erm_plausible_values(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, n_draws, seed, pv, node, coarse, out4)) return rc;
+        obs_all(n_subj, n_item, n_obs);
+        return 0;
+    }
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
+    ItemSource S;
+    if (int rc = item_source("erm_plausible_values_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S,
+                             FAMILY_GAUSSIAN, 0.0, obs, n_obs)) return rc;
+    return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
+}
+
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out)
 {
     if (n <= 0 || !out || !psi4) return fail(ERM_ERR_ARG, "bad n / psi / out");

@@ -628,7 +628,32 @@ def psisLoo(L, device=0, want_lw=False):
 # ------------------------------------------------------------------------------------------------------------------
 def _scores_output(r, weighting="equal") -> OutputScores:
     return OutputScores(theta=r["theta"], thetaSd=r["thetaSd"], zeta=r["zeta"], zetaSd=r["zetaSd"], cov=r["cov"], rowEss=r["rowEss"], coarse=r["coarse"],
-                        nRows=r["nRows"], nNodes=r["nNodes"], nCoarse=r["nCoarse"], weighting=weighting)
+                        nRows=r["nRows"], nNodes=r["nNodes"], nCoarse=r["nCoarse"], weighting=weighting, nObs=r.get("nObs"))
+
+
+# Incomplete response patterns (include/ertirt.h: erm_score_masked): scoreRespondents and drawPlausibleValues take obs [N, J], 1 = the cell was
+# administered.  Calibration keeps its complete-data contract.
+def observedMask(Y, logT=None) -> np.ndarray:
+    """The observed mask of a data set whose missing cells are marked in the data: uint8 [N, J], 1 where Y is 0 or 1 and logT is finite (logT=None, GibbsMlIrt: Y
+    alone).  One bit per cell: a response without a time, or a time without a response, counts as not administered."""
+    Y = np.asarray(Y, dtype=np.float64)
+    ok = (Y == 0.0) | (Y == 1.0)
+    if logT is not None:
+        lt = np.asarray(logT, dtype=np.float64)
+        if lt.shape != Y.shape:
+            raise ValueError("logT does not match Y")
+        ok &= np.isfinite(lt)
+    return ok.astype(np.uint8)
+
+
+def _masked_data(Y, logT, obs):
+    """Y and logT with the unobserved cells set to 0 (the library never reads them; a NaN in a float Y would not survive the conversion to uint8)."""
+    if obs is None:
+        return Y, logT
+    O = np.asarray(obs) != 0
+    if O.shape != np.shape(Y):
+        raise ValueError("obs does not match Y")
+    return np.where(O, np.asarray(Y), 0), None if logT is None else np.where(O, np.asarray(logT, dtype=np.float64), 0.0)
 
 
 def getScores(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES) -> OutputScores:
@@ -640,14 +665,17 @@ def getScores(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES) -> OutputScores:
     return _scores_output(_marginal_source(MCMC, "getScores").scores(Q))
 
 
-def scoreRespondents(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal", device=0) -> OutputScores:
+def scoreRespondents(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal", device=0, obs=None) -> OutputScores:
     """Scores of respondents -- new ones, or those of a run that is no longer resident -- against saved item-trace rows [R, item_trace_width] (Engine.item_trace()),
     on the device (erm_score).  model: the model code (_lib.MODEL_*); Y, logT [N, J], X [N, F] or None.  weighting "equal": every row counts once, the usual
-    operational scoring; "likelihood": row s counts exp(l_s), the posterior of a new respondent given their own data and the saved item posterior."""
+    operational scoring; "likelihood": row s counts exp(l_s), the posterior of a new respondent given their own data and the saved item posterior.
+    obs [N, J], 0/1 (observedMask builds one): respondents who did not see every item (erm_score_masked) -- every sum over the items runs over the observed cells,
+    a respondent with none gets the population law; the result carries nObs, the observed cells per respondent."""
     if model not in _lib.MARGINAL_MODELS:
         raise ValueError("scoreRespondents serves the five models without quantile weights")
     w = _lib.score_weighting(weighting)
-    return _scores_output(_lib.score(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), weighting=w, device=device), "likelihood" if w else "equal")
+    Y, logT = _masked_data(Y, logT, obs)
+    return _scores_output(_lib.score(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), weighting=w, device=device, obs=obs), "likelihood" if w else "equal")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -656,7 +684,8 @@ def scoreRespondents(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighti
 # the row's mean and variance, and draws zeta from its Gaussian conditional.
 # ------------------------------------------------------------------------------------------------------------------
 def _pv_output(r) -> OutputPv:
-    return OutputPv(theta=r["theta"], zeta=r["zeta"], node=r["node"], coarse=r["coarse"], nRows=r["nRows"], nNodes=r["nNodes"], nCoarse=r["nCoarse"], seed=r["seed"])
+    return OutputPv(theta=r["theta"], zeta=r["zeta"], node=r["node"], coarse=r["coarse"], nRows=r["nRows"], nNodes=r["nNodes"], nCoarse=r["nCoarse"], seed=r["seed"],
+                    nObs=r.get("nObs"))
 
 
 def getPlausibleValues(MCMC: _GibbsBase, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES) -> OutputPv:
@@ -668,13 +697,15 @@ def getPlausibleValues(MCMC: _GibbsBase, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nod
     return _pv_output(_marginal_source(MCMC, "getPlausibleValues").plausible_values(K, seed, Q))
 
 
-def drawPlausibleValues(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES, device=0) -> OutputPv:
+def drawPlausibleValues(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES, device=0, obs=None) -> OutputPv:
     """Plausible values of respondents -- new ones, or those of a run that is no longer resident -- against saved item-trace rows [R, item_trace_width]
-    (Engine.item_trace()), on the device (erm_plausible_values).  model: the model code (_lib.MODEL_*); Y, logT [N, J], X [N, F] or None; every row counts once."""
+    (Engine.item_trace()), on the device (erm_plausible_values).  model: the model code (_lib.MODEL_*); Y, logT [N, J], X [N, F] or None; every row counts once.
+    obs [N, J], 0/1: respondents who did not see every item (erm_plausible_values_masked), as scoreRespondents takes it; the result carries nObs."""
     if model not in _lib.MARGINAL_MODELS:
         raise ValueError("drawPlausibleValues serves the five models without quantile weights")
     Q, K, seed = _lib.marginal_nodes(nodes), _lib.pv_draws(K), _lib.pv_seed(seed)
-    return _pv_output(_lib.plausible_values(model, Y, logT, X, rows, K=K, seed=seed, nodes=Q, device=device))
+    Y, logT = _masked_data(Y, logT, obs)
+    return _pv_output(_lib.plausible_values(model, Y, logT, X, rows, K=K, seed=seed, nodes=Q, device=device, obs=obs))
 
 
 # ------------------------------------------------------------------------------------------------------------------

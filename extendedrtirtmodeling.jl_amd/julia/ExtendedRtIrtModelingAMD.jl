@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getWaicMarginalQr, getLooMarginalQr, quantileMarginalLogLik, getScores, scoreRespondents, getPlausibleValues, drawPlausibleValues, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getWaicMarginalQr, getLooMarginalQr, quantileMarginalLogLik, getScores, scoreRespondents, getPlausibleValues, drawPlausibleValues, observedMask, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -545,21 +545,32 @@ function getScores(M::GibbsAMD; nodes::Integer = 61)
 end
 
 """
-    scoreRespondents(model, Y, logT, X, rows; nodes = 61, weighting = :equal, device = 0)
+    scoreRespondents(model, Y, logT, X, rows; nodes = 61, weighting = :equal, device = 0, obs = nothing)
 
 `getScores` for caller-supplied respondents (`Y` UInt8 nSubj x nItem, `logT`, `X` nSubj x nFeat) against saved item-trace rows (`rows` is item_trace_width x nRows,
 as `marginalLogLik` takes them), on the device (`erm_score`).  `weighting = :equal`: every row counts once, the usual operational scoring; `:likelihood`: row s
 counts exp(l_s), the posterior of a new respondent given their own data and the saved item posterior.
+`obs` (UInt8 nSubj x nItem, 1 = the cell was administered): respondents who did not see every item (`erm_score_masked`) -- every sum over the items runs over the
+observed cells, `Y` and `logT` at the others are never read; the result then also has `nObs`, the observed cells per respondent.
 """
 function scoreRespondents(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}; nodes::Integer = 61,
-                          weighting::Symbol = :equal, device::Integer = 0)
+                          weighting::Symbol = :equal, device::Integer = 0, obs::Union{Nothing,Matrix{UInt8}} = nothing)
     N, J = size(Y)
     w = weighting == :equal ? 0 : weighting == :likelihood ? 1 : error("weighting must be :equal or :likelihood")
     score, out = zeros(N, 7), zeros(4)
-    check(ccall((:erm_score, LIB[]), Cint,
-                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
-                device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, w, score, out))
-    return scoresTuple(score, out)
+    if obs === nothing
+        check(ccall((:erm_score, LIB[]), Cint,
+                    (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                    device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, w, score, out))
+        return scoresTuple(score, out)
+    end
+    size(obs) == (N, J) || error("obs does not match Y")
+    nObs = zeros(Int32, N)
+    check(ccall((:erm_score_masked, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}),
+                device, model, N, J, size(X, 2), Y, logT, X, obs, rows, size(rows, 2), nodes, w, score, out, nObs))
+    return merge(scoresTuple(score, out), (nObs = nObs,))
 end
 
 # pv as erm_get_plausible_values fills it (column-major [nSubj][K][2]), node [nSubj][K], coarse [nSubj] and out4 -> a named tuple
@@ -591,22 +602,41 @@ function getPlausibleValues(M::GibbsAMD; K::Integer = 5, seed::Integer = 20191, 
 end
 
 """
-    drawPlausibleValues(model, Y, logT, X, rows; K = 5, seed = 20191, nodes = 61, device = 0)
+    drawPlausibleValues(model, Y, logT, X, rows; K = 5, seed = 20191, nodes = 61, device = 0, obs = nothing)
 
 `getPlausibleValues` for caller-supplied respondents (`Y` UInt8 nSubj x nItem, `logT`, `X` nSubj x nFeat) against saved item-trace rows (`rows` is
 item_trace_width x nRows, as `marginalLogLik` takes them), on the device (`erm_plausible_values`); every row counts once.
+`obs` (UInt8 nSubj x nItem, 1 = the cell was administered): respondents who did not see every item (`erm_plausible_values_masked`), as `scoreRespondents` takes
+it; the result then also has `nObs`.
 """
 function drawPlausibleValues(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}; K::Integer = 5, seed::Integer = 20191,
-                             nodes::Integer = 61, device::Integer = 0)
+                             nodes::Integer = 61, device::Integer = 0, obs::Union{Nothing,Matrix{UInt8}} = nothing)
     N, J = size(Y)
     1 <= K <= 4096 || error("K must be in 1 .. 4096")
     pv, node, coarse, out = zeros(N, K, 2), zeros(Int32, N, K), zeros(Int32, N), zeros(4)
-    check(ccall((:erm_plausible_values, LIB[]), Cint,
-                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
-                 Ptr{Float64}),
-                device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, K, seed, pv, node, coarse, out))
-    return pvTuple(pv, node, coarse, out, UInt64(seed))
+    if obs === nothing
+        check(ccall((:erm_plausible_values, LIB[]), Cint,
+                    (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
+                     Ptr{Float64}),
+                    device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, K, seed, pv, node, coarse, out))
+        return pvTuple(pv, node, coarse, out, UInt64(seed))
+    end
+    size(obs) == (N, J) || error("obs does not match Y")
+    nObs = zeros(Int32, N)
+    check(ccall((:erm_plausible_values_masked, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Int64, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Int32},
+                 Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+                device, model, N, J, size(X, 2), Y, logT, X, obs, rows, size(rows, 2), nodes, K, seed, pv, node, coarse, out, nObs))
+    return merge(pvTuple(pv, node, coarse, out, UInt64(seed)), (nObs = nObs,))
 end
+
+"""
+    observedMask(Y, logT) -> Matrix{UInt8}
+
+The observed mask of a data set whose missing cells are marked in the data: 1 where `Y` is 0 or 1 and `logT` is finite (`logT = nothing`, GibbsMlIrt: `Y` alone).
+"""
+observedMask(Y::AbstractMatrix, logT::Union{Nothing,AbstractMatrix} = nothing) =
+    UInt8.(((Y .== 0) .| (Y .== 1)) .& (logT === nothing ? trues(size(Y)) : isfinite.(logT)))
 
 """
     setPointwise!(MCMC, unit)   # unit = :off | :subject | :cell

@@ -80,11 +80,46 @@ def _gaussian_rt_term(r, e, th, lt, lam, sg, rho, s11, m0, m1, v):
     return e, (P, np.sum(g[None, :] * (lam[None, :] - lt), axis=1), np.sum(g * rho))
 
 
-def _marginal_rows_host(model, Y, logT, X, rows, Q, rt_term=_gaussian_rt_term):
+def _obs_mask(obs, shape):
+    """The observed mask as a boolean (N, J) array: 1 = administered, 0 = not; anything else is refused."""
+    O = np.asarray(obs)
+    if O.shape != tuple(shape):
+        raise ValueError("obs does not match Y")
+    if not np.all((O == 0) | (O == 1)):
+        raise ValueError("obs must be 0/1")
+    return O.astype(bool)
+
+
+def _masked_gaussian_rt_term(O):
+    """_gaussian_rt_term over the observed cells O (N, J) alone, include/ertirt.h's definition for incomplete patterns restated: every sum over the items is a sum
+    over O_i -- P, L and the n_i of -(n_i / 2) log 2 pi become per-subject -- and lt holds 0 at the unobserved cells.  sums = (P (N,), R0 (N,), R1 (N,))."""
+    Of = O.astype(np.float64)
+    n = Of.sum(axis=1)
+
+    def term(r, e, th, lt, lam, sg, rho, s11, m0, m1, v):
+        g = Of * (1.0 / sg)[None, :]                                                  # (N, J): g_j at the observed cells, 0 elsewhere
+        d = lam[None, None, :] - lt[:, None, :] - rho[None, None, :] * th[:, :, None]
+        P, R, D = np.sum(g, axis=1)[:, None], np.sum(g[:, None, :] * d, axis=2), np.sum(g[:, None, :] * d * d, axis=2)
+        L = np.sum(Of * np.log(sg)[None, :], axis=1)[:, None]
+        m = np.asarray(m0)[:, None] + m1 * th if np.ndim(m0) else m0 + m1 * th
+        e = e - 0.5 * n[:, None] * np.log(2 * np.pi) - 0.5 * L - 0.5 * np.log1p(v * P) - 0.5 * (D + (P * m * m - 2 * R * m - v * R * R) / (1 + v * P))
+        return e, (P[:, 0], np.sum(g * (lam[None, :] - lt), axis=1), np.sum(g * rho[None, :], axis=1))
+    return term
+
+
+def _marginal_rows_host(model, Y, logT, X, rows, Q, rt_term=_gaussian_rt_term, obs=None):
     """The rule at every row for marginalLogLikHost, quantileMarginalLogLikHost, scoresHost and plausibleValuesHost: the row unpacked, the population law, the
     theta part of e, and the family's response-time term.  Yields (e (N, Q), z (Q,), law, sums) with law = (mu (N,), sd, m0, m1, v) and sums as rt_term returns
-    them (None for GibbsMlIrt)."""
+    them (None for GibbsMlIrt).  obs (N, J), 0/1: incomplete patterns -- the response part and the response-time term are sums over the observed cells alone (the
+    Gaussian family only); Y and logT at the unobserved cells are not read."""
     t = _lib.MODEL_TRAITS[model]
+    O = None if obs is None else _obs_mask(obs, np.shape(Y))
+    if O is not None:
+        if rt_term is not _gaussian_rt_term:
+            raise ValueError("an observed mask is served for the five models without quantile weights only")
+        Y = np.where(O, np.asarray(Y), 0)
+        logT = np.where(O, np.asarray(logT, dtype=np.float64), 0.0) if t.rt else None
+        rt_term = _masked_gaussian_rt_term(O)
     Y = np.asarray(Y, dtype=np.float64)
     N, J = Y.shape
     F = 0 if X is None or not t.sees_x else np.shape(X)[1]
@@ -115,7 +150,8 @@ def _marginal_rows_host(model, Y, logT, X, rows, Q, rt_term=_gaussian_rt_term):
                 mu, m0, m1, v = zero, zero, s12 / s11, s22 - s12 * s12 / s11
         th = mu[:, None] + np.sqrt(s11) * z[None, :]                                  # (N, Q)
         eta = a[None, None, :] * (th[:, :, None] - b[None, None, :])                  # (N, Q, J)
-        e = np.log(h) - 0.5 * np.log(2 * np.pi) - 0.5 * z[None, :] ** 2 + np.sum(Y[:, None, :] * eta - _log1pexp(eta), axis=2)
+        cell = Y[:, None, :] * eta - _log1pexp(eta)
+        e = np.log(h) - 0.5 * np.log(2 * np.pi) - 0.5 * z[None, :] ** 2 + (np.sum(cell, axis=2) if O is None else np.sum(np.where(O[:, None, :], cell, 0.0), axis=2))
         sums = None
         if t.rt:
             e, sums = rt_term(r, e, th, lt, lam, sg, rho, s11, m0, m1, v)
@@ -130,11 +166,11 @@ def _loglik_rows(rule, with_S):
     return (out, outS) if with_S else out
 
 
-def marginalLogLikHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, with_S=False) -> np.ndarray:
+def marginalLogLikHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, with_S=False, obs=None) -> np.ndarray:
     """l_i^(s) of the marginal WAIC with numpy (the test twin of marginal_kernel): an (R, N) array for the item-trace rows [R, item_trace_width] (as
     Engine.item_trace() returns them) and the data Y, logT [N, J], X [N, F] or None.  with_S=True also returns S = sum_q exp(e_q - max_q e_q) per (row, subject):
-    S < 2 marks a posterior too narrow for the rule."""
-    return _loglik_rows(_marginal_rows_host(model, Y, logT, X, rows, _lib.marginal_nodes(nodes)), with_S)
+    S < 2 marks a posterior too narrow for the rule.  obs (N, J), 0/1: the observed mask of incomplete patterns (the twin of the MASKED instantiations)."""
+    return _loglik_rows(_marginal_rows_host(model, Y, logT, X, rows, _lib.marginal_nodes(nodes), obs=obs), with_S)
 
 
 def waicFromLogLik(L, unit=MARGINAL_UNIT, **extra) -> OutputWaic:
@@ -348,15 +384,16 @@ def _row_moments(e, z, law, sums, rt):
     return E, V, c0, c1, u, M, s
 
 
-def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal") -> OutputScores:
+def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal", obs=None) -> OutputScores:
     """scoreRespondents with numpy (the test twin of score_kernel), written beside marginalLogLikHost: the rule's weights at every row, the moments of theta, the
-    zeta conditional, and the rows joined in two passes (the means, then the deviations from them)."""
+    zeta conditional, and the rows joined in two passes (the means, then the deviations from them).  obs (N, J), 0/1: the observed mask of incomplete patterns; the
+    result then carries nObs (N,)."""
     if model not in _lib.MARGINAL_MODELS:
         raise ValueError("scoresHost serves the five models without quantile weights")
     Q, wt = _lib.marginal_nodes(nodes), _lib.score_weighting(weighting)
     rt = _lib.MODEL_TRAITS[model].rt
     E, V, Ez, Vz, Cz, l, S = ([] for _ in range(7))
-    for e, z, law, sums in _marginal_rows_host(model, Y, logT, X, rows, Q):
+    for e, z, law, sums in _marginal_rows_host(model, Y, logT, X, rows, Q, obs=obs):
         Es, Vs, c0, c1, u, M, s = _row_moments(e, z, law, sums, rt)
         for lst, val in zip((E, V, Ez, Vz, Cz, l, S), (Es, Vs, c0 + c1 * Es, u + c1 * c1 * Vs, c1 * Vs, M[:, 0] + np.log(s), s)):
             lst.append(val)
@@ -367,10 +404,13 @@ def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="eq
     th, ze = mean(E), mean(Ez)
     nan = np.full(E.shape[1], np.nan)
     coarse = np.any(S < 2.0, axis=0)
-    return OutputScores(theta=th, thetaSd=np.sqrt(np.maximum(mean(V) + mean((E - th) ** 2), 0.0)), zeta=ze if rt else nan,
-                        zetaSd=np.sqrt(np.maximum(mean(Vz) + mean((Ez - ze) ** 2), 0.0)) if rt else nan, cov=mean(Cz) + mean((E - th) * (Ez - ze)) if rt else nan,
-                        rowEss=W * W / np.sum(om * om, axis=0), coarse=coarse, nRows=E.shape[0], nNodes=Q, nCoarse=int(np.sum(coarse)),
-                        weighting="likelihood" if wt else "equal")
+    out = OutputScores(theta=th, thetaSd=np.sqrt(np.maximum(mean(V) + mean((E - th) ** 2), 0.0)), zeta=ze if rt else nan,
+                       zetaSd=np.sqrt(np.maximum(mean(Vz) + mean((Ez - ze) ** 2), 0.0)) if rt else nan, cov=mean(Cz) + mean((E - th) * (Ez - ze)) if rt else nan,
+                       rowEss=W * W / np.sum(om * om, axis=0), coarse=coarse, nRows=E.shape[0], nNodes=Q, nCoarse=int(np.sum(coarse)),
+                       weighting="likelihood" if wt else "equal")
+    if obs is not None:
+        out.nObs = _obs_mask(obs, np.shape(Y)).sum(axis=1).astype(np.int32)
+    return out
 
 
 def pvRow(k, K, n_rows):
@@ -392,10 +432,11 @@ def pvFinish(E, V, mu, sd, c0, c1, u, q, h, w0, w1, w2):
     return theta, (c0 + c1 * theta) + np.sqrt(u) * _ppc_normal(w1, w2)
 
 
-def plausibleValuesHost(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES, i_base=0, with_gap=False, with_rows=False):
+def plausibleValuesHost(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES, i_base=0, with_gap=False, with_rows=False, obs=None):
     """drawPlausibleValues with numpy (the test twin of pv_kernel), written beside scoresHost on _marginal_rows_host and _philox4x32_10.  i_base: the data-set index
     of Y's first subject.  with_gap=True also returns, per draw, the difference of the two largest keys (N, K): a draw whose gap is below the rounding of e_q is
-    undecidable between two implementations.  with_rows=True also returns the rows r_k (K,) and the row moments E, V (N, K) each draw was made from."""
+    undecidable between two implementations.  with_rows=True also returns the rows r_k (K,) and the row moments E, V (N, K) each draw was made from.
+    obs (N, J), 0/1: the observed mask of incomplete patterns; the result then carries nObs (N,)."""
     if model not in _lib.MARGINAL_MODELS:
         raise ValueError("plausibleValuesHost serves the five models without quantile weights")
     Q, K, seed = _lib.marginal_nodes(nodes), _lib.pv_draws(K), _lib.pv_seed(seed)
@@ -410,7 +451,7 @@ def plausibleValuesHost(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_S
     theta, zeta, node, gap = np.empty((N, K)), np.full((N, K), np.nan), np.empty((N, K), dtype=np.int32), np.empty((N, K))
     Ek, Vk = np.empty((N, K)), np.empty((N, K))
     coarse = np.zeros(N, dtype=bool)
-    for r, (e, z, law, sums) in zip(used, _marginal_rows_host(model, Y, logT, X, rows[used], Q)):
+    for r, (e, z, law, sums) in zip(used, _marginal_rows_host(model, Y, logT, X, rows[used], Q, obs=obs)):
         (mu, sd), (E, V, c0, c1, u, _, s) = law[:2], _row_moments(e, z, law, sums, rt)
         coarse |= s < 2.0
         ks = np.nonzero(rk == r)[0]
@@ -420,12 +461,14 @@ def plausibleValuesHost(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_S
         top = np.sort(key, axis=2)
         f0, f1, f2, _ = _philox4x32_10(ii[:, None], ks[None, :], 0xFFFFFFFF, site, seed, seed >> 32)                        # (N, draws)
         col = lambda a: a[:, None] if np.ndim(a) else a
-        th, ze = pvFinish(col(E), col(V), col(mu), sd, col(c0), col(c1), u, q, h, f0, f1, f2)
+        th, ze = pvFinish(col(E), col(V), col(mu), sd, col(c0), col(c1), col(u), q, h, f0, f1, f2)
         theta[:, ks], node[:, ks], gap[:, ks] = th, q, top[:, :, -1] - top[:, :, -2]
         Ek[:, ks], Vk[:, ks] = col(E), col(V)
         if rt:
             zeta[:, ks] = ze
     out = OutputPv(theta=theta, zeta=zeta, node=node, coarse=coarse, nRows=rows.shape[0], nNodes=Q, nCoarse=int(np.sum(coarse)), seed=seed)
+    if obs is not None:
+        out.nObs = _obs_mask(obs, np.shape(Y)).sum(axis=1).astype(np.int32)
     extra = ((gap,) if with_gap else ()) + ((rk, Ek, Vk),) * bool(with_rows)
     return (out, *extra) if extra else out
 

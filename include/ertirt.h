@@ -378,6 +378,44 @@ int erm_get_plausible_values(erm_handle h, int32_t n_nodes, int32_t n_draws, uin
 int erm_plausible_values(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                          int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4);
 
+/* Incomplete response patterns: respondents who did not see every item (booklet designs, adaptive forms, not-reached items, time limits) scored against a saved
+ * posterior -- the three caller-data entries above with an OBSERVED MASK.  Calibration keeps its complete-data contract (erm_set_data takes no mask); scoring,
+ * plausible values and the held-out marginal log-likelihood take incomplete respondents.
+ * The mask is obs, uint8 [n_subj][n_item], column-major as Y is.  1: the cell was administered, so both its response and its log-time are observed; 0: it was not.
+ * O_i = the observed items of subject i in rising item order, n_i = |O_i|.  ONE mask bit per cell: separate response and time masks (an omitted response with a
+ * recorded time) are out of scope.
+ * Definition.  Everything in the definitions of erm_get_marginal_waic, erm_get_scores and erm_get_plausible_values holds, with three changes:
+ *   - "sum over j = 1..J" is read as "sum over j in O_i, in rising order";
+ *   - T(theta) takes n_i for J in -(n_i / 2) log 2 pi;
+ *   - each of these sums runs over O_i only: A1 = sum y_j a_j, A0 = sum y_j a_j b_j, sum_j log(1 + e^eta_j), and P, R0, R1, D0, D1, D2, L = sum log sig2t_j.
+ *   The population law, the node rule, COARSE, the row weights, the row accumulator, the Gumbel-max node choice and its Philox counters (the subject index i within
+ *   the call) are unchanged.
+ * Consequences:
+ *   - n_i = 0 is an ordinary case: every sum is empty and T = 0.  The score is the population law averaged over the rows; zeta | theta ~ N(m0 + m1 theta, v), because
+ *     P = 0; l is the log of the rule's total weight.
+ *   - Y and logT at unobserved cells are never read: they may be NaN, 255 or anything else; the validation skips them and no result changes by a bit.
+ *   - obs == NULL means complete, and the result is the unmasked entry's bit for bit (the unmasked entry is called); n_obs receives n_item.
+ *   - with obs all ones the result is also the unmasked entry's bit for bit: lane s of a subject adds the list positions s, s + 8, ... in order, every node's chain
+ *     runs over the list in order, and the butterflies are those of the complete kernel.
+ *   - a subject with pattern O gives the result of that subject in a data set that has only the items O, scored through the unmasked entry on the rows restricted to
+ *     the columns of those items (a, b, lambda, sig2t, and Cross's rho, subset in the same order): the order of every floating-point operation is the same.
+ * Work, memory and traffic are proportional to the observed cells: the host compacts every subject's cells into a list (item index, y, logT) while it validates them,
+ * and the kernels' item sums and node chains run over the list.
+ * n_obs, int32 [n_subj], receives n_i; it may be NULL.  All other outputs, n_nodes, n_draws, weighting and the row limits are the unmasked entries'.  Served: the five
+ * models of erm_get_marginal_waic; the quantile models are refused with its messages (erm_quantile_marginal_loglik has no masked sibling).
+ * Validation: erm_marginal_loglik's, with these differences -- an obs value above 1: ERM_ERR_ARG; a NaN in logT: ERM_ERR_NONFINITE, and Y > 1: ERM_ERR_ARG, at
+ *   observed cells only.  X and the rows are validated as there.
+ * PSIS-LOO of incomplete respondents needs nothing new: erm_psis_loo takes the l erm_marginal_loglik_masked returns.
+ * The engine and farm entries (erm_get_scores and the others) take no mask: a resident data set is complete by construction. */
+int erm_marginal_loglik_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
+                               const uint8_t* obs, const double* rows, int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u,
+                               int32_t* n_obs);
+int erm_score_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                     const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4, int32_t* n_obs);
+int erm_plausible_values_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
+                                const uint8_t* obs, const double* rows, int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node,
+                                int32_t* coarse, double* out4, int32_t* n_obs);
+
 /* Marginal PSIS-LOO: Pareto-smoothed importance-sampling leave-one-subject-out (Vehtari, Gelman and Gabry 2017; Vehtari, Simpson, Gelman, Yao and Gabry 2024), the
  * criterion the "p_u > 0.4" count of erm_get_waic / erm_get_marginal_waic sends its reader to, and with it a Pareto k^ per respondent: for which respondents the
  * posterior would move if they were left out -- the aberrant or highly influential response / time patterns.  (ERM_SCORE_LIKELIHOOD importance-weights the rows with raw
