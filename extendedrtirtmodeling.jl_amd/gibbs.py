@@ -558,6 +558,9 @@ def getWaicMarginal(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES, pointwise=False
     """Marginal WAIC of the last sample! -- of one engine or of the chain farm of sample!(...; devices=), whose chains' post-burn-in rows enter as one table --
     computed on the device from the resident item trace and data set (erm_get_marginal_waic / erm_farm_get_marginal_waic); needs no waic= at sample!.
     unit = "subject-marginal"; nNodes = nodes, nCoarse = the subjects for which the rule was too coarse at some row (raise nodes if it is not 0).
+    nodes: odd, 3 .. 1025.  The default of 61 suits forms of some tens of items; a form of several hundred items narrows every posterior below the spacing, and
+    61 nodes then flag every respondent (at 586, 683 and 896 items of the test data all 40 of 40, S between 1 and 2).  Raise nodes until nCoarse is 0: 255 clears
+    it at 896 items on that data (tests/test_item_pass_limits_host.py).
     pointwise=True also fetches lppd_i and p_i, which compareWaic needs."""
     return _waic_output(_marginal_pass(MCMC, "gaussian", "waic", "getWaicMarginal", nodes, pointwise), pointwise)
 
@@ -660,7 +663,8 @@ def getScores(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES) -> OutputScores:
     """Scores of the subjects of the last sample! -- of one engine or of the chain farm of sample!(...; devices=) -- computed on the device from the resident item
     trace and data set (erm_get_scores / erm_farm_get_scores), in either trace mode: theta, thetaSd, zeta, zetaSd, cov, rowEss, coarse per subject; relTheta,
     relZeta.  The scores are posterior under the population law of getWaicMarginal: for the response-time models theta borrows strength from the response times, so
-    they differ from Post.mean by design (the sampler's theta and zeta draws each use the marginal prior); for GibbsMlIrt the two agree."""
+    they differ from Post.mean by design (the sampler's theta and zeta draws each use the marginal prior); for GibbsMlIrt the two agree.
+    nodes: as getWaicMarginal's -- the default of 61 flags every respondent of a form of several hundred items; raise it until nCoarse is 0 (255 at 896 items)."""
     Q = _marginal_check(MCMC, nodes, "getScores")
     return _scores_output(_marginal_source(MCMC, "getScores").scores(Q))
 
@@ -700,7 +704,9 @@ def getPlausibleValues(MCMC: _GibbsBase, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nod
 def drawPlausibleValues(model, Y, logT, X, rows, K=_lib.PV_DRAWS, seed=_lib.PV_SEED, nodes=_lib.MARGINAL_NODES, device=0, obs=None) -> OutputPv:
     """Plausible values of respondents -- new ones, or those of a run that is no longer resident -- against saved item-trace rows [R, item_trace_width]
     (Engine.item_trace()), on the device (erm_plausible_values).  model: the model code (_lib.MODEL_*); Y, logT [N, J], X [N, F] or None; every row counts once.
-    obs [N, J], 0/1: respondents who did not see every item (erm_plausible_values_masked), as scoreRespondents takes it; the result carries nObs."""
+    obs [N, J], 0/1: respondents who did not see every item (erm_plausible_values_masked), as scoreRespondents takes it; the result carries nObs.
+    nodes: as getWaicMarginal's -- the default of 61 flags every respondent of a form of several hundred items (the draws then sit on one or two nodes); raise it
+    until nCoarse is 0 (255 at 896 items)."""
     if model not in _lib.MARGINAL_MODELS:
         raise ValueError("drawPlausibleValues serves the five models without quantile weights")
     Q, K, seed = _lib.marginal_nodes(nodes), _lib.pv_draws(K), _lib.pv_seed(seed)
