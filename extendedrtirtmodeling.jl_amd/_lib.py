@@ -73,6 +73,7 @@ EXPORTS = [
     "erm_get_quantile_marginal_waic", "erm_farm_get_quantile_marginal_waic", "erm_get_quantile_marginal_loo", "erm_farm_get_quantile_marginal_loo",
     "erm_quantile_marginal_loglik",
     "erm_marginal_loglik_masked", "erm_score_masked", "erm_plausible_values_masked",
+    "erm_get_person_fit", "erm_farm_get_person_fit", "erm_person_fit", "erm_person_fit_masked",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -204,7 +205,7 @@ def load():
     I32, VP = C.c_int32, C.c_void_p
     stems = [fam.stem for fam in MARGINAL_FAMILIES.values()]
     pairs = [("diagnostics", [C.c_int, VP, VP]), ("convergence", [C.c_int, VP]), ("rank_diagnostics", [C.c_int, VP, VP, VP]), ("rank_convergence", [C.c_int, VP]),
-             ("scores", [I32, VP, VP]), ("plausible_values", [I32, I32, C.c_uint64, VP, VP, VP, VP])]
+             ("scores", [I32, VP, VP]), ("person_fit", [I32, VP, VP]), ("plausible_values", [I32, I32, C.c_uint64, VP, VP, VP, VP])]
     pairs += [(stem + "waic", [I32, VP, VP, VP]) for stem in stems] + [(stem + "loo", [I32, VP, VP]) for stem in stems]
     for prefix in ("erm_get_", "erm_farm_get_"):          # every pair that _Diagnostics and _ItemPasses resolve through _get_prefix
         for name, args in pairs:
@@ -219,6 +220,8 @@ def load():
     lib.erm_marginal_loglik_masked.argtypes = mhead + [I32, VP, VP, VP, VP, VP]
     lib.erm_score_masked.argtypes = mhead + [I32, I32, VP, VP, VP]
     lib.erm_plausible_values_masked.argtypes = mhead + [I32, I32, C.c_uint64, VP, VP, VP, VP, VP]
+    lib.erm_person_fit.argtypes = head + [I32, I32, VP, VP]
+    lib.erm_person_fit_masked.argtypes = mhead + [I32, I32, VP, VP, VP]
     _lib = lib
     return lib
 
@@ -299,6 +302,24 @@ def _score_call(fn, h, nodes, n_subj):
     score, out = np.empty((len(SCORE_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
     check(fn(h, marginal_nodes(nodes), score.ctypes.data, out.ctypes.data))
     return _score_result(score, out)
+
+
+# erm_get_person_fit / erm_farm_get_person_fit / erm_person_fit: the columns of fit [n_subj][6] (ERM_FIT_*); the weightings are the scores'
+FIT_COLUMNS = ("lz", "pResp", "ltz", "pTime", "rowEss", "coarse")
+
+
+def _fit_result(fit, out):
+    """fit as the library fills it, (6, n_subj) C-ordered = column-major [n_subj][6], and out4 -> a dict of the columns with nSubj, nRows, nNodes, nCoarse."""
+    res = {name: fit[k] for k, name in enumerate(FIT_COLUMNS)}
+    res["coarse"] = fit[5] != 0.0
+    res.update(nSubj=int(out[0]), nRows=int(out[1]), nNodes=int(out[2]), nCoarse=int(out[3]))
+    return res
+
+
+def _fit_call(fn, h, nodes, n_subj):
+    fit, out = np.empty((len(FIT_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
+    check(fn(h, marginal_nodes(nodes), fit.ctypes.data, out.ctypes.data))
+    return _fit_result(fit, out)
 
 
 # erm_get_plausible_values / erm_farm_get_plausible_values / erm_plausible_values: the number of draws, the seed, and the outputs
@@ -415,7 +436,7 @@ class _Diagnostics:
 
 
 class _ItemPasses:
-    """The four passes over the item trace of an Engine (erm_get_*: its resident data set and its own post-burn-in rows) and of a Farm (erm_farm_get_*: the
+    """The five passes over the item trace of an Engine (erm_get_*: its resident data set and its own post-burn-in rows) and of a Farm (erm_farm_get_*: the
     post-burn-in rows of all chains -- chain 0's, then chain 1's, ... -- on chain 0's device and data set).  One implementation, keyed by `_get_prefix`."""
 
     def _pass(self, name: str):
@@ -449,6 +470,12 @@ class _ItemPasses:
         """erm_get_scores / erm_farm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on
         the device from the resident item trace after the run (equal weights).  A dict of SCORE_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
         return _score_call(self._pass("scores"), self._h, nodes, self.cfg.n_subj)
+
+    def person_fit(self, nodes=MARGINAL_NODES):
+        """erm_get_person_fit / erm_farm_get_person_fit: every subject's lz with its normal p-value, the Wilson-Hilferty z of the response-time quadratic form with
+        its exact chi^2 p-value, and the rows' effective size, computed on the device from the resident item trace after the run (equal weights).  A dict of
+        FIT_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
+        return _fit_call(self._pass("person_fit"), self._h, nodes, self.cfg.n_subj)
 
     def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
         """erm_get_plausible_values / erm_farm_get_plausible_values: K draws of every subject's (theta, zeta) from its posterior given the resident item trace,
@@ -875,6 +902,22 @@ def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", d
     check(load().erm_score_masked(*_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes), score_weighting(weighting), sc.ctypes.data, out.ctypes.data,
                                   n_obs.ctypes.data))
     return dict(_score_result(sc, out), nObs=n_obs)
+
+
+def person_fit(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", device=0, obs=None):
+    """erm_person_fit: the person fit's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
+    Engine.item_trace() returns them, R >= 1; weighting "equal" | "likelihood".  Returns Engine.person_fit's dict.  obs [N, J], 0/1 (None: complete,
+    erm_person_fit): erm_person_fit_masked on incomplete patterns; the dict then has nObs [N]."""
+    arrays, dims = _caller_data(model, Y, logT, X, rows)
+    N = dims[0]
+    ft, out = np.empty((len(FIT_COLUMNS), N), dtype=np.float64), np.empty(4, dtype=np.float64)
+    if obs is None:
+        check(load().erm_person_fit(*_caller_head(device, model, arrays, dims), marginal_nodes(nodes), score_weighting(weighting), ft.ctypes.data, out.ctypes.data))
+        return _fit_result(ft, out)
+    O, n_obs = _caller_obs(obs, N, dims[1])
+    check(load().erm_person_fit_masked(*_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes), score_weighting(weighting), ft.ctypes.data,
+                                       out.ctypes.data, n_obs.ctypes.data))
+    return dict(_fit_result(ft, out), nObs=n_obs)
 
 
 def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES, device=0, obs=None):

@@ -173,6 +173,28 @@ class OutputScores:
                 f"relTheta={self.relTheta:.4f}, relZeta={self.relZeta:.4f})")
 
 
+class OutputPersonFit:
+    """Person fit of the respondents (getPersonFit / personFit; the reference has no counterpart): per subject lz (Drasgow, Levine and Williams' standardised
+    log-likelihood of the responses, averaged over the posterior of theta; negative: misfit) with pResp, its posterior predictive p-value under lz's normal
+    approximation; ltz (the Wilson-Hilferty z of the response-time quadratic form; positive: misfit) with pTime, its exact chi^2 posterior predictive p-value
+    (both NaN for GibbsMlIrt); small p-values mean misfit.  rowEss, coarse, nRows, nNodes, nCoarse as OutputScores'; nObs: the observed cells per subject (None
+    without a mask).  A subject without an observed cell has NaN in the four statistics."""
+
+    def __init__(self, lz=None, pResp=None, ltz=None, pTime=None, rowEss=None, coarse=None, nRows=None, nNodes=None, nCoarse=None, weighting="equal", nObs=None):
+        self.lz, self.pResp, self.ltz, self.pTime, self.rowEss, self.coarse = lz, pResp, ltz, pTime, rowEss, coarse
+        self.nRows, self.nNodes, self.nCoarse, self.weighting, self.nObs = nRows, nNodes, nCoarse, weighting, nObs
+
+    def flagged(self, alpha=0.05):
+        """(responses, times): boolean (N,) -- the p-value is below alpha (NaN is not flagged)."""
+        below = lambda p: np.zeros(0, dtype=bool) if p is None else np.nan_to_num(np.asarray(p, dtype=np.float64), nan=1.0) < alpha
+        return below(self.pResp), below(self.pTime)
+
+    def __repr__(self):
+        fr, ft = self.flagged()
+        return (f"OutputPersonFit(nSubj={None if self.lz is None else np.size(self.lz)}, nRows={self.nRows}, nNodes={self.nNodes}, nCoarse={self.nCoarse}, "
+                f"flaggedResp={int(np.sum(fr))}, flaggedTime={int(np.sum(ft))})")
+
+
 class OutputPv:
     """Plausible values of the respondents (getPlausibleValues / drawPlausibleValues; the reference has no counterpart): theta (N, K) and zeta (N, K), K draws per
     subject from its posterior given the item trace (zeta is NaN for GibbsMlIrt); node (N, K), the rule's node behind every draw; coarse (N,), the theta rule was too

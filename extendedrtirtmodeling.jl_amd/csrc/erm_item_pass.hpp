@@ -3,6 +3,8 @@
 // is its own argument checks, ONE source maker (item_source) and ONE product call (item_waic / item_loo / item_scores / item_pv).  The five entries of LatentQr's
 // marginal WAIC and LOO (erm_get_quantile_marginal_* and erm_quantile_marginal_loglik) are the same makers and products for FAMILY_QUANTILE, and the
 // three masked entries (erm_marginal_loglik_masked / erm_score_masked / erm_plausible_values_masked) the caller-data maker with an observed mask.
+// The person fit is a fifth pass on the same makers with a product of its own, item_fit: erm_get_person_fit, erm_farm_get_person_fit,
+// erm_person_fit and erm_person_fit_masked.
 //
 // The first half is plain C++: the facts of a pass as one table, the refusals built from it and the chunk rule; g++ compiles this half with
 // -fsanitize=undefined -ftrapv into tests/item_pass_check (tests/test_item_pass_host.py).
@@ -29,15 +31,19 @@ constexpr ItemPassFacts ITEM_PASSES[N_ITEM_PASSES] = {
     { "the scores",           true,  1, 1, "at least one post-burn-in row" },
     { "the plausible values", true,  1, 1, "at least one post-burn-in row" },
 };
+// the fifth pass, the person fit, has its facts beside the table; every reader of a pass's facts goes through item_pass_facts
+constexpr int PASS_FIT = N_ITEM_PASSES;
+constexpr ItemPassFacts FIT_PASS_FACTS = { "the person fit", false, 1, 1, "at least one post-burn-in row" };
+constexpr const ItemPassFacts& item_pass_facts(int pass) { return pass == PASS_FIT ? FIT_PASS_FACTS : ITEM_PASSES[pass]; }
 inline std::string item_pass_on_shard(int pass)
 {
-    const ItemPassFacts& p = ITEM_PASSES[pass];
+    const ItemPassFacts& p = item_pass_facts(pass);
     return std::string(p.noun) + (p.plural ? " are" : " is") + " not available on a shard (every subject's data must be resident on one device)";
 }
 // too few rows: an engine's own (engine_rows > 0) and a farm chain's ("chain l: " in front)
 inline std::string item_pass_needs_rows(int pass)
 {
-    const ItemPassFacts& p = ITEM_PASSES[pass];
+    const ItemPassFacts& p = item_pass_facts(pass);
     return std::string(p.noun) + (p.plural ? " need " : " needs ") + p.need;
 }
 
@@ -249,7 +255,7 @@ static int item_source(erm_farm_handle f, int pass, ItemSource& S, int family = 
     for (int l = 0; l < L; ++l) {
         const EngineBase* e = f->eng[l]->e.get();
         if (e->rows_done != rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + std::to_string(e->rows_done) + " rows recorded where chain 0 has " + std::to_string(rows));
-        if (e->post_rows < ITEM_PASSES[pass].farm_rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + item_pass_needs_rows(pass));
+        if (e->post_rows < item_pass_facts(pass).farm_rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + item_pass_needs_rows(pass));
     }
     std::vector<double> table((size_t)L * post * wi);
     for (int l = 0; l < L; ++l) {
@@ -423,6 +429,28 @@ static int item_scores(const ItemSource& S, int Q, int weighting, double* score,
     unsigned long long nc = 0;
     if (int rc = coarse.count(S.stream, &nc)) return rc;
     HIPCHK(hipMemcpy(score, dScore.p, (size_t)N * SCORE_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
+    return 0;
+}
+// Person fit (erm_fit_kernels.hpp; include/ertirt.h: erm_get_person_fit, erm_person_fit): the one place that launches fit_kernel; fit [N][6]
+static int item_fit(const ItemSource& S, int Q, int weighting, double* fit, double* out4)
+{
+    const int64_t N = S.D.N;
+    DevBuf dFit;
+    CoarseFlags coarse;
+    const char* what = "the person fit";
+    if (int rc = dFit.try_alloc((size_t)N * FIT_COLS * sizeof(double), what)) return rc;
+    if (int rc = coarse.alloc(N, what)) return rc;
+    MargArgs a = marg_args(S.D, S.rows, S.n_rows, Q);
+    a.coarse = coarse.flags();
+    auto launch = [&](auto M, auto real, auto masked) -> int {
+        if (weighting == SCORE_LIKELIHOOD) return marg_tile_launch(&fit_kernel<decltype(M)::value, decltype(real), true, decltype(masked)::value>, a, S.stream, dFit.as<double>());
+        return marg_tile_launch(&fit_kernel<decltype(M)::value, decltype(real), false, decltype(masked)::value>, a, S.stream, dFit.as<double>());
+    };
+    if (int rc = marg_dispatch_obs(S.D, launch)) return rc;
+    unsigned long long nc = 0;
+    if (int rc = coarse.count(S.stream, &nc)) return rc;
+    HIPCHK(hipMemcpy(fit, dFit.p, (size_t)N * FIT_COLS * sizeof(double), hipMemcpyDeviceToHost));
     if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
     return 0;
 }

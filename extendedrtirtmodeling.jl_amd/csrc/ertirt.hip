@@ -23,6 +23,7 @@
 #include "erm_marginal_kernels.hpp"        // marginal WAIC: theta and zeta integrated out, from the item trace
 #include "erm_psis_kernels.hpp"            // marginal PSIS-LOO: Pareto-smoothed leave-one-subject-out from marginal_kernel's l
 #include "erm_score_kernels.hpp"           // scores of respondents: posterior moments of theta and zeta, from the item trace
+#include "erm_fit_kernels.hpp"             // person fit: lz and the response-time chi^2 of every respondent, from the item trace
 #include "erm_pv_kernels.hpp"              // plausible values: draws of theta and zeta from each subject's posterior, from the item trace
 #include "erm_farm_diag.hpp"               // the chain farm's joint diagnostics: chunk arithmetic
 #include "erm_geometry.hpp"
@@ -1729,7 +1730,7 @@ template <typename real> int Engine<real>::item_source(int pass, ItemSource& S)
     if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
     if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
     if (!S.rows) {
-        if (post_rows < ITEM_PASSES[pass].engine_rows) return fail(ERM_ERR_STATE, item_pass_needs_rows(pass));
+        if (post_rows < item_pass_facts(pass).engine_rows) return fail(ERM_ERR_STATE, item_pass_needs_rows(pass));
         S.rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); S.n_rows = post_rows;
     }
     HIPCHK(hipSetDevice(cfg.device));
@@ -1773,6 +1774,14 @@ template <typename H> static int get_scores(H h, int32_t n_nodes, double* score,
     if (int rc = item_entry_args(score, n_nodes, &Q)) return rc;
     if (int rc = item_source(h, PASS_SCORES, S)) return rc;
     return item_scores(S, Q, SCORE_EQUAL, score, out4);
+}
+template <typename H> static int get_person_fit(H h, int32_t n_nodes, double* fit, double* out4)
+{
+    int Q = 0;
+    ItemSource S;
+    if (int rc = item_entry_args(fit, n_nodes, &Q)) return rc;
+    if (int rc = item_source(h, PASS_FIT, S)) return rc;
+    return item_fit(S, Q, SCORE_EQUAL, fit, out4);
 }
 template <typename H> static int get_plausible_values(H h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
@@ -1831,6 +1840,7 @@ int erm_get_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* p
 int erm_get_quantile_marginal_waic(erm_handle h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_H; return get_marginal_waic(h, n_nodes, out10, lppd_u, p_u, FAMILY_QUANTILE); }
 int erm_get_quantile_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw) { CHK_H; return get_marginal_loo(h, n_nodes, out12, pw, FAMILY_QUANTILE); }
 int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4) { CHK_H; return get_scores(h, n_nodes, score, out4); }
+int erm_get_person_fit(erm_handle h, int32_t n_nodes, double* fit, double* out4) { CHK_H; return get_person_fit(h, n_nodes, fit, out4); }
 int erm_get_plausible_values(erm_handle h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
     CHK_H;
@@ -2051,6 +2061,7 @@ int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12,
 int erm_farm_get_quantile_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u) { CHK_F; return get_marginal_waic(f, n_nodes, out10, lppd_u, p_u, FAMILY_QUANTILE); }
 int erm_farm_get_quantile_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw) { CHK_F; return get_marginal_loo(f, n_nodes, out12, pw, FAMILY_QUANTILE); }
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4) { CHK_F; return get_scores(f, n_nodes, score, out4); }
+int erm_farm_get_person_fit(erm_farm_handle f, int32_t n_nodes, double* fit, double* out4) { CHK_F; return get_person_fit(f, n_nodes, fit, out4); }
 int erm_farm_get_plausible_values(erm_farm_handle f, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
     CHK_F;
@@ -2197,6 +2208,39 @@ int erm_plausible_values_masked(int device, int model, int64_t n_subj, int32_t n
     if (int rc = item_source("erm_plausible_values_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S,
                              FAMILY_GAUSSIAN, 0.0, obs, n_obs)) return rc;
     return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
+}
+
+// ---- person fit on caller-supplied data and rows, complete or with an observed mask
+int erm_person_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                   int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4)
+{
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
+    if (!fit) return fail(ERM_ERR_ARG, "out is NULL");
+    ItemSource S;
+    if (int rc = item_source("erm_person_fit's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S)) return rc;
+    return item_fit(S, Q, weighting, fit, out4);
+}
+
+int erm_person_fit_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                          const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4, int32_t* n_obs)
+{
+    if (!obs) {
+        if (int rc = erm_person_fit(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, weighting, fit, out4)) return rc;
+        obs_all(n_subj, n_item, n_obs);
+        return 0;
+    }
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
+    if (!fit) return fail(ERM_ERR_ARG, "out is NULL");
+    ItemSource S;
+    if (int rc = item_source("erm_person_fit_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN,
+                             0.0, obs, n_obs)) return rc;
+    return item_fit(S, Q, weighting, fit, out4);
 }
 
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out)

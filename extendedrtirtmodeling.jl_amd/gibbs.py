@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import InputPara, OutputDic, OutputLoo, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions
+from .base import InputPara, OutputDic, OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions
 
 _PREC = {"f32": _lib.PREC_F32, "f64": _lib.PREC_F64}
 _TRACE = {"summary": _lib.TRACE_SUMMARY, "full": _lib.TRACE_FULL}
@@ -680,6 +680,36 @@ def scoreRespondents(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighti
     w = _lib.score_weighting(weighting)
     Y, logT = _masked_data(Y, logT, obs)
     return _scores_output(_lib.score(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), weighting=w, device=device, obs=obs), "likelihood" if w else "equal")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Person fit (include/ertirt.h: erm_get_person_fit).  A fit flag beside every score: lz of the responses and the chi^2 of the response times, each
+# averaged over the posterior of theta on the marginal WAIC's rule at every row, with posterior predictive p-values.  Deterministic.
+# ------------------------------------------------------------------------------------------------------------------
+def _fit_output(r, weighting="equal") -> OutputPersonFit:
+    return OutputPersonFit(lz=r["lz"], pResp=r["pResp"], ltz=r["ltz"], pTime=r["pTime"], rowEss=r["rowEss"], coarse=r["coarse"], nRows=r["nRows"],
+                           nNodes=r["nNodes"], nCoarse=r["nCoarse"], weighting=weighting, nObs=r.get("nObs"))
+
+
+def getPersonFit(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES) -> OutputPersonFit:
+    """Person fit of the subjects of the last sample! -- of one engine or of the chain farm of sample!(...; devices=) -- computed on the device from the resident
+    item trace and data set (erm_get_person_fit / erm_farm_get_person_fit), in either trace mode: lz, pResp, ltz, pTime, rowEss, coarse per subject.  Small pResp:
+    the responses are improbable for that person (guessing, pre-knowledge, copying); small pTime: the response times are.  Under the population law of getScores.
+    nodes: as getWaicMarginal's."""
+    Q = _marginal_check(MCMC, nodes, "getPersonFit")
+    return _fit_output(_marginal_source(MCMC, "getPersonFit").person_fit(Q))
+
+
+def personFit(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal", device=0, obs=None) -> OutputPersonFit:
+    """Person fit of respondents -- new ones, or those of a run that is no longer resident -- against saved item-trace rows [R, item_trace_width]
+    (Engine.item_trace()), on the device (erm_person_fit); the arguments are scoreRespondents'.  obs [N, J], 0/1: respondents who did not see every item
+    (erm_person_fit_masked) -- every sum runs over the observed cells and the chi^2 has n_i degrees of freedom; a respondent with none gets NaN; the result
+    carries nObs."""
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("personFit serves the five models without quantile weights")
+    w = _lib.score_weighting(weighting)
+    Y, logT = _masked_data(Y, logT, obs)
+    return _fit_output(_lib.person_fit(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), weighting=w, device=device, obs=obs), "likelihood" if w else "equal")
 
 
 # ------------------------------------------------------------------------------------------------------------------

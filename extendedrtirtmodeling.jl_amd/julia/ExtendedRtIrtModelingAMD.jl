@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getWaicMarginalQr, getLooMarginalQr, quantileMarginalLogLik, getScores, scoreRespondents, getPlausibleValues, drawPlausibleValues, observedMask, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getWaicMarginalQr, getLooMarginalQr, quantileMarginalLogLik, getScores, scoreRespondents, getPersonFit, personFit, getPlausibleValues, drawPlausibleValues, observedMask, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -571,6 +571,59 @@ function scoreRespondents(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64
                  Ptr{Int32}),
                 device, model, N, J, size(X, 2), Y, logT, X, obs, rows, size(rows, 2), nodes, w, score, out, nObs))
     return merge(scoresTuple(score, out), (nObs = nObs,))
+end
+
+# fit as erm_get_person_fit fills it (column-major [nSubj][6], the ERM_FIT_* columns) and out4 -> a named tuple
+fitTuple(fit::Matrix{Float64}, out::Vector{Float64}, nObs = nothing) =
+    (lz = fit[:, 1], pResp = fit[:, 2], ltz = fit[:, 3], pTime = fit[:, 4], rowEss = fit[:, 5], coarse = fit[:, 6] .!= 0.0,
+     nRows = Int(out[2]), nNodes = Int(out[3]), nCoarse = Int(out[4]), nObs = nObs)
+
+"""
+    getPersonFit(MCMC; nodes = 61) -> (lz, pResp, ltz, pTime, rowEss, coarse, nRows, nNodes, nCoarse, nObs)
+
+Person fit of the subjects of the last `sample!`: whether each respondent's responses and response times are probable under the model for that person, computed on
+the device from the resident item-level trace and data set in either trace mode (`erm_get_person_fit`; after `sample!(MCMC; devices=...)` over the rows of all
+chains, `erm_farm_get_person_fit`).  `lz` is the standardised log-likelihood of the responses averaged over the posterior of θ (negative: misfit) and `pResp` its
+posterior predictive p-value under the normal approximation; `ltz` is the Wilson-Hilferty z of the response-time quadratic form (positive: misfit) and `pTime` its
+exact χ² posterior predictive p-value; small p-values mean misfit.  `ltz` and `pTime` are NaN for GibbsMlIrt.  Not for the two quantile models.
+"""
+function getPersonFit(M::GibbsAMD; nodes::Integer = 61)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    fit, out = zeros(M.Cond.nSubj, 6), zeros(4)
+    if farmed
+        check(ccall((:erm_farm_get_person_fit, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.farm, nodes, fit, out))
+    else
+        check(ccall((:erm_get_person_fit, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.handle, nodes, fit, out))
+    end
+    return fitTuple(fit, out)
+end
+
+"""
+    personFit(model, Y, logT, X, rows; nodes = 61, weighting = :equal, device = 0, obs = nothing)
+
+`getPersonFit` for caller-supplied respondents against saved item-trace rows, on the device (`erm_person_fit`); the arguments are `scoreRespondents`'.
+`obs` (UInt8 nSubj x nItem, 1 = the cell was administered): respondents who did not see every item (`erm_person_fit_masked`) -- every sum runs over the observed
+cells and the χ² has n_i degrees of freedom; a respondent without an observed cell has NaN in the four statistics; the result then has `nObs`.
+"""
+function personFit(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}; nodes::Integer = 61,
+                   weighting::Symbol = :equal, device::Integer = 0, obs::Union{Nothing,Matrix{UInt8}} = nothing)
+    N, J = size(Y)
+    w = weighting == :equal ? 0 : weighting == :likelihood ? 1 : error("weighting must be :equal or :likelihood")
+    fit, out = zeros(N, 6), zeros(4)
+    if obs === nothing
+        check(ccall((:erm_person_fit, LIB[]), Cint,
+                    (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                    device, model, N, J, size(X, 2), Y, logT, X, rows, size(rows, 2), nodes, w, fit, out))
+        return fitTuple(fit, out)
+    end
+    size(obs) == (N, J) || error("obs does not match Y")
+    nObs = zeros(Int32, N)
+    check(ccall((:erm_person_fit_masked, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}),
+                device, model, N, J, size(X, 2), Y, logT, X, obs, rows, size(rows, 2), nodes, w, fit, out, nObs))
+    return fitTuple(fit, out, nObs)
 end
 
 # pv as erm_get_plausible_values fills it (column-major [nSubj][K][2]), node [nSubj][K], coarse [nSubj] and out4 -> a named tuple

@@ -7,7 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import OutputLoo, OutputPpc, OutputPv, OutputScores, OutputWaic
+from .base import OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic
 from .gibbs import MARGINAL_UNIT, _GibbsBase, _log1pexp, _marginal_check, _norm_logpdf, marginalRows
 
 
@@ -411,6 +411,110 @@ def scoresHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="eq
     if obs is not None:
         out.nObs = _obs_mask(obs, np.shape(Y)).sum(axis=1).astype(np.int32)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Person fit: personFit's twin beside scoresHost, on _marginal_rows_host's law
+# ------------------------------------------------------------------------------------------------------------------
+def chi2TailHost(Qf, n, dtype=np.float64):
+    """P(chi^2_n >= Qf) by the finite sum of csrc/erm_fit.hpp (fit_chi2_tail), for integer n broadcast against Qf: y = Qf / 2, o = n mod 2, m = n // 2,
+    base = o ? erfc(sqrt y) : 0, t_0 = e^-y (o ? 2 sqrt(y / pi) : 1), t_k = t_(k-1) y / (k + o / 2), tail = base + sum_(k < m) t_k; 0 for y > 700."""
+    from scipy.special import erfc
+    Qf = np.asarray(Qf, dtype=dtype)
+    n = np.broadcast_to(np.asarray(n, dtype=np.int64), Qf.shape)
+    o, m = (n % 2) == 1, n // 2
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        y = Qf / 2
+        rt = np.sqrt(y)
+        tail = np.where(o, erfc(rt.astype(np.float64)).astype(dtype), dtype(0))
+        t = np.exp(-y) * np.where(o, 2 * rt / np.sqrt(np.arccos(dtype(-1))), dtype(1))
+        for k in range(int(m.max()) if m.size else 0):
+            tail = np.where(k < m, tail + t, tail)
+            t = t * (y / (k + 1 + np.where(o, dtype(0.5), dtype(0))))
+        return np.where(y > 700, dtype(0), tail)
+
+
+def wilsonHilfertyHost(Qf, n, dtype=np.float64):
+    """Wilson-Hilferty's z of a chi^2_n value (fit_wh): ((Qf / n)^(1/3) - (1 - 2 / (9 n))) / sqrt(2 / (9 n)); NaN for n = 0."""
+    Qf, n = np.asarray(Qf, dtype=dtype), np.asarray(n, dtype=dtype)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = 2 / (9 * n)
+        return (np.cbrt(Qf / n) - (1 - c)) / np.sqrt(c)
+
+
+def personFitHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equal", obs=None, dtype=np.float64, with_S=False) -> OutputPersonFit:
+    """personFit with numpy (the test twin of fit_kernel), written beside scoresHost: the population law of every row from _marginal_rows_host; then the definition
+    of include/ertirt.h restated -- at every node lz from (W, Vw) in the form without cancellation, the quadratic form Qf of the log-times with its chi^2 tail
+    (chi2TailHost) and its Wilson-Hilferty z, e_q from the same sums; the four means under the rule's weights at the row; the weighted means over the rows.
+    obs (N, J), 0/1: the observed mask -- every sum over the items is a sum over the observed cells and n_i stands for J (restated here: the masked call never
+    reduces the data and calls itself); the result then carries nObs (N,).  dtype=np.longdouble: the same arithmetic in extended precision, for the conditioning
+    of the float64 result (erfc stays float64).  with_S: also S (R, N), the rule's sum at every row."""
+    from scipy.special import erfc
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("personFitHost serves the five models without quantile weights")
+    Q, wt = _lib.marginal_nodes(nodes), _lib.score_weighting(weighting)
+    t = _lib.MODEL_TRAITS[model]
+    f = dtype
+    O = np.ones(np.shape(Y), dtype=bool) if obs is None else _obs_mask(obs, np.shape(Y))
+    Of = O.astype(f)
+    Yz = np.where(O, np.asarray(Y), 0)
+    ltz_in = np.where(O, np.asarray(logT, dtype=np.float64), 0.0) if t.rt else None
+    Yf = Yz.astype(f)
+    N, J = Yf.shape
+    n = O.sum(axis=1)
+    lt = ltz_in.astype(f) if t.rt else None
+    rows2 = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    log2pi = np.log(2 * np.arccos(f(-1)))
+    LZ, PY, LTZ, PT, l, S = ([] for _ in range(6))
+    for (_, z, law, _), row in zip(_marginal_rows_host(model, Yz, ltz_in, X, rows2, Q), rows2):
+        mu, sd, m0, m1, v = law
+        a, b, lam, sg = (row[k * J:(k + 1) * J].astype(f) for k in range(4))
+        rho = row[4 * J:5 * J].astype(f) if t.rho else np.zeros(J, dtype=f)
+        z = z.astype(f)
+        h = f(12) / (Q - 1)
+        th = np.asarray(mu, dtype=f)[:, None] + f(sd) * z[None, :]                           # (N, Q)
+        eta = a[None, None, :] * (th[:, :, None] - b[None, None, :])                          # (N, Q, J)
+        tt = np.exp(-np.abs(eta))
+        lse = np.maximum(eta, 0) + np.log1p(tt)
+        r = np.where((Yz[:, None, :] == 1) == (eta >= 0), tt / (1 + tt), 1 / (1 + tt))
+        Oq = Of[:, None, :]
+        W = np.sum(Oq * (2 * Yf[:, None, :] - 1) * r * eta, axis=2)
+        Vw = np.sum(Oq * eta * eta * tt / ((1 + tt) * (1 + tt)), axis=2)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lz = np.where(Vw > 0, W / np.sqrt(Vw), f(0))
+        e = np.log(h) - log2pi / 2 - z[None, :] ** 2 / 2 + np.sum(Oq * (Yf[:, None, :] * eta - lse), axis=2)
+        ltz = tail = np.full((N, Q), np.nan, dtype=f)
+        if t.rt:
+            vv = f(max(v, 0.0))
+            g = Of / sg[None, :]                                                              # (N, J): g_j at the observed cells, 0 elsewhere
+            d = lam[None, None, :] - lt[:, None, :] - rho[None, None, :] * th[:, :, None]
+            P, R, D = np.sum(g, axis=1)[:, None], np.sum(g[:, None, :] * d, axis=2), np.sum(g[:, None, :] * d * d, axis=2)
+            L = np.sum(Of * np.log(sg)[None, :], axis=1)[:, None]
+            m = (np.asarray(m0, dtype=f)[:, None] if np.ndim(m0) else f(m0)) + f(m1) * th
+            quad = D + (P * m * m - 2 * R * m - vv * R * R) / (1 + vv * P)
+            e = e - n[:, None] * log2pi / 2 - L / 2 - np.log1p(vv * P) / 2 - quad / 2
+            Qf = np.maximum(quad, 0)
+            tail, ltz = chi2TailHost(Qf, n[:, None], dtype=f), wilsonHilfertyHost(Qf, n[:, None], dtype=f)
+        M = np.max(e, axis=1, keepdims=True)
+        p = np.exp(e - M)
+        s = np.sum(p, axis=1)
+        py = (erfc((-lz / np.sqrt(f(2))).astype(np.float64)) / 2).astype(f)
+        for lst, val in zip((LZ, PY, LTZ, PT), (lz, py, ltz, tail)):
+            lst.append(np.sum(p * np.where(n[:, None] > 0, val, f(0)), axis=1) / s)
+        l.append(M[:, 0] + np.log(s))
+        S.append(s)
+    LZ, PY, LTZ, PT, l, S = (np.array(a_) for a_ in (LZ, PY, LTZ, PT, l, S))                 # (R, N)
+    om = np.exp(l - np.max(l, axis=0, keepdims=True)) if wt == _lib.SCORE_LIKELIHOOD else np.ones_like(l)
+    Wt = np.sum(om, axis=0)
+    nan = np.full(N, np.nan)
+    mean = lambda a_, on: np.where(on, np.sum(om * a_, axis=0) / Wt, nan)
+    coarse = np.any(S < 2.0, axis=0)
+    out = OutputPersonFit(lz=mean(LZ, n > 0), pResp=mean(PY, n > 0), ltz=mean(LTZ, n > 0) if t.rt else nan, pTime=mean(PT, n > 0) if t.rt else nan,
+                          rowEss=Wt * Wt / np.sum(om * om, axis=0), coarse=coarse, nRows=LZ.shape[0], nNodes=Q, nCoarse=int(np.sum(coarse)),
+                          weighting="likelihood" if wt else "equal")
+    if obs is not None:
+        out.nObs = n.astype(np.int32)
+    return (out, S) if with_S else out
 
 
 def pvRow(k, K, n_rows):

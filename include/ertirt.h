@@ -416,6 +416,47 @@ int erm_plausible_values_masked(int device, int model, int64_t n_subj, int32_t n
                                 const uint8_t* obs, const double* rows, int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node,
                                 int32_t* coarse, double* out4, int32_t* n_obs);
 
+/* Person fit: whether a respondent's score can be trusted -- a fit flag beside every score, for the fitted data set, new respondents and incomplete patterns, from the
+ * item-level trace alone.  Pre-knowledge, rapid guessing, copying and a speeded ending show as a response pattern or a time pattern that the model finds improbable
+ * for that person.  Deterministic (no random numbers); computed AFTER the run from resident state, in both trace modes; the calls only read the engine.  Served: the
+ * five models of erm_get_marginal_waic; the two quantile models are refused with ERM_ERR_ARG for its reason.
+ * Definition, for subject i at row s.  O_i = the observed items, n = n_i their count (all n_item on complete data).  The population law, the node rule (z_q, theta_q,
+ * e_q, M, S) and the item sums (P, R0, R1, D0, D1, D2) are exactly those of erm_get_marginal_waic; (M, S) are its (M, S) bit for bit, so COARSE is its flag.
+ *   responses, at node theta_q    eta_j = a_j (theta_q - b_j),  t_j = e^-|eta_j|;  r_j = t_j / (1 + t_j) if (y_j = 1) <=> (eta_j >= 0), else r_j = 1 / (1 + t_j).
+ *                      W = sum_{j in O_i} (2 y_j - 1) r_j eta_j  (= l0 - E[l0 | theta], l0 = sum y eta - log(1 + e^eta));
+ *                      Vw = sum_{j in O_i} eta_j^2 t_j / (1 + t_j)^2  (= Var[l0 | theta]);   lz(theta_q) = W / sqrt(Vw), and 0 (its Phi: 1/2) when Vw = 0.
+ *                      lz is the statistic of Drasgow, Levine and Williams (1985); negative means misfit.  This is the form with no cancellation: W is never formed
+ *                      as theta A1 - A0 - sum p eta, which loses every digit at a node where all items are decided (a_j = 8, |eta| > 30).
+ *   response times, at node theta_q (models with times)    Qf = D + (P m^2 - 2 R m - v R^2) / (1 + v P), clamped at 0, with R = R0 - theta R1,
+ *                      D = D0 - 2 theta D1 + theta^2 D2, m = m0 + m1 theta: exactly -2 (T(theta) - its constants).  Given theta the log-times are
+ *                      N(lambda - rho theta - m 1, diag sig2t + v 1 1'); Qf is their Mahalanobis form: chi^2_n exactly, with zeta integrated out.
+ *                      tail(theta_q) = P(chi^2_n >= Qf), the finite sum for integer n: with y = Qf / 2, o = n mod 2, m = floor(n / 2),
+ *                        base = o ? erfc(sqrt y) : 0,  t_0 = e^-y (o ? 2 sqrt(y / pi) : 1),  t_k = t_(k-1) y / (k + o / 2),  tail = base + sum_{k < m} t_k;  0 for y > 700.
+ *                      ltz(theta_q) = ((Qf / n)^(1/3) - (1 - 2 / (9 n))) / sqrt(2 / (9 n)): Wilson-Hilferty's z, positive means misfit.  Descriptive: it is not
+ *                      used for the p-value.
+ *   at the row         four weighted means under w_q = exp(e_q - M) / S:  LZ_s = sum w_q lz(theta_q),  PY_s = sum w_q Phi(lz(theta_q)), Phi(x) = erfc(-x / sqrt 2) / 2,
+ *                      LTZ_s = sum w_q ltz(theta_q),  PT_s = sum w_q tail(theta_q).  The six running sums S, S LZ, S PY, S LTZ, S PT and M stream and merge under the
+ *                      running maximum exactly as the scores' sums do.  PY and PT are posterior predictive p-values with a realised discrepancy (Gelman, Meng and
+ *                      Stern 1996): PY through lz's normal approximation, PT exact given theta.  Small means misfit for both.
+ *   across the rows    in trace order, with weight omega_s = 1 (ERM_SCORE_EQUAL) or exp(l_s - Lambda) with the running-maximum rescale (ERM_SCORE_LIKELIHOOD), as
+ *                      erm_get_scores: the weighted running means of the four row values;  row_ess = (sum omega)^2 / sum omega^2.
+ * Output: fit, column-major [n_subj][6], column ERM_FIT_*; COARSE is 1.0 if S < 2 at some row and 0.0 otherwise.  out4 (may be NULL) = { n_subj, n_rows, Q, number of
+ *   coarse subjects }.  GibbsMlIrt gets NaN in LTZ and P_TIME.  A subject with n_i = 0 gets NaN in all four statistic columns; ROW_ESS and COARSE stay ordinary.
+ *   Everything is fp64 whatever the engine's precision; every sum has a fixed order and nothing is atomic; a subject's result depends on its own data, the rows, Q and
+ *   the weighting only; results are bit-reproducible from call to call and do not depend on how the sweeps were split into erm_run calls.
+ * erm_get_person_fit: the post-burn-in rows of the resident item trace, read in place, equal weights.  n_nodes and the refusals as erm_get_scores' (a shard, no data
+ *   set, a failed run, no post-burn-in row: ERM_ERR_STATE, the words name "the person fit"); ONE post-burn-in row is enough.  erm_farm_get_person_fit (below): the
+ *   same over the farm's chain-major table on chain 0's device.
+ * erm_person_fit: the same kernel on caller-supplied data and rows, validated as erm_score validates them; n_rows >= 1; an unknown weighting: ERM_ERR_ARG.
+ * erm_person_fit_masked: erm_person_fit with the observed mask of erm_score_masked, with its validation and its n_obs; obs == NULL calls erm_person_fit.
+ * Out of scope: the quantile models, separate response and time masks, a joint p-value, item-level fit. */
+enum { ERM_FIT_LZ = 0, ERM_FIT_P_RESP = 1, ERM_FIT_LTZ = 2, ERM_FIT_P_TIME = 3, ERM_FIT_ROW_ESS = 4, ERM_FIT_COARSE = 5, ERM_FIT_COLS = 6 };
+int erm_get_person_fit(erm_handle h, int32_t n_nodes, double* fit, double* out4);
+int erm_person_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
+                   int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4);
+int erm_person_fit_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                          const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4, int32_t* n_obs);
+
 /* Marginal PSIS-LOO: Pareto-smoothed importance-sampling leave-one-subject-out (Vehtari, Gelman and Gabry 2017; Vehtari, Simpson, Gelman, Yao and Gabry 2024), the
  * criterion the "p_u > 0.4" count of erm_get_waic / erm_get_marginal_waic sends its reader to, and with it a Pareto k^ per respondent: for which respondents the
  * posterior would move if they were left out -- the aberrant or highly influential response / time patterns.  (ERM_SCORE_LIKELIHOOD importance-weights the rows with raw
@@ -544,6 +585,7 @@ int erm_farm_get_mean(erm_farm_handle f, erm_state* out);
 int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Dbar over the rows of all chains, Dhat at the joint Post.mean (the same reduction as erm_farm_get_mean, evaluated on the first device) */
 int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* the marginal WAIC over the rows of all chains: see erm_get_marginal_waic */
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4);                          /* the scores over the rows of all chains: see erm_get_scores */
+int erm_farm_get_person_fit(erm_farm_handle f, int32_t n_nodes, double* fit, double* out4);                        /* the person fit over the rows of all chains: see erm_get_person_fit */
 int erm_farm_get_quantile_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* LatentQr: see erm_get_quantile_marginal_waic */
 int erm_farm_get_quantile_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* LatentQr: see erm_get_quantile_marginal_waic */
 int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* the marginal PSIS-LOO over the rows of all chains: see erm_get_marginal_loo */
