@@ -494,6 +494,7 @@ class Engine(_Diagnostics, _ItemPasses):
                 raise TypeError(f"unknown config field {k}")
             setattr(cfg, k, v)
         self.cfg = cfg
+        self._pw_unit = None         # the WAIC unit as set through this object (None: never; a unit set past it, through the C ABI, is read off the unit count)
         self._h = C.c_void_p()
         check(lib.erm_create(C.byref(cfg), C.byref(self._h)))
         self._lib = lib
@@ -617,6 +618,7 @@ class Engine(_Diagnostics, _ItemPasses):
                 raise ValueError("waic must be None, 'subject' or 'cell'")
             unit = POINTWISE_UNITS[unit]
         check(self._lib.erm_set_pointwise(self._h, int(unit)))
+        self._pw_unit = int(unit)
 
     @property
     def pointwise_units(self):
@@ -634,7 +636,10 @@ class Engine(_Diagnostics, _ItemPasses):
         U = self.pointwise_units
         lppd, p = np.empty(U, dtype=np.float64), np.empty(U, dtype=np.float64)
         check(self._lib.erm_get_pointwise(self._h, lppd.ctypes.data, p.ctypes.data))
-        if U == self.cfg.n_subj * self.cfg.n_item and U != self.cfg.n_subj:
+        # (the unit as set through this object; set past it, the count decides -- which cannot tell the units apart at one item, as many cells as subjects: the
+        # C ABI has no getter for the unit, and there the two shapes hold the same values in the same order)
+        unit = self._pw_unit if self._pw_unit is not None else (POINTWISE_CELL if U != self.cfg.n_subj else POINTWISE_SUBJECT)
+        if unit == POINTWISE_CELL and U == self.cfg.n_subj * self.cfg.n_item:
             sh = (self.cfg.n_subj, self.cfg.n_item)
             return lppd.reshape(sh, order="F"), p.reshape(sh, order="F")
         return lppd, p
@@ -690,6 +695,7 @@ class _Borrowed(Engine):
 
     def __init__(self, lib, handle, cfg):
         self._lib, self._h, self.cfg = lib, handle, cfg
+        self._pw_unit = None
 
     def close(self):
         self._h = None

@@ -210,4 +210,52 @@ inline int plan_geometry(const GeomIn& g, Geom& out, std::string& err)
     return 0;
 }
 
+// ---- The passes behind a sweep (WAIC: erm_waic_kernels.hpp; the replicate pass and its item step: erm_predictive_kernels.hpp) and DIC's loglik_kernel
+// (erm_service_kernels.hpp).  Their geometry is a function of (model, N, J) and, for the WAIC grids, the compute-unit count -- never of the sweep kernels'
+// plan --, decided here and nowhere else: the engine launches what pass_geom() says, tests/pass_geom_check.cpp replays the kernels' index loops on it.
+constexpr int PRED_NQ_RT = 5, PRED_NQ_RA = 3;              // slab columns of the replicate pass: Delta, sum l, [D^T_obs, D^T_rep,] score_rep
+constexpr int PRED_MAX_BLOCKS = 1024;                      // slab rows at most
+constexpr int PRED_IT_THREADS = 1024, PRED_IT_PARTS = PRED_IT_THREADS / 64;
+constexpr int PASS_THREADS = 256;                          // workgroup of the WAIC pass and of loglik_kernel; the replicate pass starts from it
+constexpr int PW_BLOCKS_PER_CU_SUBJECT = 8, PW_BLOCKS_PER_CU_CELL = 16;
+constexpr int LOGLIK_MAX_BLOCKS = 1024, LOGLIK_ROWS = 64;  // loglik_kernel: at most this many workgroups, of at least this many subjects (but the last)
+
+ERM_HD constexpr int pred_nq(int model) { return model == MLIRT ? PRED_NQ_RA : PRED_NQ_RT; }
+// lanes per subject of the passes behind a sweep (the replicate pass and the WAIC subject unit), as log2: the smallest power of two <= 64 that leaves a lane at most four items
+constexpr int pass_log_lanes(int J) { int lw = 0; while ((1 << lw) < 64 && (4 << lw) < J) ++lw; return lw; }
+// dynamic LDS of predictive_kernel with T threads: a b lambda sig2t rho | column means [6][J], then T / W private item accumulators [NQ][J]
+inline size_t pred_lds_bytes(int model, int J, int T, int logW) { return ((size_t)6 * J + (size_t)(T >> logW) * pred_nq(model) * J) * sizeof(double); }
+
+struct PassGeom {
+    int logW = 0;                       // W = 2^logW lanes share a subject (both passes behind a sweep)
+    int T = PASS_THREADS, R = PASS_THREADS;      // replicate pass: threads per workgroup, subjects a workgroup takes at a time (W * R == T)
+    int nq = PRED_NQ_RT;                // slab columns
+    int nb_pred = 1;                    // replicate pass: workgroups = slab rows
+    size_t lds_pred = 0;                // its dynamic LDS
+    int R_pw = PASS_THREADS;            // WAIC, subject unit: subjects a 256-thread workgroup takes at a time
+    int nb_pw_subject = 1, nb_pw_cell = 1;      // WAIC grids (grid-stride loops behind the caps)
+    size_t lds_pw = 0;
+    int nb_loglik = 1; long long rows_per_block = 1;      // loglik_kernel: workgroup b owns subjects [b * rows_per_block, ...) clipped to N
+    size_t lds_loglik = 0;
+};
+
+// (the caller has validated model, N >= 1, 1 <= J <= MAX_ITEMS and cu_count >= 1: plan_geometry)
+inline PassGeom pass_geom(int model, long long N, int J, int cu_count)
+{
+    PassGeom g;
+    g.logW = pass_log_lanes(J); g.T = PASS_THREADS; g.nq = pred_nq(model);
+    while (g.T > 64 && pred_lds_bytes(model, J, g.T, g.logW) > LDS_LIMIT) g.T >>= 1;      // long tests: fewer subject slots (nItem 896: 128 threads, 115 KB)
+    g.lds_pred = pred_lds_bytes(model, J, g.T, g.logW);
+    g.R = g.T >> g.logW;
+    g.nb_pred = (int)std::min<long long>((N + g.R - 1) / g.R, PRED_MAX_BLOCKS);
+    g.R_pw = PASS_THREADS >> g.logW;
+    g.nb_pw_subject = (int)std::min<long long>((N + g.R_pw - 1) / g.R_pw, (long long)cu_count * PW_BLOCKS_PER_CU_SUBJECT);
+    g.nb_pw_cell = (int)std::min<long long>((N * (long long)J + PASS_THREADS - 1) / PASS_THREADS, (long long)cu_count * PW_BLOCKS_PER_CU_CELL);
+    g.lds_pw = (size_t)7 * J * sizeof(double);
+    g.nb_loglik = (int)std::min<long long>(LOGLIK_MAX_BLOCKS, (N + LOGLIK_ROWS - 1) / LOGLIK_ROWS);
+    g.rows_per_block = (N + g.nb_loglik - 1) / g.nb_loglik;
+    g.lds_loglik = ((size_t)5 * J + 4 + 2 * PMAX) * sizeof(double);
+    return g;
+}
+
 }  // namespace erm

@@ -25,20 +25,12 @@
 // bit-reproducible run to run and do not depend on the sweep kernels' geometry or schedule.
 #pragma once
 #include "erm_kernels.hpp"
+#include "erm_geometry.hpp"      // the pass's launch geometry, slab columns and LDS request: pass_geom, pred_nq, pass_log_lanes, pred_lds_bytes
 
 namespace erm {
 
 constexpr uint32_t SITE_PRED = 14;                         // the replicate draws' stream site (free in erm_rng.hpp's Site)
-constexpr int PRED_NQ_RT = 5, PRED_NQ_RA = 3;              // slab columns: Delta, sum l, [D^T_obs, D^T_rep,] score_rep
 constexpr int PRED_SUBJ = 8, PRED_ITEM = 12, PRED_TOT = 8; // doubles per subject [RA, RT][4], per item [RA, RT, SCORE][4], of the data set [RA, RT][4]
-constexpr int PRED_MAX_BLOCKS = 1024;                      // slab rows at most
-constexpr int PRED_IT_THREADS = 1024, PRED_IT_PARTS = PRED_IT_THREADS / 64;
-
-__host__ __device__ constexpr int pred_nq(int model) { return model == MLIRT ? PRED_NQ_RA : PRED_NQ_RT; }
-// lanes per subject of the passes behind a sweep (this one and the WAIC subject unit), as log2: the smallest power of two <= 64 that leaves a lane at most four items
-constexpr int pass_log_lanes(int J) { int lw = 0; while ((1 << lw) < 64 && (4 << lw) < J) ++lw; return lw; }
-// dynamic LDS of predictive_kernel with T threads: a b lambda sig2t rho | column means [6][J], then T / W private item accumulators [NQ][J]
-inline size_t pred_lds_bytes(int model, int J, int T, int logW) { return ((size_t)6 * J + (size_t)(T >> logW) * pred_nq(model) * J) * sizeof(double); }
 
 struct PredArgs {
     CellArgs cell;                                        // erm_waic_kernels.hpp

@@ -24,7 +24,7 @@ struct CellArgs {
     const double* par;                                    // the parameter block of the sweep just drawn
     const double* cm;                                     // column means of logT [J]
     const Ctl* ctl;                                       // the counters that sweep published: sweep, row, burn_rows
-    long long N; int J; int logW;                         // W = 2^logW lanes share a subject (pass_log_lanes, erm_predictive_kernels.hpp)
+    long long N; int J; int logW;                         // W = 2^logW lanes share a subject (pass_geom, erm_geometry.hpp)
     double k1, k2;
 };
 

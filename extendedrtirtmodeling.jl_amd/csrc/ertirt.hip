@@ -710,12 +710,28 @@ template <typename real> struct Engine : EngineBase {
     // ---- WAIC: the pointwise pass behind a sweep (erm_waic_kernels.hpp).  buf: the half of the double buffers the sweep published its parameter block and
     // counters in.  The same launch for every sweep (the kernel itself skips burn-in rows), so it sits inside the captured graphs like the sweep's own kernels.
     int64_t pw_units(int unit) const { return unit == PW_SUBJECT ? N : unit == PW_CELL ? N * (int64_t)J : 0; }
+    // the geometry of every pass behind a sweep and of DIC's loglik_kernel: pass_geom (erm_geometry.hpp) and nothing else
+    PassGeom pgeom() const { return pass_geom(cfg.model, N, J, cu_count); }
+    // A pass whose launch was refused must not leave zeros behind a run that reports success: outside stream capture the launch status is read, inside a
+    // capture (where a refused node invalidates the capture) the capture's own status.  (hipGetLastError also returns an earlier error of this thread that nobody
+    // read: the message names the launch it was found behind, not necessarily its cause.)
+    int behind_status(const char* what) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIPCHK(hipStreamIsCapturing(stream, &cs));
+        if (cs == hipStreamCaptureStatusNone) {
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail(ERM_ERR_HIP, std::string("HIP error pending behind the launch of ") + what + ": " + hipGetErrorString(e));
+        } else if (cs != hipStreamCaptureStatusActive) {
+            return fail(ERM_ERR_HIP, std::string("launch of ") + what + " invalidated the stream capture");
+        }
+        return 0;
+    }
     // the resident cell as every pass behind a sweep reads it (CellArgs, erm_waic_kernels.hpp)
     CellArgs cell_args(int buf) const {
         CellArgs c{};
         c.Y = dY.as<uint8_t>(); c.C = dC.p; c.nu = mt().nu == NU_CELL ? dNuSnap.p : nullptr; c.theta = dTheta.p; c.zeta = dZeta.p;
         c.par = dParB[buf].template as<double>(); c.cm = dCst.as<double>() + cst_off_m(J); c.ctl = dCtlB[buf].template as<Ctl>();
-        c.N = N; c.J = J; c.logW = pass_log_lanes(J);
+        c.N = N; c.J = J; c.logW = pgeom().logW;
         const QuantileConsts k = quantile_consts();
         c.k1 = k.k1; c.k2 = k.k2;
         return c;
@@ -725,16 +741,10 @@ template <typename real> struct Engine : EngineBase {
         PwArgs a{};
         a.cell = cell_args(buf);
         a.acc_ms = dPwMs.as<double2>(); a.acc_w = dPwW.as<double2>();
-        const size_t lds = (size_t)7 * J * sizeof(double);
-        if (pw_unit == PW_SUBJECT) {
-            const int64_t R = 256 >> a.cell.logW;
-            const int nb = (int)std::min<int64_t>((N + R - 1) / R, (int64_t)cu_count * 8);
-            hipLaunchKernelGGL((pointwise_kernel<MODEL, real, PW_SUBJECT>), dim3(nb), dim3(256), lds, stream, a);
-        } else {
-            const int nb = (int)std::min<int64_t>((N * (int64_t)J + 255) / 256, (int64_t)cu_count * 16);
-            hipLaunchKernelGGL((pointwise_kernel<MODEL, real, PW_CELL>), dim3(nb), dim3(256), lds, stream, a);
-        }
-        return 0;
+        const PassGeom g = pgeom();
+        if (pw_unit == PW_SUBJECT) hipLaunchKernelGGL((pointwise_kernel<MODEL, real, PW_SUBJECT>), dim3(g.nb_pw_subject), dim3(PASS_THREADS), g.lds_pw, stream, a);
+        else hipLaunchKernelGGL((pointwise_kernel<MODEL, real, PW_CELL>), dim3(g.nb_pw_cell), dim3(PASS_THREADS), g.lds_pw, stream, a);
+        return behind_status("the WAIC pass");
     }
     // The one way a pass behind the sweep is switched (erm_set_pointwise, erm_set_predictive).  sw: the pass's switch (pw_unit / pred_thin, 0 = off), want: its new
     // value; bufs: the buffers the pass owns and the sizes it wants of them now (0 = released).  The refusals, in this order; the device drained; `configure` (the
@@ -812,33 +822,24 @@ template <typename real> struct Engine : EngineBase {
     // ---- posterior predictive checks: the replicate pass behind a sweep and the item / total step behind it (erm_predictive_kernels.hpp).  Like the WAIC pass
     // the same two launches for every sweep (the kernels skip rows that are no replicate rows), inside the captured graphs; with both enabled, both run.
     // The geometry is a function of (N, J) alone: the accumulators do not depend on the device, the sweep kernels' geometry or the schedule.
-    struct PredGeom { int logW, T, nb, nq; size_t lds; };
-    PredGeom pred_geom() const {
-        PredGeom g{};
-        g.logW = pass_log_lanes(J); g.T = 256; g.nq = pred_nq(cfg.model);
-        while (g.T > 64 && pred_lds_bytes(cfg.model, J, g.T, g.logW) > (size_t)160 * 1024) g.T >>= 1;      // long tests: fewer subject slots (nItem 896: 128 threads, 115 KB)
-        g.lds = pred_lds_bytes(cfg.model, J, g.T, g.logW);
-        const int64_t R = g.T >> g.logW;
-        g.nb = (int)std::min<int64_t>((N + R - 1) / R, PRED_MAX_BLOCKS);
-        return g;
-    }
     template <int MODEL> int launch_behind(int buf) {
         if (int rc = launch_pointwise<MODEL>(buf)) return rc;
         return launch_predictive<MODEL>(buf);
     }
     template <int MODEL> int launch_predictive(int buf) {
         if (pred_thin == 0) return 0;
-        const PredGeom g = pred_geom();
+        const PassGeom g = pgeom();
         PredArgs a{};
         a.cell = cell_args(buf);
         a.subj = dPredSubj.as<double>(); a.slab = dPredSlab.as<double>(); a.thin = (uint32_t)pred_thin;
         a.seed = cfg.seed; a.chain = (uint32_t)cfg.chain_id; a.row_base = (uint32_t)row_base;
-        hipLaunchKernelGGL((predictive_kernel<MODEL, real>), dim3(g.nb), dim3(g.T), g.lds, stream, a);
+        hipLaunchKernelGGL((predictive_kernel<MODEL, real>), dim3(g.nb_pred), dim3(g.T), g.lds_pred, stream, a);
+        if (int rc = behind_status("the replicate pass")) return rc;
         PredItemArgs b{};
-        b.slab = dPredSlab.as<double>(); b.nb = g.nb; b.nq = g.nq; b.J = J; b.N = (double)N; b.k0 = dCst.as<double>() + cst_off_k0(J);
+        b.slab = dPredSlab.as<double>(); b.nb = g.nb_pred; b.nq = g.nq; b.J = J; b.N = (double)N; b.k0 = dCst.as<double>() + cst_off_k0(J);
         b.ctl = a.cell.ctl; b.thin = a.thin; b.item = dPredItem.as<double>(); b.tot = dPredItem.as<double>() + (size_t)J * PRED_ITEM;
         hipLaunchKernelGGL(predictive_items_kernel, dim3(1), dim3(PRED_IT_THREADS), 0, stream, b);
-        return 0;
+        return behind_status("the replicate pass's item step");
     }
     int pred_clear() {
         if (dPredSubj.p) { HIPCHK(hipMemsetAsync(dPredSubj.p, 0, dPredSubj.bytes, stream)); HIPCHK(hipMemsetAsync(dPredItem.p, 0, dPredItem.bytes, stream)); }
@@ -846,18 +847,18 @@ template <typename real> struct Engine : EngineBase {
     }
     int set_predictive(int on, int32_t thin) override {
         if (on && thin < 1) return fail(ERM_ERR_ARG, "erm_set_predictive: thin must be at least 1");
-        const PredGeom g = pred_geom();
+        const PassGeom g = pgeom();
         const size_t dbl = on ? sizeof(double) : 0;      // off: every buffer released
         const char* acc = "the predictive accumulators";
         auto lds_limit = [&]() -> int {
             if (!on) return 0;
             return dispatch([&](auto m) -> int {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&predictive_kernel<decltype(m)::value, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&predictive_kernel<decltype(m)::value, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_pred));
                 return 0; });
         };
         if (int rc = switch_pass("erm_set_predictive", "posterior predictive checks are", pred_thin, on ? thin : 0,
                                  {{&dPredSubj, (size_t)N * PRED_SUBJ * dbl, acc}, {&dPredItem, ((size_t)J * PRED_ITEM + PRED_TOT + 1) * dbl, acc},
-                                  {&dPredSlab, (size_t)g.nb * g.nq * J * dbl, "the predictive slab"}}, "the copy of nu", lds_limit)) return rc;
+                                  {&dPredSlab, (size_t)g.nb_pred * g.nq * J * dbl, "the predictive slab"}}, "the copy of nu", lds_limit)) return rc;
         return pred_clear();
     }
     int64_t predictive_reps() const override { return pred_thin > 0 ? (post_rows + pred_thin - 1) / pred_thin : 0; }
@@ -1568,7 +1569,8 @@ template <typename real> struct Engine : EngineBase {
     int loglik_at(const double* dsum, double inv, double* ll) override {
         if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
         HIPCHK(hipSetDevice(cfg.device));
-        const int nb = (int)std::min<int64_t>(1024, (N + 63) / 64);
+        const PassGeom g = pgeom();
+        const int nb = g.nb_loglik;
         DevBuf dPart;
         if (int rc = dPart.alloc((size_t)nb * sizeof(double))) return rc;
         LogLikArgs D{};
@@ -1578,9 +1580,8 @@ template <typename real> struct Engine : EngineBase {
         D.off_theta = L.theta; D.off_zeta = L.zeta; D.off_nu = L.nu;
         const QuantileConsts k = quantile_consts();
         D.k1 = k.k1; D.k2 = k.k2;
-        D.rows_per_block = (N + nb - 1) / nb; D.part = dPart.as<double>();
-        const size_t lds = ((size_t)5 * J + 4 + 2 * PMAX) * sizeof(double);
-        hipLaunchKernelGGL((loglik_kernel<real>), dim3(nb), dim3(256), lds, stream, D);
+        D.rows_per_block = g.rows_per_block; D.part = dPart.as<double>();
+        hipLaunchKernelGGL((loglik_kernel<real>), dim3(nb), dim3(PASS_THREADS), g.lds_loglik, stream, D);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
         std::vector<double> part(nb);

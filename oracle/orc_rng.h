@@ -238,6 +238,7 @@ static inline int orc_pg1_attempt(double z, const uint32_t w[4], double* out)
 static inline double orc_pg1(orc_stream* s, double c)
 {
     double z = 0.5 * fabs(c);
+    if (!(z == z)) return z;      /* a NaN argument (a state that is no longer finite) has no accepting attempt: NaN out instead of spinning */
     for (;;) {
         uint32_t w[4];
         w[0] = orc_u32(s); w[1] = orc_u32(s); w[2] = orc_u32(s); w[3] = orc_u32(s);
@@ -250,6 +251,7 @@ static inline double orc_pg1(orc_stream* s, double c)
 static inline double orc_truncnorm0(orc_stream* s, double m, double sd)
 {
     double alpha = -m / sd, z;
+    if (!(alpha == alpha)) return alpha;      /* NaN in, NaN out (neither loop below would end) */
     if (alpha <= 0.0) {
         do { z = orc_normal(s); } while (z < alpha);
     } else {
@@ -263,10 +265,12 @@ static inline double orc_truncnorm0(orc_stream* s, double m, double sd)
     return m + sd * z;
 }
 
-/* ---- Gamma(shape >= 1, scale 1), Marsaglia-Tsang without the squeeze ---- */
+/* ---- Gamma(shape >= 1, scale 1), Marsaglia-Tsang without the squeeze.  Every caller passes shape >= 1/2; a shape below 1/3 (where d <= 0 and the
+ * method is undefined) or a NaN shape returns NaN -- it used to spin for ever ---- */
 static inline double orc_gamma(orc_stream* s, double shape)
 {
     double d = shape - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    if (!(c == c)) return c;      /* shape below 1/3 or NaN: outside the method, NaN out instead of spinning */
     for (;;) {
         double x, v;
         do { x = orc_normal(s); v = 1.0 + c * x; } while (v <= 0.0);
