@@ -2,13 +2,13 @@
 
 Export list mirrors the part of /root/reference/src/ExtendedRtIrtModeling.jl:33-77 that belongs to the hot path.
 """
-from .base import InputData, InputData4R, InputPara, OutputDic, OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions, setCond
+from .base import InputData, InputData4R, InputPara, OutputDic, OutputItemFit, OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions, setCond
 from .gibbs import (GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCross, GibbsRtIrtCrossQr, GibbsRtIrtLatent, GibbsRtIrtLatentQr, GibbsRtIrtNull,
                     GibbsRtIrtQuantile, checkConvergence, coef, compareLoo, compareWaic, drawPlausibleValues, getDic, getDicHost, getLogLikelihood,
-                    getLooMarginal, getLooMarginalQr, getPersonFit, getPlausibleValues, getPpc, getScores, getWaic, getWaicMarginal, getWaicMarginalQr, observedMask, personFit, precis, psisLoo,
+                    getItemFit, getLooMarginal, getLooMarginalQr, getPersonFit, getPlausibleValues, getPpc, getScores, getWaic, getWaicMarginal, getWaicMarginalQr, itemFit, observedMask, personFit, precis, psisLoo,
                     sample, sample_b, scoreRespondents, simulateData)
 from .twins import (ess_rhat, getLooMarginalHost, getLooMarginalQrHost, getPpcHost, getWaicHost, getWaicMarginalHost, getWaicMarginalQrHost,
-                    marginalLogLikHost, personFitHost, plausibleValuesHost, pointwiseLogLikHost, psisLooHost, quantileMarginalLogLikHost, rank_ess_rhat, scoresHost)
+                    itemFitHost, marginalLogLikHost, personFitHost, plausibleValuesHost, pointwiseLogLikHost, psisLooHost, quantileMarginalLogLikHost, rank_ess_rhat, scoresHost)
 from .simtools import (comparePara, getBias, getMetrics, getMetrics2, getRmse, runSimulation, setDataMlIrt, setDataRtIrt, setDataRtIrtCross,
                        setDataRtIrtLatent, setDataRtIrtNull,
                        setTrueParaMlIrt, setTrueParaRtIrt, setTrueParaRtIrtCross, setTrueParaRtIrtLatent)
@@ -29,6 +29,7 @@ __all__ = [
     "getBias", "getRmse", "getDic", "getDicHost", "getWaic", "getWaicHost", "compareWaic", "pointwiseLogLikHost",
     "getWaicMarginal", "getWaicMarginalHost", "marginalLogLikHost", "OutputWaic", "getScores", "scoreRespondents", "scoresHost", "OutputScores",
     "getPersonFit", "personFit", "personFitHost", "OutputPersonFit",
+    "getItemFit", "itemFit", "itemFitHost", "OutputItemFit",
     "getPlausibleValues", "drawPlausibleValues", "plausibleValuesHost", "OutputPv", "observedMask", "getLooMarginal", "getLooMarginalHost",
     "getWaicMarginalQr", "getWaicMarginalQrHost", "getLooMarginalQr", "getLooMarginalQrHost", "quantileMarginalLogLikHost",
     "psisLoo", "psisLooHost", "compareLoo", "OutputLoo", "getPpc", "getPpcHost", "OutputPpc", "checkConvergence", "ess_rhat", "rank_ess_rhat",

@@ -74,6 +74,7 @@ EXPORTS = [
     "erm_quantile_marginal_loglik",
     "erm_marginal_loglik_masked", "erm_score_masked", "erm_plausible_values_masked",
     "erm_get_person_fit", "erm_farm_get_person_fit", "erm_person_fit", "erm_person_fit_masked",
+    "erm_get_item_fit", "erm_farm_get_item_fit", "erm_item_fit",
 ]
 ABI_VERSION = 4            # ERM_ABI_VERSION of the include/ertirt.h these ctypes structs mirror
 
@@ -205,7 +206,7 @@ def load():
     I32, VP = C.c_int32, C.c_void_p
     stems = [fam.stem for fam in MARGINAL_FAMILIES.values()]
     pairs = [("diagnostics", [C.c_int, VP, VP]), ("convergence", [C.c_int, VP]), ("rank_diagnostics", [C.c_int, VP, VP, VP]), ("rank_convergence", [C.c_int, VP]),
-             ("scores", [I32, VP, VP]), ("person_fit", [I32, VP, VP]), ("plausible_values", [I32, I32, C.c_uint64, VP, VP, VP, VP])]
+             ("scores", [I32, VP, VP]), ("person_fit", [I32, VP, VP]), ("item_fit", [I32, VP, VP]), ("plausible_values", [I32, I32, C.c_uint64, VP, VP, VP, VP])]
     pairs += [(stem + "waic", [I32, VP, VP, VP]) for stem in stems] + [(stem + "loo", [I32, VP, VP]) for stem in stems]
     for prefix in ("erm_get_", "erm_farm_get_"):          # every pair that _Diagnostics and _ItemPasses resolve through _get_prefix
         for name, args in pairs:
@@ -222,6 +223,7 @@ def load():
     lib.erm_plausible_values_masked.argtypes = mhead + [I32, I32, C.c_uint64, VP, VP, VP, VP, VP]
     lib.erm_person_fit.argtypes = head + [I32, I32, VP, VP]
     lib.erm_person_fit_masked.argtypes = mhead + [I32, I32, VP, VP, VP]
+    lib.erm_item_fit.argtypes = mhead + [I32, VP, VP]      # (obs may be NULL; no weighting, no n_obs)
     _lib = lib
     return lib
 
@@ -320,6 +322,24 @@ def _fit_call(fn, h, nodes, n_subj):
     fit, out = np.empty((len(FIT_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
     check(fn(h, marginal_nodes(nodes), fit.ctypes.data, out.ctypes.data))
     return _fit_result(fit, out)
+
+
+# erm_get_item_fit / erm_farm_get_item_fit / erm_item_fit: the columns of fit [n_item][6] (ERM_IFIT_*)
+IFIT_COLUMNS = ("infit", "outfit", "respZ", "rtMsq", "rtZ", "nObs")
+
+
+def _item_fit_result(fit, out):
+    """fit as the library fills it, (6, n_item) C-ordered = column-major [n_item][6], and out4 -> a dict of the columns with nSubj, nRows, nNodes, nCoarse."""
+    res = {name: fit[k] for k, name in enumerate(IFIT_COLUMNS)}
+    res["nObs"] = fit[5].astype(np.int64)
+    res.update(nSubj=int(out[0]), nRows=int(out[1]), nNodes=int(out[2]), nCoarse=int(out[3]))
+    return res
+
+
+def _item_fit_call(fn, h, nodes, n_item):
+    fit, out = np.empty((len(IFIT_COLUMNS), n_item), dtype=np.float64), np.empty(4, dtype=np.float64)
+    check(fn(h, marginal_nodes(nodes), fit.ctypes.data, out.ctypes.data))
+    return _item_fit_result(fit, out)
 
 
 # erm_get_plausible_values / erm_farm_get_plausible_values / erm_plausible_values: the number of draws, the seed, and the outputs
@@ -476,6 +496,12 @@ class _ItemPasses:
         its exact chi^2 p-value, and the rows' effective size, computed on the device from the resident item trace after the run (equal weights).  A dict of
         FIT_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
         return _fit_call(self._pass("person_fit"), self._h, nodes, self.cfg.n_subj)
+
+    def item_fit(self, nodes=MARGINAL_NODES):
+        """erm_get_item_fit / erm_farm_get_item_fit: every item's infit, outfit, signed response residual, response-time mean square and signed response-time
+        residual with the number of subjects that observed it, computed on the device from the resident item trace after the run (equal weights).  A dict of
+        IFIT_COLUMNS [n_item] with nSubj, nRows, nNodes, nCoarse."""
+        return _item_fit_call(self._pass("item_fit"), self._h, nodes, self.cfg.n_item)
 
     def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
         """erm_get_plausible_values / erm_farm_get_plausible_values: K draws of every subject's (theta, zeta) from its posterior given the resident item trace,
@@ -924,6 +950,20 @@ def person_fit(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equa
     check(load().erm_person_fit_masked(*_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes), score_weighting(weighting), ft.ctypes.data,
                                        out.ctypes.data, n_obs.ctypes.data))
     return dict(_fit_result(ft, out), nObs=n_obs)
+
+
+def item_fit(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, device=0, obs=None):
+    """erm_item_fit: the item fit's kernels on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
+    Engine.item_trace() returns them, R >= 1.  Returns Engine.item_fit's dict.  obs [N, J], 0/1 (None: complete data, the unmasked kernel): incomplete patterns."""
+    arrays, dims = _caller_data(model, Y, logT, X, rows)
+    N, J = dims[0], dims[1]
+    ft, out = np.empty((len(IFIT_COLUMNS), J), dtype=np.float64), np.empty(4, dtype=np.float64)
+    O = None if obs is None else _caller_obs(obs, N, J)[0]
+    head = list(_caller_head(device, model, arrays, dims, O))
+    if O is None:
+        head.insert(8, None)                                  # obs = NULL between X and rows
+    check(load().erm_item_fit(*head, marginal_nodes(nodes), ft.ctypes.data, out.ctypes.data))
+    return _item_fit_result(ft, out)
 
 
 def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES, device=0, obs=None):

@@ -195,6 +195,33 @@ class OutputPersonFit:
                 f"flaggedResp={int(np.sum(fr))}, flaggedTime={int(np.sum(ft))})")
 
 
+class OutputItemFit:
+    """Item fit and drift (getItemFit / itemFit; the reference has no counterpart): per item infit and outfit (mean squares of the response residuals, about 1),
+    respZ (the signed response residual; negative: harder than calibrated), rtMsq (mean square of the leave-one-item-out response-time residual, about 1) and rtZ
+    (its signed sum; positive: slower than calibrated) -- the two time columns NaN for GibbsMlIrt --, nObs (J,) the subjects that observed the item (an item nobody
+    observed has NaN in the five statistics); nSubj, nRows, nNodes, nCoarse as OutputScores'.  The signed columns are the ones that find drift in a new sample; a
+    misfit that a free a_j or sig2t_j absorbs does not show on the item's own calibration sample."""
+
+    def __init__(self, infit=None, outfit=None, respZ=None, rtMsq=None, rtZ=None, nObs=None, nRows=None, nNodes=None, nCoarse=None, nSubj=None):
+        self.infit, self.outfit, self.respZ, self.rtMsq, self.rtZ, self.nObs = infit, outfit, respZ, rtMsq, rtZ, nObs
+        self.nRows, self.nNodes, self.nCoarse, self.nSubj = nRows, nNodes, nCoarse, nSubj
+
+    def flagged(self, z=3.0, lo=0.7, hi=1.3):
+        """(responses, times): boolean (J,) -- |respZ| (|rtZ|) is at least z, or infit (rtMsq) lies outside [lo, hi]; NaN is not flagged."""
+        def flag(sz, msq):
+            if sz is None or msq is None:
+                return np.zeros(0, dtype=bool)
+            sz, msq = np.asarray(sz, dtype=np.float64), np.asarray(msq, dtype=np.float64)
+            with np.errstate(invalid="ignore"):
+                return (np.abs(sz) >= z) | (msq < lo) | (msq > hi)
+        return flag(self.respZ, self.infit), flag(self.rtZ, self.rtMsq)
+
+    def __repr__(self):
+        fr, ft = self.flagged()
+        return (f"OutputItemFit(nItem={None if self.infit is None else np.size(self.infit)}, nSubj={self.nSubj}, nRows={self.nRows}, nNodes={self.nNodes}, "
+                f"nCoarse={self.nCoarse}, flaggedResp={int(np.sum(fr))}, flaggedTime={int(np.sum(ft))})")
+
+
 class OutputPv:
     """Plausible values of the respondents (getPlausibleValues / drawPlausibleValues; the reference has no counterpart): theta (N, K) and zeta (N, K), K draws per
     subject from its posterior given the item trace (zeta is NaN for GibbsMlIrt); node (N, K), the rule's node behind every draw; coarse (N,), the theta rule was too

@@ -4,7 +4,8 @@
 // marginal WAIC and LOO (erm_get_quantile_marginal_* and erm_quantile_marginal_loglik) are the same makers and products for FAMILY_QUANTILE, and the
 // three masked entries (erm_marginal_loglik_masked / erm_score_masked / erm_plausible_values_masked) the caller-data maker with an observed mask.
 // The person fit is a fifth pass on the same makers with a product of its own, item_fit: erm_get_person_fit, erm_farm_get_person_fit,
-// erm_person_fit and erm_person_fit_masked.
+// erm_person_fit and erm_person_fit_masked.  The item fit is a sixth, with the product item_itemfit: erm_get_item_fit, erm_farm_get_item_fit and
+// erm_item_fit.
 //
 // The first half is plain C++: the facts of a pass as one table, the refusals built from it and the chunk rule; g++ compiles this half with
 // -fsanitize=undefined -ftrapv into tests/item_pass_check (tests/test_item_pass_host.py).
@@ -34,7 +35,10 @@ constexpr ItemPassFacts ITEM_PASSES[N_ITEM_PASSES] = {
 // the fifth pass, the person fit, has its facts beside the table; every reader of a pass's facts goes through item_pass_facts
 constexpr int PASS_FIT = N_ITEM_PASSES;
 constexpr ItemPassFacts FIT_PASS_FACTS = { "the person fit", false, 1, 1, "at least one post-burn-in row" };
-constexpr const ItemPassFacts& item_pass_facts(int pass) { return pass == PASS_FIT ? FIT_PASS_FACTS : ITEM_PASSES[pass]; }
+// the sixth pass, the item fit, sits beside them in the same way
+constexpr int PASS_ITEM_FIT = N_ITEM_PASSES + 1;
+constexpr ItemPassFacts ITEM_FIT_PASS_FACTS = { "the item fit", false, 1, 1, "at least one post-burn-in row" };
+constexpr const ItemPassFacts& item_pass_facts(int pass) { return pass == PASS_ITEM_FIT ? ITEM_FIT_PASS_FACTS : pass == PASS_FIT ? FIT_PASS_FACTS : ITEM_PASSES[pass]; }
 inline std::string item_pass_on_shard(int pass)
 {
     const ItemPassFacts& p = item_pass_facts(pass);
@@ -452,6 +456,48 @@ static int item_fit(const ItemSource& S, int Q, int weighting, double* fit, doub
     if (int rc = coarse.count(S.stream, &nc)) return rc;
     HIPCHK(hipMemcpy(fit, dFit.p, (size_t)N * FIT_COLS * sizeof(double), hipMemcpyDeviceToHost));
     if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
+    return 0;
+}
+// Item fit (erm_ifit_kernels.hpp; include/ertirt.h: erm_get_item_fit, erm_item_fit): the one place that launches item_fit_kernel and its two reduction kernels;
+// fit [J][6].  The subjects go through in chunks of whole blocks of IFIT_BLOCK (ifit_chunk on item_pass_chunk's budget for the 48 J bytes of a subject's workspace
+// and the 8 Q of its parked nodes; ERM_IFIT_CHUNK caps the chunk length); every chunk leaves its block sums in a table that stage B reads once at the end.
+static int item_itemfit(const ItemSource& S, int Q, double* fit, double* out4)
+{
+    const int64_t N = S.D.N;
+    const int J = S.D.J;
+    const int64_t per_subject = (int64_t)IFIT_VALS * sizeof(double) * J + (int64_t)sizeof(double) * Q;
+    const int64_t chunk = ifit_chunk(item_pass_chunk(per_subject, INT64_MAX, 0), item_chunk_cap("ERM_IFIT_CHUNK"));
+    const int64_t slots = std::min(chunk, ifit_blocks(N) * IFIT_BLOCK), n_blocks = ifit_blocks(N);      // (a multiple of IFIT_BLOCK, so of MARG_TILE)
+    DevBuf dWs, dEq, dBlk, dFit;
+    CoarseFlags coarse;
+    const char* what = "the item fit";
+    const size_t ws_bytes = (size_t)slots * J * IFIT_VALS * sizeof(double);
+    if (int rc = dWs.try_alloc(ws_bytes, what)) return rc;
+    if (int rc = dEq.try_alloc((size_t)slots * Q * sizeof(double), what)) return rc;
+    if (int rc = dBlk.try_alloc((size_t)n_blocks * J * IFIT_SUMS * sizeof(double), what)) return rc;
+    if (int rc = dFit.try_alloc((size_t)J * IFIT_COLS * sizeof(double), what)) return rc;
+    if (int rc = coarse.alloc(N, what)) return rc;
+    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+        const int64_t nc = std::min(chunk, N - c0);
+        const MargData Dc = marg_chunk(S.D, c0, nc);
+        MargArgs a = marg_args(Dc, S.rows, S.n_rows, Q);
+        a.coarse = coarse.flags() + c0;
+        HIPCHK(hipMemsetAsync(dWs.p, 0, ws_bytes, S.stream));
+        if (int rc = marg_dispatch_obs(S.D, [&](auto M, auto real, auto masked) {
+                return marg_tile_launch(&item_fit_kernel<decltype(M)::value, decltype(real), decltype(masked)::value>, a, S.stream, dEq.as<double>(), dWs.as<double>()); })) return rc;
+        hipLaunchKernelGGL(item_fit_block_kernel, dim3((unsigned)ifit_blocks(nc), (unsigned)J), dim3(IFIT_BLOCK), 0, S.stream, dWs.as<double>(), (long long)nc, J,
+                           a.off, a.idx, dBlk.as<double>() + (size_t)(c0 / IFIT_BLOCK) * J * IFIT_SUMS);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(S.stream));
+    }
+    hipLaunchKernelGGL(item_fit_finish_kernel, dim3((unsigned)((J + 255) / 256)), dim3(256), 0, S.stream, dBlk.as<double>(), (long long)n_blocks, J, (long long)S.n_rows,
+                       model_traits(S.D.model).rt ? 1 : 0, dFit.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(S.stream));
+    unsigned long long n_coarse = 0;
+    if (int rc = coarse.count(S.stream, &n_coarse)) return rc;
+    HIPCHK(hipMemcpy(fit, dFit.p, (size_t)J * IFIT_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)n_coarse; }
     return 0;
 }
 // Plausible values (erm_pv_kernels.hpp; include/ertirt.h: erm_get_plausible_values, erm_plausible_values): the one place that launches pv_kernel.  The subjects

@@ -24,6 +24,7 @@
 #include "erm_psis_kernels.hpp"            // marginal PSIS-LOO: Pareto-smoothed leave-one-subject-out from marginal_kernel's l
 #include "erm_score_kernels.hpp"           // scores of respondents: posterior moments of theta and zeta, from the item trace
 #include "erm_fit_kernels.hpp"             // person fit: lz and the response-time chi^2 of every respondent, from the item trace
+#include "erm_ifit_kernels.hpp"            // item fit and drift: infit, outfit and the signed residuals of every item, from the item trace
 #include "erm_pv_kernels.hpp"              // plausible values: draws of theta and zeta from each subject's posterior, from the item trace
 #include "erm_farm_diag.hpp"               // the chain farm's joint diagnostics: chunk arithmetic
 #include "erm_geometry.hpp"
@@ -1784,7 +1785,15 @@ template <typename H> static int get_person_fit(H h, int32_t n_nodes, double* fi
     if (int rc = item_source(h, PASS_FIT, S)) return rc;
     return item_fit(S, Q, SCORE_EQUAL, fit, out4);
 }
-template <typename H> static int get_plausible_values(H h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
+template <typename H> static int get_item_fit(H h, int32_t n_nodes, double* fit, double* out4)
+{
+    int Q = 0;
+    ItemSource S;
+    if (int rc = item_entry_args(fit, n_nodes, &Q)) return rc;
+    if (int rc = item_source(h, PASS_ITEM_FIT, S)) return rc;
+    return item_itemfit(S, Q, fit, out4);
+}
+template <typename H> static int get_plausible_values(H h,int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
     int Q = 0;
     ItemSource S;
@@ -1842,6 +1851,7 @@ int erm_get_quantile_marginal_waic(erm_handle h, int32_t n_nodes, double* out10,
 int erm_get_quantile_marginal_loo(erm_handle h, int32_t n_nodes, double* out12, double* pw) { CHK_H; return get_marginal_loo(h, n_nodes, out12, pw, FAMILY_QUANTILE); }
 int erm_get_scores(erm_handle h, int32_t n_nodes, double* score, double* out4) { CHK_H; return get_scores(h, n_nodes, score, out4); }
 int erm_get_person_fit(erm_handle h, int32_t n_nodes, double* fit, double* out4) { CHK_H; return get_person_fit(h, n_nodes, fit, out4); }
+int erm_get_item_fit(erm_handle h, int32_t n_nodes, double* fit, double* out4) { CHK_H; return get_item_fit(h, n_nodes, fit, out4); }
 int erm_get_plausible_values(erm_handle h, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
     CHK_H;
@@ -2063,6 +2073,7 @@ int erm_farm_get_quantile_marginal_waic(erm_farm_handle f, int32_t n_nodes, doub
 int erm_farm_get_quantile_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw) { CHK_F; return get_marginal_loo(f, n_nodes, out12, pw, FAMILY_QUANTILE); }
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4) { CHK_F; return get_scores(f, n_nodes, score, out4); }
 int erm_farm_get_person_fit(erm_farm_handle f, int32_t n_nodes, double* fit, double* out4) { CHK_F; return get_person_fit(f, n_nodes, fit, out4); }
+int erm_farm_get_item_fit(erm_farm_handle f, int32_t n_nodes, double* fit, double* out4) { CHK_F; return get_item_fit(f, n_nodes, fit, out4); }
 int erm_farm_get_plausible_values(erm_farm_handle f, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
     CHK_F;
@@ -2242,6 +2253,20 @@ int erm_person_fit_masked(int device, int model, int64_t n_subj, int32_t n_item,
     if (int rc = item_source("erm_person_fit_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN,
                              0.0, obs, n_obs)) return rc;
     return item_fit(S, Q, weighting, fit, out4);
+}
+
+// ---- item fit on caller-supplied data and rows; obs may be NULL (complete data: the unmasked kernel)
+int erm_item_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                 const double* rows, int64_t n_rows, int32_t n_nodes, double* fit, double* out4)
+{
+    if (int rc = marg_refuse_model(model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (!fit) return fail(ERM_ERR_ARG, "out is NULL");
+    ItemSource S;
+    if (int rc = item_source("erm_item_fit's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN, 0.0,
+                             obs, nullptr)) return rc;
+    return item_itemfit(S, Q, fit, out4);
 }
 
 int erm_debug_invwishart(int device, uint64_t seed, uint32_t sweep, int64_t n, double nu, const double* psi4, double* out)

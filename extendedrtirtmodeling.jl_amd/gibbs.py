@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import InputPara, OutputDic, OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions
+from .base import InputPara, OutputDic, OutputItemFit, OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic, SimConditions
 
 _PREC = {"f32": _lib.PREC_F32, "f64": _lib.PREC_F64}
 _TRACE = {"summary": _lib.TRACE_SUMMARY, "full": _lib.TRACE_FULL}
@@ -710,6 +710,34 @@ def personFit(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting="equ
     w = _lib.score_weighting(weighting)
     Y, logT = _masked_data(Y, logT, obs)
     return _fit_output(_lib.person_fit(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), weighting=w, device=device, obs=obs), "likelihood" if w else "equal")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Item fit and drift (include/ertirt.h: erm_get_item_fit).  Per item infit, outfit, a signed response residual, a response-time mean square and a
+# signed response-time residual: the person fit's cells summed over the subjects instead of the items.  Deterministic; equal row weights.
+# ------------------------------------------------------------------------------------------------------------------
+def _item_fit_output(r) -> OutputItemFit:
+    return OutputItemFit(infit=r["infit"], outfit=r["outfit"], respZ=r["respZ"], rtMsq=r["rtMsq"], rtZ=r["rtZ"], nObs=r["nObs"], nRows=r["nRows"], nNodes=r["nNodes"],
+                         nCoarse=r["nCoarse"], nSubj=r["nSubj"])
+
+
+def getItemFit(MCMC: _GibbsBase, nodes=_lib.MARGINAL_NODES) -> OutputItemFit:
+    """Item fit of the last sample! -- of one engine or of the chain farm of sample!(...; devices=) -- computed on the device from the resident item trace and data
+    set (erm_get_item_fit / erm_farm_get_item_fit), in either trace mode: infit, outfit, respZ, rtMsq, rtZ, nObs per item.  On the calibration sample itself a
+    misfit that a free a_j or sig2t_j absorbs does not show: check a second sample with itemFit.  nodes: as getWaicMarginal's."""
+    Q = _marginal_check(MCMC, nodes, "getItemFit")
+    return _item_fit_output(_marginal_source(MCMC, "getItemFit").item_fit(Q))
+
+
+def itemFit(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, device=0, obs=None) -> OutputItemFit:
+    """Item fit and drift of a sample -- a new one, or one that is no longer resident -- against saved item-trace rows [R, item_trace_width]
+    (Engine.item_trace()), on the device (erm_item_fit); the arguments are scoreRespondents' without the weighting (the rows count equally).  respZ below -3: the
+    item is harder for this sample than calibrated; rtZ above 3: slower.  obs [N, J], 0/1: respondents who did not see every item -- an item's sums run over the
+    respondents that saw it, nObs counts them, an item nobody saw gets NaN."""
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("itemFit serves the five models without quantile weights")
+    Y, logT = _masked_data(Y, logT, obs)
+    return _item_fit_output(_lib.item_fit(model, Y, logT, X, rows, nodes=_lib.marginal_nodes(nodes), device=device, obs=obs))
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ module ExtendedRtIrtModelingAMD
 using LinearAlgebra, Random
 
 export sample!, GibbsMlIrt, GibbsRtIrt, GibbsRtIrtCrossQr, GibbsRtIrtLatentQr, GibbsRtIrtQuantile, GibbsRtIrtNull, GibbsRtIrtCross,
-       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getWaicMarginalQr, getLooMarginalQr, quantileMarginalLogLik, getScores, scoreRespondents, getPersonFit, personFit, getPlausibleValues, drawPlausibleValues, observedMask, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
+       GibbsRtIrtLatent, essRhat, rankEssRhat, rankEssRhatDraws, simulateData!, libertirt_path!, rcclUniqueId, getDicDevice, getWaicDevice, getWaicMarginal, marginalLogLik, getWaicMarginalQr, getLooMarginalQr, quantileMarginalLogLik, getScores, scoreRespondents, getPersonFit, personFit, getItemFit, itemFit, getPlausibleValues, drawPlausibleValues, observedMask, getLooMarginal, psisLoo, setPointwise!, getPpcDevice, setPredictive!, checkConvergenceDevice, setSeed!
 
 const LIB = Ref{String}(get(ENV, "LIBERTIRT", "libertirt.so"))
 libertirt_path!(p::AbstractString) = (LIB[] = String(p))
@@ -624,6 +624,50 @@ function personFit(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::M
                  Ptr{Int32}),
                 device, model, N, J, size(X, 2), Y, logT, X, obs, rows, size(rows, 2), nodes, w, fit, out, nObs))
     return fitTuple(fit, out, nObs)
+end
+
+# fit as erm_get_item_fit fills it (column-major [nItem][6], the ERM_IFIT_* columns) and out4 -> a named tuple
+itemFitTuple(fit::Matrix{Float64}, out::Vector{Float64}) =
+    (infit = fit[:, 1], outfit = fit[:, 2], respZ = fit[:, 3], rtMsq = fit[:, 4], rtZ = fit[:, 5], nObs = Int.(fit[:, 6]),
+     nSubj = Int(out[1]), nRows = Int(out[2]), nNodes = Int(out[3]), nCoarse = Int(out[4]))
+
+"""
+    getItemFit(MCMC; nodes = 61) -> (infit, outfit, respZ, rtMsq, rtZ, nObs, nSubj, nRows, nNodes, nCoarse)
+
+Item fit of the last `sample!`: per item the infit and outfit mean squares of the response residuals, the signed response residual `respZ` (negative: harder than
+calibrated), the mean square `rtMsq` of the leave-one-item-out response-time residual and its signed sum `rtZ` (positive: slower than calibrated), computed on the
+device from the resident item-level trace and data set (`erm_get_item_fit`; after `sample!(MCMC; devices=...)`, `erm_farm_get_item_fit`).  The two time columns are
+NaN for GibbsMlIrt.  Not for the two quantile models.  A misfit that a free a_j or σ²t_j absorbs does not show on the calibration sample: check a second sample
+with `itemFit`.
+"""
+function getItemFit(M::GibbsAMD; nodes::Integer = 61)
+    farmed = M.farm != C_NULL
+    farmed || M.handle != C_NULL || error("run sample! first")
+    fit, out = zeros(M.Cond.nItem, 6), zeros(4)
+    if farmed
+        check(ccall((:erm_farm_get_item_fit, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.farm, nodes, fit, out))
+    else
+        check(ccall((:erm_get_item_fit, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), M.handle, nodes, fit, out))
+    end
+    return itemFitTuple(fit, out)
+end
+
+"""
+    itemFit(model, Y, logT, X, rows; nodes = 61, device = 0, obs = nothing)
+
+`getItemFit` for a caller-supplied sample against saved item-trace rows, on the device (`erm_item_fit`): the drift check of a new sample against a saved
+calibration.  The arguments are `scoreRespondents`' without the weighting.  `obs` (UInt8 nSubj x nItem, 1 = the cell was administered): an item's sums run over
+the respondents that saw it, `nObs` counts them, an item nobody saw has NaN in the five statistics.
+"""
+function itemFit(model::Integer, Y::Matrix{UInt8}, logT::Matrix{Float64}, X::Matrix{Float64}, rows::Matrix{Float64}; nodes::Integer = 61, device::Integer = 0,
+                 obs::Union{Nothing,Matrix{UInt8}} = nothing)
+    N, J = size(Y)
+    obs === nothing || size(obs) == (N, J) || error("obs does not match Y")
+    fit, out = zeros(J, 6), zeros(4)
+    check(ccall((:erm_item_fit, LIB[]), Cint,
+                (Cint, Cint, Int64, Int32, Int32, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}),
+                device, model, N, J, size(X, 2), Y, logT, X, obs === nothing ? C_NULL : obs, rows, size(rows, 2), nodes, fit, out))
+    return itemFitTuple(fit, out)
 end
 
 # pv as erm_get_plausible_values fills it (column-major [nSubj][K][2]), node [nSubj][K], coarse [nSubj] and out4 -> a named tuple

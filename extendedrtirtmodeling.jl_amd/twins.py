@@ -7,7 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .base import OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic
+from .base import OutputItemFit, OutputLoo, OutputPersonFit, OutputPpc, OutputPv, OutputScores, OutputWaic
 from .gibbs import MARGINAL_UNIT, _GibbsBase, _log1pexp, _marginal_check, _norm_logpdf, marginalRows
 
 
@@ -515,6 +515,91 @@ def personFitHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, weighting=
     if obs is not None:
         out.nObs = n.astype(np.int32)
     return (out, S) if with_S else out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Item fit and drift: itemFit's twin beside personFitHost, on _marginal_rows_host's law
+# ------------------------------------------------------------------------------------------------------------------
+def itemFitHost(model, Y, logT, X, rows, nodes=_lib.MARGINAL_NODES, obs=None, dtype=np.float64, with_cells=False, with_S=False) -> OutputItemFit:
+    """itemFit with numpy (the test twin of item_fit_kernel and its reduction), written beside personFitHost: the population law of every row from
+    _marginal_rows_host; then the definition of include/ertirt.h restated as masked sums -- at every node of an observed cell r, c, z^2 and the signed residual
+    e from eta, the leave-one-item-out response-time residual d from the subject's observed times, e_q from the same sums; the six means under the rule's weights
+    at the row; their equal-weight means over the rows; the sums over the subjects that observed the item.  obs (N, J), 0/1: the observed mask (the masked call
+    never reduces the data and calls itself).  dtype=np.longdouble: the same arithmetic in extended precision.  with_cells: also the (N, J, 6) table of the
+    per-cell means E[e], E[r^2], E[c], E[z^2], E[d], E[d^2] (0 at unobserved cells); with_S: also S (R, N), the rule's sum at every row."""
+    if model not in _lib.MARGINAL_MODELS:
+        raise ValueError("itemFitHost serves the five models without quantile weights")
+    Q = _lib.marginal_nodes(nodes)
+    t = _lib.MODEL_TRAITS[model]
+    f = dtype
+    O = np.ones(np.shape(Y), dtype=bool) if obs is None else _obs_mask(obs, np.shape(Y))
+    Yz = np.where(O, np.asarray(Y), 0)
+    ltz_in = np.where(O, np.asarray(logT, dtype=np.float64), 0.0) if t.rt else None
+    N, J = Yz.shape
+    rows2 = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    R = rows2.shape[0]
+    log2pi = np.log(2 * np.arccos(f(-1)))
+    h = f(12) / (Q - 1)
+    cells = np.zeros((N, J, 6), dtype=f)
+    S = np.empty((R, N), dtype=f)
+    step = 256                                                                                # subjects at a time: the (n, Q, J) arrays stay small
+    for k, ((_, z, law, _), row) in enumerate(zip(_marginal_rows_host(model, Yz, ltz_in, X, rows2, Q), rows2)):
+        mu, sd, m0, m1, v = law
+        a, b, lam, sg = (row[c * J:(c + 1) * J].astype(f) for c in range(4))
+        rho = row[4 * J:5 * J].astype(f) if t.rho else np.zeros(J, dtype=f)
+        z = z.astype(f)
+        vv = f(max(v, 0.0))
+        for lo in range(0, N, step):
+            sl = slice(lo, min(lo + step, N))
+            Of = O[sl].astype(f)
+            Oq = Of[:, None, :]
+            Yf = Yz[sl].astype(f)
+            y1 = (Yz[sl] == 1)[:, None, :]
+            n = O[sl].sum(axis=1)
+            th = np.asarray(mu, dtype=f)[sl, None] + f(sd) * z[None, :]                       # (n, Q)
+            eta = a[None, None, :] * (th[:, :, None] - b[None, None, :])                      # (n, Q, J)
+            ab = np.abs(eta)
+            tt = np.exp(-ab)
+            agree = y1 == (eta >= 0)
+            r = np.where(agree, tt / (1 + tt), 1 / (1 + tt))
+            c = tt / ((1 + tt) * (1 + tt))
+            z2 = np.where(agree, tt, np.exp(np.minimum(ab, f(700))))
+            sgn = 2 * Yf[:, None, :] - 1
+            e = np.log(h) - log2pi / 2 - z[None, :] ** 2 / 2 + np.sum(Oq * (Yf[:, None, :] * eta - (np.maximum(eta, 0) + np.log1p(tt))), axis=2)
+            vals = [sgn * r, r * r, c, z2]
+            if t.rt:
+                lt = ltz_in[sl].astype(f)
+                g = Of / sg[None, :]                                                          # (n, J): g_j at the observed cells, 0 elsewhere
+                u = lam[None, None, :] - rho[None, None, :] * th[:, :, None] - lt[:, None, :]
+                P, Rs, D = np.sum(g, axis=1)[:, None], np.sum(g[:, None, :] * u, axis=2), np.sum(g[:, None, :] * u * u, axis=2)
+                L = np.sum(Of * np.log(sg)[None, :], axis=1)[:, None]
+                m = (np.asarray(m0, dtype=f)[sl, None] if np.ndim(m0) else f(m0)) + f(m1) * th
+                e = e - n[:, None] * log2pi / 2 - L / 2 - np.log1p(vv * P) / 2 - (D + (P * m * m - 2 * Rs * m - vv * Rs * Rs) / (1 + vv * P)) / 2
+                gj = (1 / sg)[None, None, :]
+                Pi = 1 + vv * (P[:, :, None] - gj)
+                with np.errstate(invalid="ignore", divide="ignore"):                          # (an unobserved cell's g_j is not in P: its values are dropped below)
+                    d = -(u - (m[:, :, None] + vv * (Rs[:, :, None] - gj * u)) / Pi) / np.sqrt(sg[None, None, :] + vv / Pi)
+                vals += [d, d * d]
+            M = np.max(e, axis=1, keepdims=True)
+            p = np.exp(e - M)
+            s = np.sum(p, axis=1)
+            S[k, sl] = s
+            w = (p / s[:, None])[:, :, None]
+            for col, val in enumerate(vals):
+                cells[sl, :, col] += np.where(O[sl], np.sum(w * val, axis=1), f(0))
+    cells /= R
+    sums = cells.sum(axis=0)                                                                  # (J, 6)
+    n_j = O.sum(axis=0).astype(f)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nan = np.full(J, np.nan)
+        on = n_j > 0
+        pick = lambda val, ok=True: np.where(on, val, nan).astype(np.float64) if ok else nan
+        coarse = np.any(S < 2.0, axis=0)
+        out = OutputItemFit(infit=pick(sums[:, 1] / sums[:, 2]), outfit=pick(sums[:, 3] / n_j), respZ=pick(sums[:, 0] / np.sqrt(sums[:, 2])),
+                            rtMsq=pick(sums[:, 5] / n_j, t.rt), rtZ=pick(sums[:, 4] / np.sqrt(n_j), t.rt), nObs=O.sum(axis=0).astype(np.int64), nRows=R, nNodes=Q,
+                            nCoarse=int(np.sum(coarse)), nSubj=N)
+    extra = ([cells] if with_cells else []) + ([S] if with_S else [])
+    return (out, *extra) if extra else out
 
 
 def pvRow(k, K, n_rows):

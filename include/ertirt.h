@@ -449,13 +449,57 @@ int erm_plausible_values_masked(int device, int model, int64_t n_subj, int32_t n
  *   same over the farm's chain-major table on chain 0's device.
  * erm_person_fit: the same kernel on caller-supplied data and rows, validated as erm_score validates them; n_rows >= 1; an unknown weighting: ERM_ERR_ARG.
  * erm_person_fit_masked: erm_person_fit with the observed mask of erm_score_masked, with its validation and its n_obs; obs == NULL calls erm_person_fit.
- * Out of scope: the quantile models, separate response and time masks, a joint p-value, item-level fit. */
+ * Out of scope: the quantile models, separate response and time masks, a joint p-value. */
 enum { ERM_FIT_LZ = 0, ERM_FIT_P_RESP = 1, ERM_FIT_LTZ = 2, ERM_FIT_P_TIME = 3, ERM_FIT_ROW_ESS = 4, ERM_FIT_COARSE = 5, ERM_FIT_COLS = 6 };
 int erm_get_person_fit(erm_handle h, int32_t n_nodes, double* fit, double* out4);
 int erm_person_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                    int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4);
 int erm_person_fit_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
                           const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4, int32_t* n_obs);
+
+/* Item fit and drift: whether saved item parameters still hold for a sample -- the fitted one or, above all, a NEW one scored against a saved calibration (a leaked
+ * item that has become easier and faster, a translated item that behaves differently, an item whose times drift at the end of a booklet).  Per item: infit and outfit
+ * mean squares, a signed response residual, a response-time mean square and a signed response-time residual, from the item-level trace alone.  Deterministic;
+ * computed AFTER the run from resident state, in both trace modes; the calls only read the engine.  Served: the five models of erm_get_marginal_waic; the two quantile
+ * models are refused with ERM_ERR_ARG for its reason.
+ * Definition.  Subject i, row s, O_i the observed items.  For an observed cell (i, j) at node theta_q the law (mu, sd, m0, m1, v; v clamped at 0, m = m0 + m1 theta_q),
+ * the node rule, e_q, M, S, w_q = exp(e_q - M) / S and the item sums P, R0, R1 are erm_get_person_fit's unchanged: (M, S) and COARSE are the marginal WAIC's bit for bit.
+ *   responses          eta = a_j (theta_q - b_j), t = e^-|eta|;  "agree" means (y = 1) <=> (eta >= 0).
+ *                      r = t / (1 + t) if agree, else 1 / (1 + t)  (= |y - p|);   c = t / (1 + t)^2  (= p (1 - p));
+ *                      z^2 = t if agree, else exp(min(|eta|, 700))  (= r^2 / c without the cancellation; the clamp keeps every term finite -- the library clamps
+ *                      |eta| inside t as well, which moves r and c by less than 1e-304);   signed residual e = (2 y - 1) r.
+ *   response times (models with times)   u = lambda_j - rho_j theta_q - logT_ij, g = 1 / sig2t_j, R = R0 - theta_q R1.  The residual is the leave-one-item-out
+ *                      prediction given theta and the subject's OTHER observed times, with zeta integrated out:
+ *                        Pi = 1 + v (P - g),   m_ = (m + v (R - g u)) / Pi,   v_ = v / Pi,   d = -(u - m_) / sqrt(sig2t_j + v_).
+ *                      Positive d: slower than predicted; d^2 is exactly chi^2_1 given theta.  The form has no 1 / v: v = 0 is an ordinary case.  (The marginal
+ *                      residual (u - m)^2 / (sig2t + v) is less sharp: on an item whose time variance was quadrupled it read 2.4 .. 2.9 where this reads 3.6 .. 4.1.)
+ *   per cell           six posterior means under w_q: E[e], E[r^2], E[c], E[z^2], E[d], E[d^2]; averaged over the rows with EQUAL weights, in trace order.  There is no
+ *                      likelihood weighting (the normaliser of a subject's row weights is known only after the last row), so the entries take no weighting.
+ *   per item           sums over the subjects i with j in O_i, n_j their count:
+ *                        ERM_IFIT_INFIT   = sum E[r^2] / sum E[c]        mean square, about 1
+ *                        ERM_IFIT_OUTFIT  = sum E[z^2] / n_j             mean square, outlier-sensitive (long upper tail on very easy or very hard items)
+ *                        ERM_IFIT_RESP_Z  = sum E[e] / sqrt(sum E[c])    signed; negative = harder than calibrated
+ *                        ERM_IFIT_RT_MSQ  = sum E[d^2] / n_j             about 1
+ *                        ERM_IFIT_RT_Z    = sum E[d] / sqrt(n_j)         signed; positive = slower than calibrated
+ *                        ERM_IFIT_N_OBS   = n_j
+ * Output: fit, column-major [n_item][ERM_IFIT_COLS].  out4 (may be NULL) = { n_subj, n_rows, Q, number of coarse subjects }.  GibbsMlIrt gets NaN in the two RT columns;
+ *   an item nobody observed (n_j = 0) gets NaN in the five statistics.  Everything is fp64 whatever the engine's precision.  Nothing is atomic: every word of the
+ *   per-cell workspace has one writer, and the sums over the subjects have one order -- blocks of 256 consecutive subjects by global index, each by a fixed binary tree
+ *   (absent subjects count 0), then the block sums in rising block order -- so results are bit-reproducible from call to call and do not depend on the chunking.
+ * Reading.  The mean squares alone do not find drift reliably (a difficulty shifted by one logit left infit between 0.89 and 1.42); the signed columns do.  A misfit
+ *   that a free a_j or sig2t_j can absorb -- a coin-toss item fitted with a about 0 -- leaves every column near its null value when the item is checked on its own
+ *   calibration sample: that is inherent to a 2PL.  Check a second sample against the saved rows (erm_item_fit).
+ * erm_get_item_fit: the post-burn-in rows of the resident item trace, read in place.  n_nodes and the refusals as erm_get_person_fit's (a shard, no data set, a failed
+ *   run, no post-burn-in row: ERM_ERR_STATE, the words name "the item fit"); ONE post-burn-in row is enough.  erm_farm_get_item_fit (below): the same over the farm's
+ *   chain-major table on chain 0's device.
+ * erm_item_fit: the same kernels on caller-supplied data and rows, validated as erm_person_fit_masked validates them; n_rows >= 1.  obs may be NULL: complete data, the
+ *   unmasked kernel; obs of all ones gives its result bit for bit.
+ * Out of scope: the quantile models, likelihood row weights, separate response and time masks, standardised mean squares (ZSTD), group-wise DIF beyond one call per
+ *   group. */
+enum { ERM_IFIT_INFIT = 0, ERM_IFIT_OUTFIT = 1, ERM_IFIT_RESP_Z = 2, ERM_IFIT_RT_MSQ = 3, ERM_IFIT_RT_Z = 4, ERM_IFIT_N_OBS = 5, ERM_IFIT_COLS = 6 };
+int erm_get_item_fit(erm_handle h, int32_t n_nodes, double* fit, double* out4);
+int erm_item_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                 const double* rows, int64_t n_rows, int32_t n_nodes, double* fit, double* out4);
 
 /* Marginal PSIS-LOO: Pareto-smoothed importance-sampling leave-one-subject-out (Vehtari, Gelman and Gabry 2017; Vehtari, Simpson, Gelman, Yao and Gabry 2024), the
  * criterion the "p_u > 0.4" count of erm_get_waic / erm_get_marginal_waic sends its reader to, and with it a Pareto k^ per respondent: for which respondents the
@@ -586,6 +630,7 @@ int erm_farm_get_dic(erm_farm_handle f, double* out4);     /* as erm_get_dic: Db
 int erm_farm_get_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* the marginal WAIC over the rows of all chains: see erm_get_marginal_waic */
 int erm_farm_get_scores(erm_farm_handle f, int32_t n_nodes, double* score, double* out4);                          /* the scores over the rows of all chains: see erm_get_scores */
 int erm_farm_get_person_fit(erm_farm_handle f, int32_t n_nodes, double* fit, double* out4);                        /* the person fit over the rows of all chains: see erm_get_person_fit */
+int erm_farm_get_item_fit(erm_farm_handle f, int32_t n_nodes, double* fit, double* out4);                          /* the item fit over the rows of all chains: see erm_get_item_fit */
 int erm_farm_get_quantile_marginal_waic(erm_farm_handle f, int32_t n_nodes, double* out10, double* lppd_u, double* p_u);   /* LatentQr: see erm_get_quantile_marginal_waic */
 int erm_farm_get_quantile_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* LatentQr: see erm_get_quantile_marginal_waic */
 int erm_farm_get_marginal_loo(erm_farm_handle f, int32_t n_nodes, double* out12, double* pw);                        /* the marginal PSIS-LOO over the rows of all chains: see erm_get_marginal_loo */
