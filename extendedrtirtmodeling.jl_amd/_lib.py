@@ -292,54 +292,41 @@ def score_weighting(weighting):
     raise ValueError('weighting must be "equal" or "likelihood"')
 
 
-def _score_result(score, out):
-    """score as the library fills it, (7, n_subj) C-ordered = column-major [n_subj][7], and out4 -> a dict of the columns with nSubj, nRows, nNodes, nCoarse."""
-    res = {name: score[k] for k, name in enumerate(SCORE_COLUMNS)}
-    res["coarse"] = score[6] != 0.0
-    res.update(nSubj=int(out[0]), nRows=int(out[1]), nNodes=int(out[2]), nCoarse=int(out[3]))
-    return res
-
-
-def _score_call(fn, h, nodes, n_subj):
-    score, out = np.empty((len(SCORE_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
-    check(fn(h, marginal_nodes(nodes), score.ctypes.data, out.ctypes.data))
-    return _score_result(score, out)
-
-
 # erm_get_person_fit / erm_farm_get_person_fit / erm_person_fit: the columns of fit [n_subj][6] (ERM_FIT_*); the weightings are the scores'
 FIT_COLUMNS = ("lz", "pResp", "ltz", "pTime", "rowEss", "coarse")
-
-
-def _fit_result(fit, out):
-    """fit as the library fills it, (6, n_subj) C-ordered = column-major [n_subj][6], and out4 -> a dict of the columns with nSubj, nRows, nNodes, nCoarse."""
-    res = {name: fit[k] for k, name in enumerate(FIT_COLUMNS)}
-    res["coarse"] = fit[5] != 0.0
-    res.update(nSubj=int(out[0]), nRows=int(out[1]), nNodes=int(out[2]), nCoarse=int(out[3]))
-    return res
-
-
-def _fit_call(fn, h, nodes, n_subj):
-    fit, out = np.empty((len(FIT_COLUMNS), n_subj), dtype=np.float64), np.empty(4, dtype=np.float64)
-    check(fn(h, marginal_nodes(nodes), fit.ctypes.data, out.ctypes.data))
-    return _fit_result(fit, out)
 
 
 # erm_get_item_fit / erm_farm_get_item_fit / erm_item_fit: the columns of fit [n_item][6] (ERM_IFIT_*)
 IFIT_COLUMNS = ("infit", "outfit", "respZ", "rtMsq", "rtZ", "nObs")
 
 
-def _item_fit_result(fit, out):
-    """fit as the library fills it, (6, n_item) C-ordered = column-major [n_item][6], and out4 -> a dict of the columns with nSubj, nRows, nNodes, nCoarse."""
-    res = {name: fit[k] for k, name in enumerate(IFIT_COLUMNS)}
-    res["nObs"] = fit[5].astype(np.int64)
+# The three passes whose product is one table [n][columns]: the columns, the config field that sizes the table, what the last column -- a count or a flag
+# carried as a double -- becomes in the dict, and whether the caller-data entry takes a weighting of the rows
+PassTable = namedtuple("PassTable", "columns size last weighted")
+PASS_TABLES = MappingProxyType({
+    "scores": PassTable(SCORE_COLUMNS, "n_subj", lambda flag: flag != 0.0, True),
+    "person_fit": PassTable(FIT_COLUMNS, "n_subj", lambda flag: flag != 0.0, True),
+    "item_fit": PassTable(IFIT_COLUMNS, "n_item", lambda count: count.astype(np.int64), False),
+})
+
+
+def _table_buffers(name, n):
+    return np.empty((len(PASS_TABLES[name].columns), n), dtype=np.float64), np.empty(4, dtype=np.float64)
+
+
+def _table_result(name, table, out):
+    """table as the library fills it, (columns, n) C-ordered = column-major [n][columns], and out4 -> a dict of the columns with nSubj, nRows, nNodes, nCoarse."""
+    t = PASS_TABLES[name]
+    res = {column: table[k] for k, column in enumerate(t.columns)}
+    res[t.columns[-1]] = t.last(table[-1])
     res.update(nSubj=int(out[0]), nRows=int(out[1]), nNodes=int(out[2]), nCoarse=int(out[3]))
     return res
 
 
-def _item_fit_call(fn, h, nodes, n_item):
-    fit, out = np.empty((len(IFIT_COLUMNS), n_item), dtype=np.float64), np.empty(4, dtype=np.float64)
-    check(fn(h, marginal_nodes(nodes), fit.ctypes.data, out.ctypes.data))
-    return _item_fit_result(fit, out)
+def _table_call(name, fn, h, nodes, cfg):
+    table, out = _table_buffers(name, getattr(cfg, PASS_TABLES[name].size))
+    check(fn(h, marginal_nodes(nodes), table.ctypes.data, out.ctypes.data))
+    return _table_result(name, table, out)
 
 
 # erm_get_plausible_values / erm_farm_get_plausible_values / erm_plausible_values: the number of draws, the seed, and the outputs
@@ -456,7 +443,7 @@ class _Diagnostics:
 
 
 class _ItemPasses:
-    """The five passes over the item trace of an Engine (erm_get_*: its resident data set and its own post-burn-in rows) and of a Farm (erm_farm_get_*: the
+    """The six passes over the item trace of an Engine (erm_get_*: its resident data set and its own post-burn-in rows) and of a Farm (erm_farm_get_*: the
     post-burn-in rows of all chains -- chain 0's, then chain 1's, ... -- on chain 0's device and data set).  One implementation, keyed by `_get_prefix`."""
 
     def _pass(self, name: str):
@@ -489,19 +476,19 @@ class _ItemPasses:
     def scores(self, nodes=MARGINAL_NODES):
         """erm_get_scores / erm_farm_get_scores: every subject's posterior mean and sd of theta and zeta, their covariance and the rows' effective size, computed on
         the device from the resident item trace after the run (equal weights).  A dict of SCORE_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
-        return _score_call(self._pass("scores"), self._h, nodes, self.cfg.n_subj)
+        return _table_call("scores", self._pass("scores"), self._h, nodes, self.cfg)
 
     def person_fit(self, nodes=MARGINAL_NODES):
         """erm_get_person_fit / erm_farm_get_person_fit: every subject's lz with its normal p-value, the Wilson-Hilferty z of the response-time quadratic form with
         its exact chi^2 p-value, and the rows' effective size, computed on the device from the resident item trace after the run (equal weights).  A dict of
         FIT_COLUMNS [n_subj] with nSubj, nRows, nNodes, nCoarse."""
-        return _fit_call(self._pass("person_fit"), self._h, nodes, self.cfg.n_subj)
+        return _table_call("person_fit", self._pass("person_fit"), self._h, nodes, self.cfg)
 
     def item_fit(self, nodes=MARGINAL_NODES):
         """erm_get_item_fit / erm_farm_get_item_fit: every item's infit, outfit, signed response residual, response-time mean square and signed response-time
         residual with the number of subjects that observed it, computed on the device from the resident item trace after the run (equal weights).  A dict of
         IFIT_COLUMNS [n_item] with nSubj, nRows, nNodes, nCoarse."""
-        return _item_fit_call(self._pass("item_fit"), self._h, nodes, self.cfg.n_item)
+        return _table_call("item_fit", self._pass("item_fit"), self._h, nodes, self.cfg)
 
     def plausible_values(self, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES):
         """erm_get_plausible_values / erm_farm_get_plausible_values: K draws of every subject's (theta, zeta) from its posterior given the resident item trace,
@@ -869,13 +856,13 @@ def _caller_data(model, Y, logT, X, rows):
     return (Yf, lt, xx, rr), (N, J, F, rr.shape[0])
 
 
-def _caller_head(device, model, arrays, dims, obs=None):
-    """The leading arguments of the three entries: device, model, N, J, F, Y, logT, X, rows, R (the arrays stay the caller's to keep alive); with obs (_caller_obs),
-    those of their masked siblings: obs stands between X and rows."""
+def _caller_head(device, model, arrays, dims, obs=None, slot=False):
+    """The leading arguments of the caller-data entries: device, model, N, J, F, Y, logT, X, rows, R (the arrays stay the caller's to keep alive); with obs
+    (_caller_obs), those of their masked siblings: obs stands between X and rows.  slot: the entry has that argument for complete data too (NULL)."""
     N, J, F, R = dims
     ptr = [None if a is None else a.ctypes.data for a in arrays]
-    if obs is not None:
-        ptr.insert(3, obs.ctypes.data)
+    if obs is not None or slot:
+        ptr.insert(3, None if obs is None else obs.ctypes.data)
     return (int(device), int(model), N, J, F, *ptr, R)
 
 
@@ -887,22 +874,42 @@ def _caller_obs(obs, N, J):
     return O, np.empty(N, dtype=np.int32)
 
 
+def _caller_entry(name, device, model, arrays, dims, obs, single=False):
+    """The obs / no-obs fork of a caller-data pass -> (call, extra).  call(*tail) is the entry `name` (obs None: complete data) or name + "_masked", with
+    _caller_head's arguments in front of tail and the masked entry's n_obs behind it; extra is what obs adds to the result, nObs [N].  single (erm_item_fit): one
+    entry serves both, obs or NULL, and reports no n_obs.  Only a name that has a "_masked" sibling may come with obs (the quantile family has none)."""
+    O, n_obs = (None, None) if obs is None else _caller_obs(obs, dims[0], dims[1])
+    head = _caller_head(device, model, arrays, dims, O, slot=single)
+    reports = obs is not None and not single
+    fn = getattr(load(), name + "_masked" if reports else name)
+    last = (n_obs.ctypes.data,) if reports else ()
+
+    def call(*tail):
+        keep = O      # head holds only the address of the mask: naming the array here keeps it alive for as long as call can be made
+        return fn(*head, *tail, *last)
+    return call, (dict(nObs=n_obs) if reports else {})
+
+
+def _caller_table(name, entry, model, Y, logT, X, rows, device, obs, nodes, weighting="equal", single=False):
+    """A pass of PASS_TABLES on caller-supplied data: entry(head, nodes[, weighting], table, out4[, n_obs])."""
+    arrays, dims = _caller_data(model, Y, logT, X, rows)
+    table, out = _table_buffers(name, dims[0] if PASS_TABLES[name].size == "n_subj" else dims[1])
+    call, extra = _caller_entry(entry, device, model, arrays, dims, obs, single)
+    check(call(marginal_nodes(nodes), *((score_weighting(weighting),) if PASS_TABLES[name].weighted else ()), table.ctypes.data, out.ctypes.data))
+    return dict(_table_result(name, table, out), **extra)
+
+
 def _family_loglik(family, model, Y, logT, X, rows, scalars, nodes, want_l, want_waic, device, obs=None):
-    """The caller-data entry of a family of MARGINAL_FAMILIES, with the family's scalars in the table's order; obs: the Gaussian family's masked sibling."""
+    """The caller-data entry of a family of MARGINAL_FAMILIES, with the family's scalars in the table's order; obs: the Gaussian family's masked sibling (the quantile family has
+    none, and quantile_marginal_loglik takes no obs)."""
     arrays, (N, J, F, R) = _caller_data(model, Y, logT, X, rows)
     l = np.empty((N, R), dtype=np.float64, order="F") if want_l else None
     out = np.empty(10, dtype=np.float64) if want_waic else None
     lppd, p = (np.empty(N), np.empty(N)) if want_waic else (None, None)
     ptr = lambda a: None if a is None else a.ctypes.data
-    if obs is None:
-        fn = getattr(load(), MARGINAL_FAMILIES[family].loglik)
-        check(fn(*_caller_head(device, model, arrays, (N, J, F, R)), *(float(s) for s in scalars), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
-        res = dict(l=l)
-    else:
-        O, n_obs = _caller_obs(obs, N, J)
-        check(load().erm_marginal_loglik_masked(*_caller_head(device, model, arrays, (N, J, F, R), O), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p),
-                                                n_obs.ctypes.data))
-        res = dict(l=l, nObs=n_obs)
+    call, extra = _caller_entry(MARGINAL_FAMILIES[family].loglik, device, model, arrays, (N, J, F, R), obs)
+    check(call(*(float(s) for s in scalars), marginal_nodes(nodes), ptr(l), ptr(out), ptr(lppd), ptr(p)))
+    res = dict(l=l, **extra)
     if want_waic:
         res.update(totals=_marginal_result(out, None, None), lppd=lppd, p=p)
     return res
@@ -924,46 +931,20 @@ def score(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", d
     """erm_score: the scores' kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as Engine.item_trace()
     returns them, R >= 1; weighting "equal" | "likelihood".  Returns Engine.scores' dict.  obs [N, J], 0/1 (None: complete, erm_score): erm_score_masked on
     incomplete patterns; the dict then has nObs [N]."""
-    arrays, dims = _caller_data(model, Y, logT, X, rows)
-    N = dims[0]
-    sc, out = np.empty((len(SCORE_COLUMNS), N), dtype=np.float64), np.empty(4, dtype=np.float64)
-    if obs is None:
-        check(load().erm_score(*_caller_head(device, model, arrays, dims), marginal_nodes(nodes), score_weighting(weighting), sc.ctypes.data, out.ctypes.data))
-        return _score_result(sc, out)
-    O, n_obs = _caller_obs(obs, N, dims[1])
-    check(load().erm_score_masked(*_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes), score_weighting(weighting), sc.ctypes.data, out.ctypes.data,
-                                  n_obs.ctypes.data))
-    return dict(_score_result(sc, out), nObs=n_obs)
+    return _caller_table("scores", "erm_score", model, Y, logT, X, rows, device, obs, nodes, weighting)
 
 
 def person_fit(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, weighting="equal", device=0, obs=None):
     """erm_person_fit: the person fit's kernel on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
     Engine.item_trace() returns them, R >= 1; weighting "equal" | "likelihood".  Returns Engine.person_fit's dict.  obs [N, J], 0/1 (None: complete,
     erm_person_fit): erm_person_fit_masked on incomplete patterns; the dict then has nObs [N]."""
-    arrays, dims = _caller_data(model, Y, logT, X, rows)
-    N = dims[0]
-    ft, out = np.empty((len(FIT_COLUMNS), N), dtype=np.float64), np.empty(4, dtype=np.float64)
-    if obs is None:
-        check(load().erm_person_fit(*_caller_head(device, model, arrays, dims), marginal_nodes(nodes), score_weighting(weighting), ft.ctypes.data, out.ctypes.data))
-        return _fit_result(ft, out)
-    O, n_obs = _caller_obs(obs, N, dims[1])
-    check(load().erm_person_fit_masked(*_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes), score_weighting(weighting), ft.ctypes.data,
-                                       out.ctypes.data, n_obs.ctypes.data))
-    return dict(_fit_result(ft, out), nObs=n_obs)
+    return _caller_table("person_fit", "erm_person_fit", model, Y, logT, X, rows, device, obs, nodes, weighting)
 
 
 def item_fit(model, Y, logT, X, rows, *, nodes=MARGINAL_NODES, device=0, obs=None):
     """erm_item_fit: the item fit's kernels on caller-supplied data (Y, logT [N, J], X [N, F] or None) and item-trace rows [R, item_trace_width] as
     Engine.item_trace() returns them, R >= 1.  Returns Engine.item_fit's dict.  obs [N, J], 0/1 (None: complete data, the unmasked kernel): incomplete patterns."""
-    arrays, dims = _caller_data(model, Y, logT, X, rows)
-    N, J = dims[0], dims[1]
-    ft, out = np.empty((len(IFIT_COLUMNS), J), dtype=np.float64), np.empty(4, dtype=np.float64)
-    O = None if obs is None else _caller_obs(obs, N, J)[0]
-    head = list(_caller_head(device, model, arrays, dims, O))
-    if O is None:
-        head.insert(8, None)                                  # obs = NULL between X and rows
-    check(load().erm_item_fit(*head, marginal_nodes(nodes), ft.ctypes.data, out.ctypes.data))
-    return _item_fit_result(ft, out)
+    return _caller_table("item_fit", "erm_item_fit", model, Y, logT, X, rows, device, obs, nodes, single=True)
 
 
 def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes=MARGINAL_NODES, device=0, obs=None):
@@ -971,11 +952,8 @@ def plausible_values(model, Y, logT, X, rows, *, K=PV_DRAWS, seed=PV_SEED, nodes
     Engine.item_trace() returns them, R >= 1.  Returns Engine.plausible_values' dict.  obs [N, J], 0/1 (None: complete, erm_plausible_values):
     erm_plausible_values_masked on incomplete patterns; the dict then has nObs [N]."""
     arrays, dims = _caller_data(model, Y, logT, X, rows)
-    if obs is None:
-        return _pv_call(load().erm_plausible_values, dims[0], K, seed, *_caller_head(device, model, arrays, dims), marginal_nodes(nodes))
-    O, n_obs = _caller_obs(obs, dims[0], dims[1])
-    fn = lambda *a: load().erm_plausible_values_masked(*a, n_obs.ctypes.data)
-    return dict(_pv_call(fn, dims[0], K, seed, *_caller_head(device, model, arrays, dims, O), marginal_nodes(nodes)), nObs=n_obs)
+    call, extra = _caller_entry("erm_plausible_values", device, model, arrays, dims, obs)
+    return dict(_pv_call(call, dims[0], K, seed, marginal_nodes(nodes)), **extra)
 
 
 def psis_loo(l, *, want_lw=False, device=0):

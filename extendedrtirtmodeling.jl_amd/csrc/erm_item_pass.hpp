@@ -1,15 +1,13 @@
-// erm_item_pass.hpp -- the host path of the passes that run after sampling from a data set and a table of item-trace rows: the marginal WAIC, the
-// marginal PSIS-LOO, the scores and the plausible values.  Each of erm_get_* / erm_farm_get_* (four each) and erm_marginal_loglik / erm_score / erm_plausible_values
-// is its own argument checks, ONE source maker (item_source) and ONE product call (item_waic / item_loo / item_scores / item_pv).  The five entries of LatentQr's
-// marginal WAIC and LOO (erm_get_quantile_marginal_* and erm_quantile_marginal_loglik) are the same makers and products for FAMILY_QUANTILE, and the
-// three masked entries (erm_marginal_loglik_masked / erm_score_masked / erm_plausible_values_masked) the caller-data maker with an observed mask.
-// The person fit is a fifth pass on the same makers with a product of its own, item_fit: erm_get_person_fit, erm_farm_get_person_fit,
-// erm_person_fit and erm_person_fit_masked.  The item fit is a sixth, with the product item_itemfit: erm_get_item_fit, erm_farm_get_item_fit and
-// erm_item_fit.
+// erm_item_pass.hpp -- the host path of the six passes that run after sampling from a data set and a table of item-trace rows: the marginal WAIC,
+// the marginal PSIS-LOO, the scores, the plausible values, the person fit (7n) and the item fit (7o).  A pass is ONE row of ITEM_PASSES, ONE product (item_waic /
+// item_loo / item_scores / item_pv / item_fit / item_itemfit) and, per kind of source, ONE entry body in ertirt.hip: its argument checks, the source maker
+// (item_source: an engine, a farm, or caller data with or without an observed mask) and the product call.  LatentQr's marginal WAIC and LOO
+//  are the same makers and products for FAMILY_QUANTILE.
 //
 // The first half is plain C++: the facts of a pass as one table, the refusals built from it and the chunk rule; g++ compiles this half with
 // -fsanitize=undefined -ftrapv into tests/item_pass_check (tests/test_item_pass_host.py).
-// The second half (hipcc only) is what the tile kernels share of a launch, the coarse flags, the resolved source with its three makers and the four products.
+// The second half (hipcc only) is what the tile kernels share of a launch, the coarse flags, the resolved source with its three makers, the tail the four table
+// products share (item_finish) and the products.
 // ertirt.hip includes this header where its DevBuf, fail / HIPCHK, pw_totals / pw_finish_on, EngineBase and the two handles are in scope.
 #pragma once
 #include <algorithm>
@@ -19,7 +17,7 @@
 
 namespace erm {
 
-enum ItemPass { PASS_WAIC = 0, PASS_LOO, PASS_SCORES, PASS_PV, N_ITEM_PASSES };
+enum ItemPass { PASS_WAIC = 0, PASS_LOO, PASS_SCORES, PASS_PV, PASS_FIT, PASS_ITEM_FIT, N_ITEM_PASSES };
 // the family of models an entry serves: the five without quantile weights (zeta's integral is Gaussian: erm_marginal.hpp), or LatentQr with nu integrated out
 // (erm_qmarginal.hpp: the marginal WAIC and LOO only)
 enum ItemFamily { FAMILY_GAUSSIAN = 0, FAMILY_QUANTILE };
@@ -31,23 +29,18 @@ constexpr ItemPassFacts ITEM_PASSES[N_ITEM_PASSES] = {
     { "the marginal LOO",     false, 0, 1, "post-burn-in rows (25 .. 8192 over the chains)" },
     { "the scores",           true,  1, 1, "at least one post-burn-in row" },
     { "the plausible values", true,  1, 1, "at least one post-burn-in row" },
+    { "the person fit",       false, 1, 1, "at least one post-burn-in row" },
+    { "the item fit",         false, 1, 1, "at least one post-burn-in row" },
 };
-// the fifth pass, the person fit, has its facts beside the table; every reader of a pass's facts goes through item_pass_facts
-constexpr int PASS_FIT = N_ITEM_PASSES;
-constexpr ItemPassFacts FIT_PASS_FACTS = { "the person fit", false, 1, 1, "at least one post-burn-in row" };
-// the sixth pass, the item fit, sits beside them in the same way
-constexpr int PASS_ITEM_FIT = N_ITEM_PASSES + 1;
-constexpr ItemPassFacts ITEM_FIT_PASS_FACTS = { "the item fit", false, 1, 1, "at least one post-burn-in row" };
-constexpr const ItemPassFacts& item_pass_facts(int pass) { return pass == PASS_ITEM_FIT ? ITEM_FIT_PASS_FACTS : pass == PASS_FIT ? FIT_PASS_FACTS : ITEM_PASSES[pass]; }
 inline std::string item_pass_on_shard(int pass)
 {
-    const ItemPassFacts& p = item_pass_facts(pass);
+    const ItemPassFacts& p = ITEM_PASSES[pass];
     return std::string(p.noun) + (p.plural ? " are" : " is") + " not available on a shard (every subject's data must be resident on one device)";
 }
 // too few rows: an engine's own (engine_rows > 0) and a farm chain's ("chain l: " in front)
 inline std::string item_pass_needs_rows(int pass)
 {
-    const ItemPassFacts& p = item_pass_facts(pass);
+    const ItemPassFacts& p = ITEM_PASSES[pass];
     return std::string(p.noun) + (p.plural ? " need " : " needs ") + p.need;
 }
 
@@ -259,7 +252,7 @@ static int item_source(erm_farm_handle f, int pass, ItemSource& S, int family = 
     for (int l = 0; l < L; ++l) {
         const EngineBase* e = f->eng[l]->e.get();
         if (e->rows_done != rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + std::to_string(e->rows_done) + " rows recorded where chain 0 has " + std::to_string(rows));
-        if (e->post_rows < item_pass_facts(pass).farm_rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + item_pass_needs_rows(pass));
+        if (e->post_rows < ITEM_PASSES[pass].farm_rows) return fail(ERM_ERR_STATE, "chain " + std::to_string(l) + ": " + item_pass_needs_rows(pass));
     }
     std::vector<double> table((size_t)L * post * wi);
     for (int l = 0; l < L; ++l) {
@@ -274,15 +267,17 @@ static int item_source(erm_farm_handle f, int pass, ItemSource& S, int family = 
     S.rows = S.dRows.as<double>(); S.n_rows = (int64_t)L * post;
     return item_source(f->eng[0].get(), pass, S, family);
 }
+// what every caller-data entry is given of a data set and its rows: Y, logT, X column-major as the ABI takes them, rows [n_rows][item-trace width]
+struct CallerData { int device, model; int64_t n_subj; int32_t n_item, n_feat; const uint8_t* Y; const double* logT; const double* X; const double* rows; int64_t n_rows; };
 // caller-supplied data and rows (erm_marginal_loglik, erm_score, erm_plausible_values): validated on the host, then uploaded to `device` row-major in fp64, as the
 // kernels read an engine's, for the NULL stream.  min_rows / rows_msg: the fewest rows the caller's outputs need.  FAMILY_QUANTILE (the model is LatentQr): q_rt is
 // the quantile level, and every row's Sigma_p[2,2], the scale of zeta's law, must be positive.
 // obs != NULL (the masked entries): the observed mask, column-major as Y.  The walk that validates the cells compacts them into erm_obs.hpp's lists,
 // which are uploaded in the place of the row-major Y and logT; Y and logT are read, and validated, at observed cells only; n_obs [n_subj] (may be NULL) receives n_i.
-static int item_source(const char* what, int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X,
-                       const double* rows, int64_t n_rows, int64_t min_rows, const char* rows_msg, ItemSource& S, int family = FAMILY_GAUSSIAN, double q_rt = 0.0,
+static int item_source(const char* what, const CallerData& d, int64_t min_rows, const char* rows_msg, ItemSource& S, int family = FAMILY_GAUSSIAN, double q_rt = 0.0,
                        const uint8_t* obs = nullptr, int32_t* n_obs = nullptr)
 {
+    const auto& [device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows] = d;
     const ModelTraits mt = model_traits(model);
     if (n_subj <= 0 || n_subj >= (1LL << 32) || n_item <= 0 || n_item > 896 || n_feat < 0 || n_feat > MARG_MAXF) return fail(ERM_ERR_ARG, "n_subj, n_item (1 .. 896) or n_feat (0 .. " + std::to_string(MARG_MAXF) + ") out of range");
     const int64_t N = n_subj; const int J = n_item, Fk = kernel_feat(model, n_feat);
@@ -361,7 +356,18 @@ static int item_source(const char* what, int device, int model, int64_t n_subj, 
     return 0;
 }
 
-// ---- The four products of a source.  The makers have refused a source with too few rows for the outputs asked for; all outputs are the caller's host arrays.
+// The tail of the scores, the person fit, the item fit and the plausible values: the count of the coarse flags, the pass's table to the caller (dst NULL: not
+// wanted) and out4 = {N, n_rows, Q, n_coarse} (may be NULL)
+static int item_finish(const ItemSource& S, int Q, const CoarseFlags& coarse, void* dst, const void* src, size_t bytes, double* out4)
+{
+    unsigned long long nc = 0;
+    if (int rc = coarse.count(S.stream, &nc)) return rc;
+    if (dst) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    if (out4) { out4[0] = (double)S.D.N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
+    return 0;
+}
+
+// ---- The products of a source.  The makers have refused a source with too few rows for the outputs asked for; all outputs are the caller's host arrays.
 // Marginal WAIC (erm_marginal_kernels.hpp; include/ertirt.h: erm_get_marginal_waic, erm_marginal_loglik): l [n_rows][N] (may be NULL), and the totals out10 with
 // lppd_u / p_u [N] (all three NULL: l alone)
 static int item_waic(const ItemSource& S, int Q, double* l, double* out10, double* lppd_u, double* p_u)
@@ -414,49 +420,34 @@ static int item_loo(const ItemSource& S, int Q, double* out12, double* pw)
     psis_out12(s8, N, S.n_rows, Q, (int64_t)nc, out12);
     return 0;
 }
-// Scores of respondents (erm_score_kernels.hpp; include/ertirt.h: erm_get_scores, erm_score): the one place that launches score_kernel; score [N][7]
-static int item_scores(const ItemSource& S, int Q, int weighting, double* score, double* out4)
+// The two per-subject tables, table [N][cols]: one launch of the tile kernel that kernel(model constant, real(), masked constant) picks, over all subjects.
+// `what` names the pass in the allocation messages.
+template <typename Pick>
+static int item_subject_table(const ItemSource& S, int Q, int cols, const char* what, Pick&& kernel, double* table, double* out4)
 {
     const int64_t N = S.D.N;
-    DevBuf dScore;
+    DevBuf dTable;
     CoarseFlags coarse;
-    const char* what = "the scores";
-    if (int rc = dScore.try_alloc((size_t)N * SCORE_COLS * sizeof(double), what)) return rc;
+    if (int rc = dTable.try_alloc((size_t)N * cols * sizeof(double), what)) return rc;
     if (int rc = coarse.alloc(N, what)) return rc;
     MargArgs a = marg_args(S.D, S.rows, S.n_rows, Q);
     a.coarse = coarse.flags();
-    auto launch = [&](auto M, auto real, auto masked) -> int {
-        if (weighting == SCORE_LIKELIHOOD) return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), true, decltype(masked)::value>, a, S.stream, dScore.as<double>());
-        return marg_tile_launch(&score_kernel<decltype(M)::value, decltype(real), false, decltype(masked)::value>, a, S.stream, dScore.as<double>());
-    };
-    if (int rc = marg_dispatch_obs(S.D, launch)) return rc;
-    unsigned long long nc = 0;
-    if (int rc = coarse.count(S.stream, &nc)) return rc;
-    HIPCHK(hipMemcpy(score, dScore.p, (size_t)N * SCORE_COLS * sizeof(double), hipMemcpyDeviceToHost));
-    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
-    return 0;
+    if (int rc = marg_dispatch_obs(S.D, [&](auto M, auto real, auto masked) { return marg_tile_launch(kernel(M, real, masked), a, S.stream, dTable.as<double>()); })) return rc;
+    return item_finish(S, Q, coarse, table, dTable.p, (size_t)N * cols * sizeof(double), out4);
+}
+// Scores of respondents (erm_score_kernels.hpp; include/ertirt.h: erm_get_scores, erm_score): the one place that launches score_kernel; score [N][7]
+static int item_scores(const ItemSource& S, int Q, int weighting, double* score, double* out4)
+{
+    return item_subject_table(S, Q, SCORE_COLS, "the scores", [&](auto M, auto real, auto masked) {
+        return weighting == SCORE_LIKELIHOOD ? &score_kernel<decltype(M)::value, decltype(real), true, decltype(masked)::value>
+                                             : &score_kernel<decltype(M)::value, decltype(real), false, decltype(masked)::value>; }, score, out4);
 }
 // Person fit (erm_fit_kernels.hpp; include/ertirt.h: erm_get_person_fit, erm_person_fit): the one place that launches fit_kernel; fit [N][6]
 static int item_fit(const ItemSource& S, int Q, int weighting, double* fit, double* out4)
 {
-    const int64_t N = S.D.N;
-    DevBuf dFit;
-    CoarseFlags coarse;
-    const char* what = "the person fit";
-    if (int rc = dFit.try_alloc((size_t)N * FIT_COLS * sizeof(double), what)) return rc;
-    if (int rc = coarse.alloc(N, what)) return rc;
-    MargArgs a = marg_args(S.D, S.rows, S.n_rows, Q);
-    a.coarse = coarse.flags();
-    auto launch = [&](auto M, auto real, auto masked) -> int {
-        if (weighting == SCORE_LIKELIHOOD) return marg_tile_launch(&fit_kernel<decltype(M)::value, decltype(real), true, decltype(masked)::value>, a, S.stream, dFit.as<double>());
-        return marg_tile_launch(&fit_kernel<decltype(M)::value, decltype(real), false, decltype(masked)::value>, a, S.stream, dFit.as<double>());
-    };
-    if (int rc = marg_dispatch_obs(S.D, launch)) return rc;
-    unsigned long long nc = 0;
-    if (int rc = coarse.count(S.stream, &nc)) return rc;
-    HIPCHK(hipMemcpy(fit, dFit.p, (size_t)N * FIT_COLS * sizeof(double), hipMemcpyDeviceToHost));
-    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)nc; }
-    return 0;
+    return item_subject_table(S, Q, FIT_COLS, "the person fit", [&](auto M, auto real, auto masked) {
+        return weighting == SCORE_LIKELIHOOD ? &fit_kernel<decltype(M)::value, decltype(real), true, decltype(masked)::value>
+                                             : &fit_kernel<decltype(M)::value, decltype(real), false, decltype(masked)::value>; }, fit, out4);
 }
 // Item fit (erm_ifit_kernels.hpp; include/ertirt.h: erm_get_item_fit, erm_item_fit): the one place that launches item_fit_kernel and its two reduction kernels;
 // fit [J][6].  The subjects go through in chunks of whole blocks of IFIT_BLOCK (ifit_chunk on item_pass_chunk's budget for the 48 J bytes of a subject's workspace
@@ -494,11 +485,7 @@ static int item_itemfit(const ItemSource& S, int Q, double* fit, double* out4)
                        model_traits(S.D.model).rt ? 1 : 0, dFit.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(S.stream));
-    unsigned long long n_coarse = 0;
-    if (int rc = coarse.count(S.stream, &n_coarse)) return rc;
-    HIPCHK(hipMemcpy(fit, dFit.p, (size_t)J * IFIT_COLS * sizeof(double), hipMemcpyDeviceToHost));
-    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)n_coarse; }
-    return 0;
+    return item_finish(S, Q, coarse, fit, dFit.p, (size_t)J * IFIT_COLS * sizeof(double), out4);
 }
 // Plausible values (erm_pv_kernels.hpp; include/ertirt.h: erm_get_plausible_values, erm_plausible_values): the one place that launches pv_kernel.  The subjects
 // go through in chunks whose draws (two doubles and an int each) fit item_pass_chunk's budget whatever K (ERM_PV_CHUNK caps the chunk length); a chunk's draws are
@@ -522,15 +509,7 @@ static int item_pv(const ItemSource& S, int Q, int64_t K, uint64_t seed, double*
         HIPCHK(hipMemcpy2D(pv + c0, (size_t)N * sizeof(double), dPv.p, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), (size_t)(2 * K), hipMemcpyDeviceToHost));
         if (node) HIPCHK(hipMemcpy2D(node + c0, (size_t)N * sizeof(int), dNode.p, (size_t)nc * sizeof(int), (size_t)nc * sizeof(int), (size_t)K, hipMemcpyDeviceToHost));
     }
-    unsigned long long n_coarse = 0;
-    if (int rc = flags.count(S.stream, &n_coarse)) return rc;
-    if (coarse) {
-        std::vector<unsigned int> flag((size_t)N);
-        HIPCHK(hipMemcpy(flag.data(), flags.flags(), flag.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < N; ++i) coarse[i] = (int32_t)flag[(size_t)i];
-    }
-    if (out4) { out4[0] = (double)N; out4[1] = (double)S.n_rows; out4[2] = (double)Q; out4[3] = (double)n_coarse; }
-    return 0;
+    return item_finish(S, Q, flags, coarse, flags.flags(), (size_t)N * sizeof(unsigned int), out4);      // (a flag is 0 or 1: the same four bytes as the caller's int32)
 }
 
 }  // namespace

@@ -216,7 +216,7 @@ struct EngineBase {
     virtual int get_waic(double* out8) = 0;
     virtual int64_t pointwise_units() const = 0;
     virtual int get_pointwise(double* lppd_u, double* p_u) = 0;
-    // the passes over the item trace (erm_item_pass.hpp: marginal WAIC and LOO, scores, plausible values): this engine's resident data set as the source of `pass`,
+    // the passes over the item trace (erm_item_pass.hpp: marginal WAIC and LOO, scores, plausible values, person fit, item fit): this engine's resident data set as the source of `pass`,
     // or the refusal in the pass's words; S.rows == NULL: with its own post-burn-in rows, read in place (the farm hands chain 0 a table of the rows of all chains
     // on its device).  And the resident item trace.
     virtual int item_source(int pass, ItemSource& S) = 0;
@@ -1722,7 +1722,7 @@ static int debug_upload(const double* x, int64_t n_draw, int64_t n_col, int32_t 
 }
 
 #include "erm_diagnostics.hpp"             // the convergence diagnostics' host path: the engine's, the farm's and the debug entries'
-#include "erm_item_pass.hpp"               // the item-trace passes' host path: marginal WAIC and LOO, scores, plausible values
+#include "erm_item_pass.hpp"               // the six item-trace passes' host path: marginal WAIC and LOO, scores, plausible values, person fit, item fit
 
 namespace {
 // an engine as the source of a pass (EngineBase::item_source)
@@ -1732,7 +1732,7 @@ template <typename real> int Engine<real>::item_source(int pass, ItemSource& S)
     if (poisoned) return fail(ERM_ERR_STATE, "a previous erm_run failed part-way: the state is undefined until erm_set_state");
     if (!has_data) return fail(ERM_ERR_STATE, "no data set is resident");
     if (!S.rows) {
-        if (post_rows < item_pass_facts(pass).engine_rows) return fail(ERM_ERR_STATE, item_pass_needs_rows(pass));
+        if (post_rows < ITEM_PASSES[pass].engine_rows) return fail(ERM_ERR_STATE, item_pass_needs_rows(pass));
         S.rows = dTrItem.as<double>() + (size_t)(rows_done - post_rows) * item_trace_width(); S.n_rows = post_rows;
     }
     HIPCHK(hipSetDevice(cfg.device));
@@ -1752,7 +1752,7 @@ static int pv_entry_args(int32_t n_nodes, int32_t n_draws, const double* pv, int
     if (!pv_draws_ok(n_draws)) return fail(ERM_ERR_ARG, "n_draws must be in " + std::to_string(PV_DRAWS_MIN) + " .. " + std::to_string(PV_DRAWS_MAX));
     return 0;
 }
-// erm_get_* (H = erm_handle) and erm_farm_get_* (H = erm_farm_handle) of the four passes: the checks, the source, the product
+// erm_get_* (H = erm_handle) and erm_farm_get_* (H = erm_farm_handle) of the six passes: the checks, the source, the product
 template <typename H> static int get_marginal_waic(H h, int32_t n_nodes, double* out10, double* lppd_u, double* p_u, int family = FAMILY_GAUSSIAN)
 {
     int Q = 0;
@@ -1800,6 +1800,46 @@ template <typename H> static int get_plausible_values(H h,int32_t n_nodes, int32
     if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
     if (int rc = item_source(h, PASS_PV, S)) return rc;
     return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
+}
+// The caller-data entries of a pass, erm_X and erm_X_masked, are ONE body: the model, the node count, the pass's own checks, the source, the product.  what names
+// the entry in the allocation messages; obs may be NULL (complete data), and n_obs (may be NULL) is then n_item for every subject once the pass has succeeded.
+static int obs_all(int rc, const CallerData& d, const uint8_t* obs, int32_t* n_obs)
+{
+    if (rc == 0 && !obs && n_obs) for (int64_t i = 0; i < d.n_subj; ++i) n_obs[i] = d.n_item;
+    return rc;
+}
+static int caller_marginal_loglik(const CallerData& d, const char* what, const uint8_t* obs, int32_t* n_obs, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u,
+                                  int family = FAMILY_GAUSSIAN, double q_rt = 0.0)
+{
+    if (int rc = marg_refuse_model(d.model, family)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    ItemSource S;
+    if (int rc = item_source(what, d, out10 || lppd_u || p_u ? 2 : 1, "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S, family, q_rt, obs, n_obs)) return rc;
+    return obs_all(item_waic(S, Q, l, out10, lppd_u, p_u), d, obs, n_obs);
+}
+// (the scores' and the person fit's: product is item_scores or item_fit)
+template <typename Product>
+static int caller_subject_table(const CallerData& d, const char* what, const uint8_t* obs, int32_t* n_obs, int32_t n_nodes, int32_t weighting, double* table, double* out4, Product&& product)
+{
+    if (int rc = marg_refuse_model(d.model)) return rc;
+    int Q = 0;
+    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
+    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
+    if (!table) return fail(ERM_ERR_ARG, "out is NULL");
+    ItemSource S;
+    if (int rc = item_source(what, d, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN, 0.0, obs, n_obs)) return rc;
+    return obs_all(product(S, Q, weighting, table, out4), d, obs, n_obs);
+}
+static int caller_plausible_values(const CallerData& d, const char* what, const uint8_t* obs, int32_t* n_obs, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node,
+                                   int32_t* coarse, double* out4)
+{
+    if (int rc = marg_refuse_model(d.model)) return rc;
+    int Q = 0;
+    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
+    ItemSource S;
+    if (int rc = item_source(what, d, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN, 0.0, obs, n_obs)) return rc;
+    return obs_all(item_pv(S, Q, n_draws, seed, pv, node, coarse, out4), d, obs, n_obs);
 }
 }  // namespace
 
@@ -2095,29 +2135,25 @@ const char* erm_last_error(void) { return g_err.c_str(); }
 const char* erm_version(void) { return "ertirt-amd 0.4.0 (gfx950)"; }
 int erm_abi_version(void) { return ERM_ABI_VERSION; }
 
+// ---- the passes on caller-supplied data and rows (the bodies: caller_* above).  An entry with an observed mask given obs == NULL is its complete
+// sibling, by that name in the allocation messages too.
 int erm_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                         int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u)
 {
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    ItemSource S;
-    if (int rc = item_source("erm_marginal_loglik's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, out10 || lppd_u || p_u ? 2 : 1,
-                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S)) return rc;
-    return item_waic(S, Q, l, out10, lppd_u, p_u);
+    return caller_marginal_loglik({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows}, "erm_marginal_loglik's inputs", nullptr, nullptr, n_nodes, l, out10, lppd_u, p_u);
 }
-
-// LatentQr's: the same path with the quantile family's checks and the caller's q_rt
+int erm_marginal_loglik_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                               const double* rows, int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u, int32_t* n_obs)
+{
+    return caller_marginal_loglik({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows},
+                                  obs ? "erm_marginal_loglik_masked's inputs" : "erm_marginal_loglik's inputs", obs, n_obs, n_nodes, l, out10, lppd_u, p_u);
+}
+// LatentQr's: the same body with the quantile family's checks and the caller's q_rt
 int erm_quantile_marginal_loglik(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                                  int64_t n_rows, double q_rt, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u)
 {
-    if (int rc = marg_refuse_model(model, FAMILY_QUANTILE)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    ItemSource S;
-    if (int rc = item_source("erm_quantile_marginal_loglik's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, out10 || lppd_u || p_u ? 2 : 1,
-                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S, FAMILY_QUANTILE, q_rt)) return rc;
-    return item_waic(S, Q, l, out10, lppd_u, p_u);
+    return caller_marginal_loglik({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows},
+                                  "erm_quantile_marginal_loglik's inputs", nullptr, nullptr, n_nodes, l, out10, lppd_u, p_u, FAMILY_QUANTILE, q_rt);
 }
 
 int erm_psis_loo(int device, const double* l, int64_t n_subj, int64_t n_rows, double* out12, double* pw, double* lw)
@@ -2145,117 +2181,42 @@ int erm_psis_loo(int device, const double* l, int64_t n_subj, int64_t n_rows, do
 int erm_score(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
               int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4)
 {
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
-    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
-    ItemSource S;
-    if (int rc = item_source("erm_score's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S)) return rc;
-    return item_scores(S, Q, weighting, score, out4);
+    return caller_subject_table({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows}, "erm_score's inputs", nullptr, nullptr, n_nodes, weighting, score, out4, item_scores);
+}
+int erm_score_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
+                     const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4, int32_t* n_obs)
+{
+    return caller_subject_table({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows},
+                                obs ? "erm_score_masked's inputs" : "erm_score's inputs", obs, n_obs, n_nodes, weighting, score, out4, item_scores);
 }
 
 int erm_plausible_values(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                          int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4)
 {
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
-    ItemSource S;
-    if (int rc = item_source("erm_plausible_values' inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S)) return rc;
-    return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
+    return caller_plausible_values({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows}, "erm_plausible_values' inputs", nullptr, nullptr, n_nodes, n_draws, seed, pv, node, coarse, out4);
 }
-
-// ---- incomplete response patterns: the three caller-data entries with an observed mask.  obs == NULL is the complete entry itself.
-static void obs_all(int64_t n_subj, int32_t n_item, int32_t* n_obs) { if (n_obs) for (int64_t i = 0; i < n_subj; ++i) n_obs[i] = n_item; }
-int erm_marginal_loglik_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
-                               const double* rows, int64_t n_rows, int32_t n_nodes, double* l, double* out10, double* lppd_u, double* p_u, int32_t* n_obs)
-{
-    if (!obs) {
-        if (int rc = erm_marginal_loglik(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, l, out10, lppd_u, p_u)) return rc;
-        obs_all(n_subj, n_item, n_obs);
-        return 0;
-    }
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    ItemSource S;
-    if (int rc = item_source("erm_marginal_loglik_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, out10 || lppd_u || p_u ? 2 : 1,
-                             "n_rows must be at least 1 (at least 2 for the WAIC outputs)", S, FAMILY_GAUSSIAN, 0.0, obs, n_obs)) return rc;
-    return item_waic(S, Q, l, out10, lppd_u, p_u);
-}
-
-int erm_score_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
-                     const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* score, double* out4, int32_t* n_obs)
-{
-    if (!obs) {
-        if (int rc = erm_score(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, weighting, score, out4)) return rc;
-        obs_all(n_subj, n_item, n_obs);
-        return 0;
-    }
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
-    if (!score) return fail(ERM_ERR_ARG, "out is NULL");
-    ItemSource S;
-    if (int rc = item_source("erm_score_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN, 0.0,
-                             obs, n_obs)) return rc;
-    return item_scores(S, Q, weighting, score, out4);
-}
-
 int erm_plausible_values_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
                                 const double* rows, int64_t n_rows, int32_t n_nodes, int32_t n_draws, uint64_t seed, double* pv, int32_t* node, int32_t* coarse, double* out4,
                                 int32_t* n_obs)
 {
-    if (!obs) {
-        if (int rc = erm_plausible_values(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, n_draws, seed, pv, node, coarse, out4)) return rc;
-        obs_all(n_subj, n_item, n_obs);
-        return 0;
-    }
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = pv_entry_args(n_nodes, n_draws, pv, &Q)) return rc;
-    ItemSource S;
-    if (int rc = item_source("erm_plausible_values_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S,
-                             FAMILY_GAUSSIAN, 0.0, obs, n_obs)) return rc;
-    return item_pv(S, Q, n_draws, seed, pv, node, coarse, out4);
+    return caller_plausible_values({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows},
+                                   obs ? "erm_plausible_values_masked's inputs" : "erm_plausible_values' inputs", obs, n_obs, n_nodes, n_draws, seed, pv, node, coarse, out4);
 }
 
-// ---- person fit on caller-supplied data and rows, complete or with an observed mask
+// person fit
 int erm_person_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const double* rows,
                    int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4)
 {
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
-    if (!fit) return fail(ERM_ERR_ARG, "out is NULL");
-    ItemSource S;
-    if (int rc = item_source("erm_person_fit's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S)) return rc;
-    return item_fit(S, Q, weighting, fit, out4);
+    return caller_subject_table({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows}, "erm_person_fit's inputs", nullptr, nullptr, n_nodes, weighting, fit, out4, item_fit);
 }
-
 int erm_person_fit_masked(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
                           const double* rows, int64_t n_rows, int32_t n_nodes, int32_t weighting, double* fit, double* out4, int32_t* n_obs)
 {
-    if (!obs) {
-        if (int rc = erm_person_fit(device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, n_nodes, weighting, fit, out4)) return rc;
-        obs_all(n_subj, n_item, n_obs);
-        return 0;
-    }
-    if (int rc = marg_refuse_model(model)) return rc;
-    int Q = 0;
-    if (int rc = marg_nodes(n_nodes, &Q)) return rc;
-    if (!score_weighting_ok(weighting)) return fail(ERM_ERR_ARG, "weighting must be ERM_SCORE_EQUAL or ERM_SCORE_LIKELIHOOD");
-    if (!fit) return fail(ERM_ERR_ARG, "out is NULL");
-    ItemSource S;
-    if (int rc = item_source("erm_person_fit_masked's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN,
-                             0.0, obs, n_obs)) return rc;
-    return item_fit(S, Q, weighting, fit, out4);
+    return caller_subject_table({device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows},
+                                obs ? "erm_person_fit_masked's inputs" : "erm_person_fit's inputs", obs, n_obs, n_nodes, weighting, fit, out4, item_fit);
 }
 
-// ---- item fit on caller-supplied data and rows; obs may be NULL (complete data: the unmasked kernel)
+// item fit: one entry, obs may be NULL (complete data: the unmasked kernel); it reports no n_obs
 int erm_item_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t n_feat, const uint8_t* Y, const double* logT, const double* X, const uint8_t* obs,
                  const double* rows, int64_t n_rows, int32_t n_nodes, double* fit, double* out4)
 {
@@ -2264,8 +2225,8 @@ int erm_item_fit(int device, int model, int64_t n_subj, int32_t n_item, int32_t 
     if (int rc = marg_nodes(n_nodes, &Q)) return rc;
     if (!fit) return fail(ERM_ERR_ARG, "out is NULL");
     ItemSource S;
-    if (int rc = item_source("erm_item_fit's inputs", device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows, 1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN, 0.0,
-                             obs, nullptr)) return rc;
+    if (int rc = item_source("erm_item_fit's inputs", {device, model, n_subj, n_item, n_feat, Y, logT, X, rows, n_rows},
+                                                      1, "n_rows must be at least 1", S, FAMILY_GAUSSIAN, 0.0, obs, nullptr)) return rc;
     return item_itemfit(S, Q, fit, out4);
 }
 

@@ -275,12 +275,12 @@ def test_symbols_abi_and_words(tmp_path):
     assert "ERM_FIT_LZ = 0, ERM_FIT_P_RESP = 1, ERM_FIT_LTZ = 2, ERM_FIT_P_TIME = 3, ERM_FIT_ROW_ESS = 4, ERM_FIT_COARSE = 5, ERM_FIT_COLS = 6" in header
     for name in ("getPersonFit", "personFit", "personFitHost", "OutputPersonFit"):
         assert name in P.__all__ and hasattr(P, name)
-    # the fifth pass's refusals, through the header's own accessor
+    # the fifth pass's refusals, from its row of the header's table
     src = tmp_path / "words.cpp"
-    src.write_text('#include <cstdio>\n#include "erm_item_pass.hpp"\nint main() { using namespace erm; static_assert(PASS_FIT == 4 && N_ITEM_PASSES == 4, "");\n'
-                   'printf("%s\\n%s\\n%s\\n%d %d\\n", item_pass_facts(PASS_FIT).noun, item_pass_on_shard(PASS_FIT).c_str(), item_pass_needs_rows(PASS_FIT).c_str(),\n'
-                   'item_pass_facts(PASS_FIT).engine_rows, item_pass_facts(PASS_FIT).farm_rows);\n'
-                   'return item_pass_facts(PASS_SCORES).noun == ITEM_PASSES[PASS_SCORES].noun ? 0 : 1; }\n')
+    src.write_text('#include <cstdio>\n#include "erm_item_pass.hpp"\nint main() { using namespace erm; static_assert(PASS_FIT == 4 && PASS_ITEM_FIT == 5 && N_ITEM_PASSES == 6, "");\n'
+                   'printf("%s\\n%s\\n%s\\n%d %d\\n", ITEM_PASSES[PASS_FIT].noun, item_pass_on_shard(PASS_FIT).c_str(), item_pass_needs_rows(PASS_FIT).c_str(),\n'
+                   'ITEM_PASSES[PASS_FIT].engine_rows, ITEM_PASSES[PASS_FIT].farm_rows);\n'
+                   'return 0; }\n')
     exe = str(tmp_path / "words")
     subprocess.run(["g++", "-std=c++17", "-O1", "-fsanitize=undefined", "-fno-sanitize-recover=all", "-ftrapv", "-I", INC, str(src), "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")

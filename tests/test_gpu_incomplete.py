@@ -122,25 +122,44 @@ def test_all_cells_observed_is_the_unmasked_entry_bit_for_bit(model, J):
 
 
 def test_obs_null_is_the_unmasked_entry_bit_for_bit():
+    """Each masked entry given obs = NULL through ctypes against its complete sibling called the same way: every output, every bit, and n_obs = n_item."""
     L = _pkg()._lib
     lib = L.load()
     N, J, F, R, Q, K = 33, 9, 3, 3, 61, 5
     Y, logT, X, rows, _ = ou.problem("rtirt", N, J, R, seed=301)
     ref = _products(L, 1, Y, logT, X, rows, K=K, seed=11)
     Yf, lf, Xf = np.asfortranarray(Y), np.asfortranarray(logT), np.asfortranarray(X)
-    head = (0, 1, N, J, F, Yf.ctypes.data, lf.ctypes.data, Xf.ctypes.data, None, rows.ctypes.data, R)
+    data = (0, 1, N, J, F, Yf.ctypes.data, lf.ctypes.data, Xf.ctypes.data)
+    plain, head = (*data, rows.ctypes.data, R), (*data, None, rows.ctypes.data, R)
+    ptrs = lambda bufs: [a.ctypes.data for a in bufs]
+    same = lambda got, want: all(g.tobytes() == w.tobytes() for g, w in zip(got, want))
     n_obs = np.zeros(N, dtype=np.int32)
+    # l with the WAIC outputs (3 rows allow them): l, out10, lppd_u, p_u
+    want, got = ([np.zeros((N, R), order="F"), np.zeros(10), np.zeros(N), np.zeros(N)] for _ in range(2))
+    assert lib.erm_marginal_loglik(*plain, Q, *ptrs(want)) == 0
+    assert lib.erm_marginal_loglik_masked(*head, Q, *ptrs(got), n_obs.ctypes.data) == 0
+    assert same(got, want) and np.array_equal(got[0], ref["l"]) and list(want[1][5:7]) == [N, R] and np.all(n_obs == J)
     l = np.empty((N, R), order="F")
-    assert lib.erm_marginal_loglik_masked(*head, Q, l.ctypes.data, None, None, None, n_obs.ctypes.data) == 0
-    assert np.array_equal(l, ref["l"]) and np.all(n_obs == J)
+    assert lib.erm_marginal_loglik_masked(*head, Q, l.ctypes.data, None, None, None, None) == 0 and np.array_equal(l, ref["l"])      # l alone, n_obs may be NULL
+    # the scores under both weightings: score, out4
     for w, name in enumerate(WEIGHTINGS):
-        sc, o4 = np.empty((7, N)), np.empty(4)
-        assert lib.erm_score_masked(*head, Q, w, sc.ctypes.data, o4.ctypes.data, None) == 0                   # n_obs may be NULL
-        assert all(np.array_equal(sc[k], np.asarray(ref[f"{name}.{c}"], dtype=np.float64), equal_nan=True) for k, c in enumerate(SCORE_KEYS)) and list(o4[:3]) == [N, R, Q]
-    pv, node, coarse, o4 = np.empty((2, K, N)), np.empty((K, N), dtype=np.int32), np.empty(N, dtype=np.int32), np.empty(4)
+        want, got = ([np.zeros((7, N)), np.zeros(4)] for _ in range(2))
+        n_obs[:] = 0
+        assert lib.erm_score(*plain, Q, w, *ptrs(want)) == 0
+        assert lib.erm_score_masked(*head, Q, w, *ptrs(got), n_obs.ctypes.data) == 0
+        assert same(got, want) and np.all(n_obs == J) and list(got[1][:3]) == [N, R, Q]
+        sc = got[0]
+        assert all(np.array_equal(sc[k], np.asarray(ref[f"{name}.{c}"], dtype=np.float64), equal_nan=True) for k, c in enumerate(SCORE_KEYS))
+        got = [np.zeros((7, N)), np.zeros(4)]
+        assert lib.erm_score_masked(*head, Q, w, *ptrs(got), None) == 0 and same(got, want)                 # n_obs may be NULL
+    # the plausible values: pv, node, coarse, out4
+    want, got = ([np.zeros((2, K, N)), np.zeros((K, N), dtype=np.int32), np.full(N, -1, dtype=np.int32), np.zeros(4)] for _ in range(2))
     n_obs[:] = 0
-    assert lib.erm_plausible_values_masked(*head, Q, K, 11, pv.ctypes.data, node.ctypes.data, coarse.ctypes.data, o4.ctypes.data, n_obs.ctypes.data) == 0
-    assert np.array_equal(pv[0].T, ref["pv.theta"]) and np.array_equal(pv[1].T, ref["pv.zeta"]) and np.array_equal(node.T, ref["pv.node"]) and np.all(n_obs == J)
+    assert lib.erm_plausible_values(*plain, Q, K, 11, *ptrs(want)) == 0
+    assert lib.erm_plausible_values_masked(*head, Q, K, 11, *ptrs(got), n_obs.ctypes.data) == 0
+    assert same(got, want) and np.all(n_obs == J) and list(got[3][:3]) == [N, R, Q] and set(got[2].tolist()) <= {0, 1}
+    pv, node = got[0], got[1]
+    assert np.array_equal(pv[0].T, ref["pv.theta"]) and np.array_equal(pv[1].T, ref["pv.zeta"]) and np.array_equal(node.T, ref["pv.node"])
 
 
 # ------------------------------------------------------------------------------------------------------------ 4. the reduced data set

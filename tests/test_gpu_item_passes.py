@@ -1,5 +1,5 @@
-"""The two refusals the four item-trace passes share through their one host path (csrc/erm_item_pass.hpp) and that no other test reaches for these
-entries, each pass from the engine's and from the farm's entry:
+"""The two refusals the six item-trace passes share through their one host path (csrc/erm_item_pass.hpp), on the first four of the table -- the
+marginal WAIC and LOO, the scores, the plausible values --, for whose entries no other test reaches them; each pass from the engine's and from the farm's entry:
   - an engine without a data set: ERM_ERR_STATE (-3), "no data set is resident";
   - a farm whose chains have recorded different numbers of rows (one chain's borrowed engine ran a sweep further): -3, "rows recorded where chain 0 has".
 After either refusal the engine or the farm runs on, and the same call succeeds.

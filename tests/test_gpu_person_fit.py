@@ -92,6 +92,23 @@ def test_masks_bit_for_bit(model):
     assert _same_bits(got, _fit(model, Y, logT, X, rows, obs=other), slice(0, 1), slice(0, 1))
 
 
+def test_obs_null_is_the_unmasked_entry_bit_for_bit():
+    """erm_person_fit_masked given obs = NULL through ctypes: erm_person_fit's outputs, every bit, and n_obs = n_item.  One full tile of 32 and one subject."""
+    lib = _pkg()._lib.load()
+    N, J, F, R, Q = 33, 5, 3, 2, 3
+    Y, logT, X, rows, _ = ou.problem("rtirt", N, J, R, seed=301)
+    Yf, lf, Xf = np.asfortranarray(Y), np.asfortranarray(logT), np.asfortranarray(X)
+    data = (0, 1, N, J, F, Yf.ctypes.data, lf.ctypes.data, Xf.ctypes.data)
+    for w in (0, 1):
+        ref, ref4, got, got4 = np.empty((6, N)), np.empty(4), np.empty((6, N)), np.empty(4)
+        n_obs = np.zeros(N, dtype=np.int32)
+        assert lib.erm_person_fit(*data, rows.ctypes.data, R, Q, w, ref.ctypes.data, ref4.ctypes.data) == 0
+        assert lib.erm_person_fit_masked(*data, None, rows.ctypes.data, R, Q, w, got.ctypes.data, got4.ctypes.data, n_obs.ctypes.data) == 0
+        assert got.tobytes() == ref.tobytes() and got4.tobytes() == ref4.tobytes() and list(ref4[:3]) == [N, R, Q] and np.all(n_obs == J)
+        assert lib.erm_person_fit_masked(*data, None, rows.ctypes.data, R, Q, w, got.ctypes.data, got4.ctypes.data, None) == 0      # n_obs may be NULL
+        assert got.tobytes() == ref.tobytes()
+
+
 @pytest.mark.parametrize("model", ["rtirt", "latent"])
 def test_a_subjects_fit_depends_on_its_own_data_only(model):
     rows = mu.make_rows(model, 9, 3, 4, seed=31)

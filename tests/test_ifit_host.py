@@ -197,12 +197,12 @@ def test_symbols_abi_and_words(tmp_path):
     assert "ERM_IFIT_INFIT = 0, ERM_IFIT_OUTFIT = 1, ERM_IFIT_RESP_Z = 2, ERM_IFIT_RT_MSQ = 3, ERM_IFIT_RT_Z = 4, ERM_IFIT_N_OBS = 5, ERM_IFIT_COLS = 6" in header
     for name in ("getItemFit", "itemFit", "itemFitHost", "OutputItemFit"):
         assert name in P.__all__ and hasattr(P, name)
-    # the sixth pass's refusals, through the header's own accessor; the four passes of the table and the fifth keep their facts
+    # the sixth pass's refusals, from its row of the header's table; the fifth keeps its noun
     src = tmp_path / "words.cpp"
-    src.write_text('#include <cstdio>\n#include "erm_item_pass.hpp"\nint main() { using namespace erm; static_assert(PASS_ITEM_FIT == 5 && PASS_FIT == 4 && N_ITEM_PASSES == 4, "");\n'
-                   'printf("%s\\n%s\\n%s\\n%d %d\\n%s\\n", item_pass_facts(PASS_ITEM_FIT).noun, item_pass_on_shard(PASS_ITEM_FIT).c_str(), item_pass_needs_rows(PASS_ITEM_FIT).c_str(),\n'
-                   'item_pass_facts(PASS_ITEM_FIT).engine_rows, item_pass_facts(PASS_ITEM_FIT).farm_rows, item_pass_facts(PASS_FIT).noun);\n'
-                   'return item_pass_facts(PASS_SCORES).noun == ITEM_PASSES[PASS_SCORES].noun ? 0 : 1; }\n')
+    src.write_text('#include <cstdio>\n#include "erm_item_pass.hpp"\nint main() { using namespace erm; static_assert(PASS_FIT == 4 && PASS_ITEM_FIT == 5 && N_ITEM_PASSES == 6, "");\n'
+                   'printf("%s\\n%s\\n%s\\n%d %d\\n%s\\n", ITEM_PASSES[PASS_ITEM_FIT].noun, item_pass_on_shard(PASS_ITEM_FIT).c_str(), item_pass_needs_rows(PASS_ITEM_FIT).c_str(),\n'
+                   'ITEM_PASSES[PASS_ITEM_FIT].engine_rows, ITEM_PASSES[PASS_ITEM_FIT].farm_rows, ITEM_PASSES[PASS_FIT].noun);\n'
+                   'return 0; }\n')
     exe = str(tmp_path / "words")
     subprocess.run(UBSAN + [str(src), "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")

@@ -1,4 +1,4 @@
-"""The plain C++ half of csrc/erm_item_pass.hpp on the CPU: the header the four item-trace passes' host path is built on, compiled by g++ with
+"""The plain C++ half of csrc/erm_item_pass.hpp on the CPU: the header the six item-trace passes' host path is built on, compiled by g++ with
 UndefinedBehaviorSanitizer and -ftrapv into tests/item_pass_check.cpp.
   - item_pass_chunk against Python integers at the corners of its two callers: the plausible values' 20 K bytes per subject at K = 1 and K = 4096, PSIS-LOO's 8 S
     bytes at its row maximum and capped, a subject that exceeds the budget alone, a large N with a negative cap.
@@ -50,12 +50,14 @@ WORDS = [  # noun, on a shard, (fewest rows of an engine, its refusal), (fewest 
     ("the scores", "the scores are" + SHARD, (1, "the scores need at least one post-burn-in row"), (1, "the scores need at least one post-burn-in row")),
     ("the plausible values", "the plausible values are" + SHARD, (1, "the plausible values need at least one post-burn-in row"),
      (1, "the plausible values need at least one post-burn-in row")),
+    ("the person fit", "the person fit is" + SHARD, (1, "the person fit needs at least one post-burn-in row"), (1, "the person fit needs at least one post-burn-in row")),
+    ("the item fit", "the item fit is" + SHARD, (1, "the item fit needs at least one post-burn-in row"), (1, "the item fit needs at least one post-burn-in row")),
 ]
 
 
 def test_refusal_words_are_the_literal_strings(exe):
     out = _run(exe, ["words"])
-    assert len(out) == 4 * len(WORDS)
+    assert len(WORDS) == 6 and len(out) == 4 * len(WORDS)
     for p, (noun, shard, engine, farm) in enumerate(WORDS):
         got = out[4 * p:4 * p + 4]
         assert got[0] == noun and got[1] == shard
